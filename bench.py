@@ -8,10 +8,15 @@ camera path (D = --frames-per-launch, 32 at N = 1 for the headline; every frame 
 hot path, Scene::render -> the HIP march kernel, over the synthetic frame, the sky already resident in
 HBM).  `value` = frames x W x H / the timed region's wall time; `ms_per_step` is per batch and
 `ms_per_frame` per frame.  Default arithmetic: BH_MATH_EXACT, the bit-exact path (the only one that can
-meet |delta| < 1e-4); RGBA16F col + blackout targets as north_star asks.  Besides the
-headline the line carries `single_frame` (one bh_render per frame, the reference's one Scene::render
-per redraw, src/state.rs:270-279) and `orbit` (every frame its own camera), untimed for `value`, and
-`clock`: the shader clock measured inside the timed launches (bh_set_clock_probe).
+meet |delta| < 1e-4); RGBA16F col + blackout targets as north_star asks.  The line also
+carries `clock`: the shader clock measured inside the timed launches (bh_set_clock_probe).
+
+A plain run sets up, warms up, times the K steps and prints the line.  `--full` adds what takes runs of
+its own, untimed for `value`: `single_frame` (one bh_render per frame, the reference's one Scene::render
+per redraw, src/state.rs:270-279) and `orbit` (every frame its own camera), the step-count launch behind
+`roofline` and `kernel.sum_*`, and `cpu_baseline` / `parity` (the CPU oracle over the whole frame); those
+keys are null or absent without it.  `--dump-outputs DIR` writes what the last timed step rendered
+(dump_outputs below); the inputs are seeded, so equal arguments give equal files from run to run.
 
 Workloads (--workload):
   strong   (default) north_star's fixed 4096x2048 frame, split over the N GPUs (strong scaling; at
@@ -24,7 +29,7 @@ per RGBA16F pixel), the batch's shards are gathered to rank 0 (one collective pe
 the next batch's render), and rank 0 unpacks BOTH targets, col and blackout_col, row-major.  Every timed
 step includes render, gather and unpack; the line carries a per-rank breakdown (`ranks`).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload strong|config4|weak]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload strong|config4|weak] [--full] [--dump-outputs DIR]
 
 Without torchrun, `--gpus N` (N > 1) starts its own N ranks (child processes, before anything
 touches a GPU) and exits non-zero unless all N ranks finish; the ranks never fall back to fewer GPUs.
@@ -69,8 +74,15 @@ def parse(argv=None):
     p.add_argument("--settle-ms", type=float, default=0.0,
                    help="optional untimed power-state settle before the warm-up: full launches of the workload "
                         "for this many ms (DESIGN.md §6); 0 = none (the warm-up batches cover the clock ramp)")
+    p.add_argument("--full", action="store_true",
+                   help="after the timed steps also run everything beside the headline: the single_frame / orbit "
+                        "legs, the step-count launch behind `roofline` and kernel.sum_*, and the cpu_baseline / "
+                        "parity leg (a plain run sets up, warms up, times the steps and prints the line)")
+    p.add_argument("--dump-outputs", metavar="DIR", default="",
+                   help="after the timed steps write what the last timed step rendered -- both targets of its "
+                        "frames, at a fixed seeded sample of pixels -- as float32 DIR/<name>.npy (at most 48 MiB in all)")
     p.add_argument("--no-extra", action="store_true",
-                   help="skip the single_frame / orbit legs (N = 1) that follow the timed region")
+                   help="--full: skip the single_frame / orbit legs (N = 1) that follow the timed region")
     p.add_argument("--workload", choices=["strong", "config4", "weak"], default="strong")
     p.add_argument("--config", type=int, choices=[1, 2, 3, 4, 5], default=0,
                    help="BASELINE.json configs[N-1]: 1 = 256x256 cap 64 no surfaces camera A, 2 = 1920x1080 cap 256 "
@@ -91,7 +103,7 @@ def parse(argv=None):
                         "(an offline camera path: every frame of a multi-frame launch has its own camera)")
     p.add_argument("--surfaces", choices=["on", "off"], default="on",
                    help="off = scene_flags 0 (no disc, no markers: BASELINE config 1's scene)")
-    p.add_argument("--no-cpu", action="store_true", help="skip the cpu_baseline / parity leg")
+    p.add_argument("--no-cpu", action="store_true", help="--full: skip the cpu_baseline / parity leg")
     p.add_argument("--cpu-threads", type=int, default=0, help="0 = every CPU this process may use")
     p.add_argument("--cpu-reps", type=int, default=3)
     p.add_argument("--graph", action="store_true",
@@ -589,7 +601,7 @@ def main() -> int:
             scene.render_frames([buf[f * stride:(f + 1) * stride] for f in range(nf)], None, cameras=cams(nf, path),
                                 fmt=fmt, stream=stream, schedule=sched, **shard, **kw)
 
-    extra = not (args.no_extra or sharded or args.graph)
+    extra = args.full and not (args.no_extra or sharded or args.graph)
     n_orbit_frames = (args.warmup + args.steps) * D if args.camera_path == "orbit" else 0
     if extra:
         # _leg's two passes + the untimed one (orbit), and the one-frame orbit leg's two passes
@@ -670,6 +682,11 @@ def main() -> int:
         dist.barrier()
     elapsed = time.perf_counter() - t0
     scene.set_clock_probe(None)
+    if args.dump_outputs and rank == 0:
+        # before anything else renders into the targets: they hold the last timed step's D frames
+        beat("dump outputs")
+        dump_outputs(Path(args.dump_outputs), cols if not sharded else frame_cols, bos if not sharded else frame_bos,
+                     W, H, torch)
     per_rank = [elapsed]
     if sharded:
         t = torch.tensor([elapsed], dtype=torch.float64, device=dev)
@@ -766,23 +783,25 @@ def main() -> int:
     # (lower by the cycle fast-forward of the tile schedule) -- the roofline uses the latter.
     px_shape = (H, W) if not sharded else (stride * 64,)  # the layout's pixel index space
     nm = 1 if args.camera_path == "fixed" else D  # orbit: every frame of a launch (own cameras), averaged
-    frame_no[0] = 0
-    beat("step counts")
-    nrk_bufs = [torch.zeros(px_shape, dtype=torch.int16, device=dev) for _ in range(nm)]
-    steps_bufs = [torch.zeros(px_shape, dtype=torch.int16, device=dev) for _ in range(nm)]
-    launch(nm, dbg_n_rk=nrk_bufs, dbg_steps=steps_bufs)
-    torch.cuda.synchronize(dev)
-    sum_nrk = sum(int(b.cpu().numpy().view(np.uint16).astype(np.int64).sum()) for b in nrk_bufs) // nm
-    sum_steps = sum(int(b.cpu().numpy().view(np.uint16).astype(np.int64).sum()) for b in steps_bufs) // nm
+    sum_nrk = sum_steps = None  # a launch of its own: --full
+    if args.full:
+        frame_no[0] = 0
+        beat("step counts")
+        nrk_bufs = [torch.zeros(px_shape, dtype=torch.int16, device=dev) for _ in range(nm)]
+        steps_bufs = [torch.zeros(px_shape, dtype=torch.int16, device=dev) for _ in range(nm)]
+        launch(nm, dbg_n_rk=nrk_bufs, dbg_steps=steps_bufs)
+        torch.cuda.synchronize(dev)
+        sum_nrk = sum(int(b.cpu().numpy().view(np.uint16).astype(np.int64).sum()) for b in nrk_bufs) // nm
+        sum_steps = sum(int(b.cpu().numpy().view(np.uint16).astype(np.int64).sum()) for b in steps_bufs) // nm
 
     if rank == 0:
         frames = K * D
         value = W * H * frames / elapsed / 1e6
         # per launch: D frames' executed steps / the launch's average duration (HIP events)
-        achieved_tf = sum_steps * D * F_STEP[flags] / kern_avg_s / 1e12
+        achieved_tf = sum_steps * D * F_STEP[flags] / kern_avg_s / 1e12 if args.full else None
         alg_bytes = int(my_bytes * D) + sky.nbytes
         achieved_gbs = alg_bytes / kern_avg_s / 1e9
-        pmc = _pmc_entry(W, H, cap, args, n, D)
+        pmc = _pmc_entry(W, H, cap, args, n, D) if args.full else {}
         mhz = clock["mhz"] if clock else None
         result = {
             "metric": METRIC,
@@ -832,9 +851,11 @@ def main() -> int:
                        "avg_ms": round(kern_avg_s * 1e3, 5), "min_ms": round(float(kern_ms.min()), 5),
                        "max_ms": round(float(kern_ms.max()), 5), "ms_per_frame": round(kern_frame_s * 1e3, 5),
                        "sum_n_rk": sum_nrk, "sum_steps": sum_steps,
-                       "mean_n_rk": round(sum_nrk / (my_tiles * 64), 4), "frames_per_s": round(1.0 / kern_frame_s, 2),
+                       "mean_n_rk": round(sum_nrk / (my_tiles * 64), 4) if args.full else None,
+                       "frames_per_s": round(1.0 / kern_frame_s, 2),
                        "note": "avg/min/max over the K timed launches (HIP events on the render stream, the order "
-                               "kernel included); sum_n_rk / sum_steps per frame (this rank's tiles)"},
+                               "kernel included); sum_n_rk / sum_steps per frame (this rank's tiles), from a "
+                               "launch of their own (--full, else null)"},
             "clock": (dict(clock, stride=CLOCK_STRIDE,
                            note="shader clock during the timed launches: one wave in "
                                 f"{CLOCK_STRIDE} of the march kernel (spread over the XCDs; per_xcd_mhz by "
@@ -843,7 +864,8 @@ def main() -> int:
                                 "sum(shader ticks) / sum(100 MHz ticks) over those waves; peak_mhz is the clock "
                                 "the 157.3 TFLOP/s peak assumes") | {"peak_mhz": PEAK_MHZ}) if clock else None,
             "clock_settle": {"ms": round(settle_ms, 1), "frames": settle_frames} if args.settle_ms > 0 else None,
-            "roofline": {"bound": "valu", "achieved": round(achieved_tf, 3), "peak": PEAK_FP32_TFLOPS,
+            "roofline": None if not args.full else {
+                         "bound": "valu", "achieved": round(achieved_tf, 3), "peak": PEAK_FP32_TFLOPS,
                          "unit": "TFLOP/s", "frac": round(achieved_tf / PEAK_FP32_TFLOPS, 5),
                          "frac_at_measured_clock": (round(achieved_tf / (PEAK_FP32_TFLOPS * mhz / PEAK_MHZ), 5)
                                                     if mhz else None),
@@ -877,7 +899,7 @@ def main() -> int:
             result["per_rank_s"] = [round(x, 6) for x in per_rank]
             result["ranks"] = ranks
             result["partition_calibration"] = calibration
-        if args.no_cpu or sharded:
+        if not args.full or args.no_cpu or sharded:
             result["cpu_baseline"] = None
         else:
             beat("cpu baseline and parity")
@@ -934,6 +956,27 @@ def _leg(fn, launches: int, frames_per_launch: int, scene, clk_row, stream, dev,
             "kernel_ms_per_frame": round(float(k.sum()) / frames, 5),
             "mpix_s": round(W * H * frames / wall / 1e6, 3),
             "clock_mhz": bh.clock_mhz(clk_row.cpu().numpy())["mhz"]}
+
+
+DUMP_BYTES = 48 << 20  # --dump-outputs: float32 bytes of col.npy + blackout_col.npy together
+DUMP_SEED = 0xD0_0D5
+
+
+def dump_outputs(out: Path, cols, bos, W: int, H: int, torch) -> None:
+    """--dump-outputs: the frames of the last timed step as a caller holds them (both row-major targets
+    of each of its D frames), as float32: out/col.npy and out/blackout_col.npy of shape (D, P, 4), the
+    channels of P pixels of every frame in the targets' own order (fp16 and unorm8 words convert exactly),
+    and out/pixel_index.npy (float64, P), their y * W + x.  P is the whole frame if the two arrays then fit
+    in DUMP_BYTES, else that many pixels drawn without replacement by a fixed seed (sorted)."""
+    out.mkdir(parents=True, exist_ok=True)
+    D = len(cols)
+    P = min(W * H, DUMP_BYTES // (2 * D * 16))
+    idx = np.arange(W * H) if P == W * H else np.sort(np.random.default_rng(DUMP_SEED).choice(W * H, P, replace=False))
+    didx = torch.from_numpy(idx).to(cols[0].device)
+    for name, frames in (("col", cols), ("blackout_col", bos)):
+        a = np.stack([f.reshape(H * W, 4)[didx].to(torch.float32).cpu().numpy() for f in frames])
+        np.save(out / f"{name}.npy", a)
+    np.save(out / "pixel_index.npy", idx.astype(np.float64))
 
 
 def kernel_ns(args, tiles: int, D: int, cap: int, dev) -> str:

@@ -157,6 +157,98 @@ def test_steps_are_batches_and_the_settle_is_optional():
     assert bench.auto_frames_per_launch(8, 4096, 2048, 512) == 64
 
 
+def test_a_plain_run_is_the_default_and_full_is_an_option():
+    sys.path.insert(0, str(ROOT))
+    import bench
+    a = bench.parse(["--gpus", "1", "--steps", "7", "--warmup", "2"])
+    assert a.full is False and a.dump_outputs == "" and a.steps == 7 and a.warmup == 2
+    a = bench.parse(["--full", "--dump-outputs", "d"])
+    assert a.full is True and a.dump_outputs == "d"
+
+
+@pytest.mark.parametrize("W,H,D,dtype", [(24, 10, 3, "float16"), (4096, 2048, 32, "float16"), (40, 16, 2, "uint8")])
+def test_dump_outputs_writes_float32_samples_within_the_budget(tmp_path, W, H, D, dtype):
+    """--dump-outputs: every pixel of a small frame, a fixed sorted sample of a large one; float32 copies of
+    the targets' words at those pixels; the same files from call to call."""
+    torch = pytest.importorskip("torch")
+    import numpy as np
+    sys.path.insert(0, str(ROOT))
+    import bench
+    base = torch.arange(H * W * 4, dtype=torch.int32).reshape(H, W, 4) % 251
+    cols = [(base + f).to(getattr(torch, dtype)) for f in range(2)] * (D // 2) + [base.to(getattr(torch, dtype))] * (D % 2)
+    bos = [c // 2 for c in cols] if dtype == "uint8" else [c * 0.5 for c in cols]
+    bench.dump_outputs(tmp_path / "a", cols, bos, W, H, torch)
+    bench.dump_outputs(tmp_path / "b", cols, bos, W, H, torch)
+    files = sorted(p.name for p in (tmp_path / "a").iterdir())
+    assert files == ["blackout_col.npy", "col.npy", "pixel_index.npy"]
+    assert sum((tmp_path / "a" / f).stat().st_size for f in files) <= 64_000_000
+    for f in files:
+        assert (tmp_path / "a" / f).read_bytes() == (tmp_path / "b" / f).read_bytes()
+    idx = np.load(tmp_path / "a" / "pixel_index.npy")
+    col, bo = np.load(tmp_path / "a" / "col.npy"), np.load(tmp_path / "a" / "blackout_col.npy")
+    assert idx.dtype == np.float64 and col.dtype == np.float32 and bo.dtype == np.float32
+    P = W * H if W * H * D * 32 <= bench.DUMP_BYTES else bench.DUMP_BYTES // (32 * D)
+    assert col.shape == bo.shape == (D, P, 4) and idx.shape == (P,)
+    i = idx.astype(np.int64)
+    assert np.all(np.diff(i) > 0) and i[0] >= 0 and i[-1] < W * H
+    for f in (0, D - 1):
+        assert np.array_equal(col[f], cols[f].reshape(-1, 4).numpy()[i].astype(np.float32))
+        assert np.array_equal(bo[f], bos[f].reshape(-1, 4).numpy()[i].astype(np.float32))
+
+
+@pytest.mark.gpu
+def test_plain_run_dumps_the_last_steps_frames(tmp_path):
+    """A plain run (no --full) on the GPU: the line keeps the headline keys, carries none of the legs that
+    take runs of their own, --steps is the number of timed launches, and the dumped frames are the
+    scene's exact-math render bit for bit (every frame of a fixed-camera batch is that frame)."""
+    torch = pytest.importorskip("torch")
+    import numpy as np
+    import black_hole_ray_marching_amd as bh
+    W, H, cap = 104, 56, 64
+    rc, lines, err = _bench("--gpus", "1", "--steps", "3", "--warmup", "1", "--width", str(W), "--height", str(H),
+                            "--max-iters", str(cap), "--frames-per-launch", "2", "--dump-outputs", str(tmp_path / "o"))
+    assert rc == 0, err[-3000:]
+    assert len(lines) == 1, lines
+    d = lines[0]
+    assert d["unit"] == "Mpix/s" and d["higher_is_better"] is True and d["dtype"] == "f32" and d["value"] > 0
+    assert d["steps"] == 3 and d["kernel"]["launches"] == 3 and d["ms_per_step"] > 0
+    assert abs(d["value"] - W * H * 2 / (d["ms_per_step"] * 1e-3) / 1e6) <= 1e-3 * d["value"]
+    assert d["roofline"] is None and d["cpu_baseline"] is None and d["kernel"]["sum_steps"] is None
+    assert "single_frame" not in d and "orbit" not in d and "parity" not in d
+    scene = bh.Scene(W, H, sky=bh.synthetic_sky(4096, 2048), device=0, max_iters=cap, math=bh.BH_MATH_EXACT)
+    col = torch.empty((H, W, 4), dtype=torch.float16, device="cuda:0")
+    bo = torch.empty_like(col)
+    scene.render(col, bo, fmt=bh.BH_OUT_RGBA16F)
+    torch.cuda.synchronize()
+    scene.close()
+    got_c, got_b = np.load(tmp_path / "o" / "col.npy"), np.load(tmp_path / "o" / "blackout_col.npy")
+    assert got_c.shape == (2, W * H, 4) and got_c.dtype == np.float32
+    for f in range(2):
+        assert np.array_equal(got_c[f], col.cpu().numpy().reshape(-1, 4).astype(np.float32))
+        assert np.array_equal(got_b[f], bo.cpu().numpy().reshape(-1, 4).astype(np.float32))
+
+
+@pytest.mark.gpu
+def test_full_run_carries_the_legs_beside_the_headline():
+    """--full: the step-count launch (roofline, kernel.sum_*), the single_frame / orbit legs and the CPU leg
+    (cpu_baseline, parity against the oracle, bit-exact in exact math) follow the timed steps."""
+    pytest.importorskip("torch")
+    W, H = 104, 72  # the CPU leg warms the oracle up on rows 0..63
+    rc, lines, err = _bench("--gpus", "1", "--steps", "3", "--warmup", "1", "--width", str(W), "--height", str(H),
+                            "--max-iters", "64", "--frames-per-launch", "2", "--cpu-reps", "1", "--full")
+    assert rc == 0, err[-3000:]
+    assert len(lines) == 1, lines
+    d = lines[0]
+    assert d["steps"] == 3 and d["kernel"]["launches"] == 3 and d["ms_per_step"] > 0 and d["value"] > 0
+    assert 0 < d["kernel"]["sum_steps"] <= d["kernel"]["sum_n_rk"] <= 64 * W * H
+    assert d["roofline"]["bound"] == "valu" and 0 < d["roofline"]["frac"] < 1
+    for leg in ("single_frame", "orbit", "single_frame_orbit"):
+        assert d[leg]["ms_per_frame"] > 0
+    assert d["cpu_baseline"]["value"] > 0
+    assert d["parity"]["pixels"] == W * H and d["parity"]["bit_exact"] is True
+    assert d["parity"]["timed_format_bit_exact"] is True
+
+
 def test_clock_accumulators_to_mhz():
     """bh_set_clock_probe's per-XCD accumulators (shader ticks, 100 MHz ticks, waves) -> MHz."""
     import numpy as np

@@ -5,13 +5,13 @@ S=${1:-100}
 mkdir -p gpurun_out/sweep
 for m in exact fast; do
   for s in tile tile-static pair persistent; do
-    timeout -k 10 200 python bench.py --steps $S --warmup 5 --math $m --schedule $s --no-cpu \
+    timeout -k 10 200 python bench.py --full --steps $S --warmup 5 --math $m --schedule $s --no-cpu \
       > gpurun_out/sweep/${m}_${s}.log 2>&1 || exit 1
     tail -1 gpurun_out/sweep/${m}_${s}.log > gpurun_out/sweep/${m}_${s}.json
   done
 done
 for c in 64 1000; do
-  timeout -k 10 200 python bench.py --steps $S --warmup 5 --math exact --max-iters $c --no-cpu \
+  timeout -k 10 200 python bench.py --full --steps $S --warmup 5 --math exact --max-iters $c --no-cpu \
     > gpurun_out/sweep/exact_tile_cap$c.log 2>&1 || exit 1
   tail -1 gpurun_out/sweep/exact_tile_cap$c.log > gpurun_out/sweep/exact_tile_cap$c.json
 done
