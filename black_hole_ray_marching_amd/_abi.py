@@ -98,6 +98,11 @@ SIGNATURES = {
                             C.POINTER(bh_render_desc), C.c_void_p]),
     "bh_render_frames": (C.c_int, [C.c_void_p, C.c_uint32, C.POINTER(bh_camera_uniform), C.POINTER(bh_uniforms),
                                    C.POINTER(bh_render_desc), C.c_void_p]),
+    "bh_render_ss": (C.c_int, [C.c_void_p, C.POINTER(bh_camera_uniform), C.POINTER(bh_uniforms),
+                               C.POINTER(bh_render_desc), C.c_uint32, C.c_void_p]),
+    "bh_render_frames_ss": (C.c_int, [C.c_void_p, C.c_uint32, C.POINTER(bh_camera_uniform), C.POINTER(bh_uniforms),
+                                      C.POINTER(bh_render_desc), C.c_uint32, C.c_void_p]),
+    "bh_ss_resolve_host": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p]),
     "bh_shard_tile_count": (C.c_int64, [C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32]),
     "bh_tiles_unpack": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32,
                                   C.c_uint64, C.c_uint32, C.c_void_p]),

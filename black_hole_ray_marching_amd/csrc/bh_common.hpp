@@ -1,6 +1,7 @@
 // bh_common.hpp — host/device shared definitions for the geodesic ray-marcher (no math here).
 #pragma once
 #include <hip/hip_runtime.h>
+#include <stddef.h>
 #include <stdint.h>
 
 #include <string>
@@ -42,7 +43,12 @@ struct MarchArgs {
     float far_r2;              // r^2 beyond which a step needs no SDF argument (bh_host.cpp sdf_far_r2; +inf: off)
     // unused: the per-term radii of a root-free-step variant measured slower and removed;
     // kept so that the kernel argument layout -- and the kernels' machine code -- stay those measured
-    float reserved_[3];
+    // The supersampled render (bh_render_ss, ss = k > 1; bh_ss.hpp) uses two of those words: log2 k and the
+    // OUTPUT frame's width.  The geometry fields below then describe the virtual frame (kW x kH).  Both
+    // are 0 for every other launch, whose kernels never read them.
+    uint32_t ss_log2;
+    uint32_t ss_out_width;
+    uint32_t reserved_[1];
     // frame
     uint32_t width, height, max_iters, scene_flags;
     uint32_t format, layout;
@@ -85,6 +91,15 @@ struct MarchArgs {
 // passed by value: the kernel argument segment holds at most 4 KiB (with the persistent kernel's
 // extra pointer)
 static_assert(sizeof(MarchArgs) + 8 <= 4096, "MarchArgs must fit the kernel argument segment");
+// the layout the existing kernels were compiled against: the supersampling words took the place of three
+// unused ones and moved nothing
+static_assert(offsetof(MarchArgs, far_r2) == 72 && offsetof(MarchArgs, ss_log2) == 76 &&
+                  offsetof(MarchArgs, ss_out_width) == 80 && offsetof(MarchArgs, width) == 88,
+              "MarchArgs: the supersampling words must stay inside the former reserved_[3]");
+static_assert(offsetof(MarchArgs, order) == 144 && offsetof(MarchArgs, sky) == 200 && offsetof(MarchArgs, out_col) == 232 &&
+                  offsetof(MarchArgs, n_frames) == 272 && offsetof(MarchArgs, frames) == 304 &&
+                  sizeof(FrameArgs) == 104 && sizeof(MarchArgs) == 304 + BH_INLINE_FRAMES * sizeof(FrameArgs),
+              "MarchArgs: kernel argument layout changed");
 
 // Shard ownership: tile (tx, ty) belongs to shard (tx + 3*ty) % S (SURVEY §8e diagonal interleave).
 // Row ty's first owned column for shard k.

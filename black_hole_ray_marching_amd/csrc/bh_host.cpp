@@ -19,6 +19,7 @@
 
 #include "bh_common.hpp"
 #include "bh_srgb.hpp"
+#include "bh_ss.hpp"
 
 struct bh_ctx {
     int device = 0;
@@ -1395,10 +1396,55 @@ static bool sdf_skip_disabled() {
     return off;
 }
 
+static int render_frames_ss(bh_ctx* c, uint32_t n_frames, const bh_camera_uniform* cams, const bh_uniforms* U,
+                            const bh_render_desc* descs, uint32_t ss, void* stream);
+
 int bh_render_frames(bh_ctx* c, uint32_t n_frames, const bh_camera_uniform* cams, const bh_uniforms* U,
                      const bh_render_desc* descs, void* stream) {
+    return render_frames_ss(c, n_frames, cams, U, descs, 1u, stream);
+}
+
+int bh_render_ss(bh_ctx* c, const bh_camera_uniform* cam, const bh_uniforms* U, const bh_render_desc* d, uint32_t ss,
+                 void* stream) {
+    return bh_render_frames_ss(c, 1u, cam, U, d, ss, stream);
+}
+
+int bh_render_frames_ss(bh_ctx* c, uint32_t n_frames, const bh_camera_uniform* cams, const bh_uniforms* U,
+                        const bh_render_desc* descs, uint32_t ss, void* stream) {
+    const uint32_t lk = bh::ss::log2_k(ss);
+    if (lk > 3u) return bad_arg(__func__, __LINE__);
+    if (ss == 1u) return bh_render_frames(c, n_frames, cams, U, descs, stream);
     if (!c || !cams || !U || !descs || n_frames == 0 || n_frames > BH_MAX_FRAMES) return bad_arg(__func__, __LINE__);
     const bh_render_desc* d = &descs[0];
+    if (d->width == 0 || d->height == 0 || (uint64_t)d->width * ss > 65536u || (uint64_t)d->height * ss > 65536u)
+        return bad_arg(__func__, __LINE__);
+    // what the resolve in the wave does not cover (include/bh_render.h): checked on every frame's desc
+    for (uint32_t i = 0; i < n_frames; ++i) {
+        const bh_render_desc* e = &descs[i];
+        const char* why = e->layout != BH_LAYOUT_ROWMAJOR      ? "a row-major output (BH_LAYOUT_ROWMAJOR)"
+                          : e->shard_count != 1u               ? "the whole frame (shard_count 1)"
+                          : e->partition                       ? "no partition"
+                          : (e->schedule & 0xFFu) != BH_SCHED_TILE ? "the tile schedule (BH_SCHED_TILE)"
+                          : (e->dbg_n_rk || e->dbg_fate || e->dbg_steps) ? "no dbg_* outputs (they are per ray, not per pixel)"
+                                                               : nullptr;
+        if (why) {
+            g_last_error = std::string("bh_render_ss: a supersampled render (ss > 1) needs ") + why + ".";
+            return BH_ERR_UNSUPPORTED;
+        }
+    }
+    return render_frames_ss(c, n_frames, cams, U, descs, ss, stream);
+}
+
+// bh_render_frames, and (ss = k > 1, arguments checked by bh_render_frames_ss) its supersampled form: the
+// launch is that of the virtual frame k*width x k*height -- geometry, order state, repeat-frame key and all
+// -- with log2 k and the output width for the kernel's resolve epilogue.
+static int render_frames_ss(bh_ctx* c, uint32_t n_frames, const bh_camera_uniform* cams, const bh_uniforms* U,
+                            const bh_render_desc* descs, uint32_t ss, void* stream) {
+    if (!c || !cams || !U || !descs || n_frames == 0 || n_frames > BH_MAX_FRAMES) return bad_arg(__func__, __LINE__);
+    const bh_render_desc* const d0 = &descs[0];
+    bh_render_desc vd = *d0;  // the launch's desc: the virtual frame's at ss > 1 (per-frame outputs stay in descs[i])
+    if (ss > 1u) { vd.width *= ss; vd.height *= ss; }
+    const bh_render_desc* d = &vd;
     const bh_camera_uniform* cam = &cams[0];
     if (!d->out_col) return bad_arg(__func__, __LINE__);
     if (d->width == 0 || d->height == 0 || d->width > 65536u || d->height > 65536u) return bad_arg(__func__, __LINE__);
@@ -1409,7 +1455,7 @@ int bh_render_frames(bh_ctx* c, uint32_t n_frames, const bh_camera_uniform* cams
     if (d->shard_count == 0 || d->shard_index >= d->shard_count) return bad_arg(__func__, __LINE__);
     if (d->layout == BH_LAYOUT_ROWMAJOR && d->shard_count != 1) return bad_arg(__func__, __LINE__);
     for (uint32_t i = 0; i < n_frames; ++i) {
-        if (!descs[i].out_col || !same_launch(d, &descs[i])) return bad_arg(__func__, __LINE__);
+        if (!descs[i].out_col || !same_launch(d0, &descs[i])) return bad_arg(__func__, __LINE__);
         if (!screen_tri_default(&cams[i])) { g_last_error = "non-default screen triangle"; return BH_ERR_UNSUPPORTED; }
     }
     if ((d->layout == BH_LAYOUT_TILES_RGBM || d->layout == BH_LAYOUT_TILES_RGBM14) &&
@@ -1436,6 +1482,7 @@ int bh_render_frames(bh_ctx* c, uint32_t n_frames, const bh_camera_uniform* cams
     a.skip_sdf = (U->delta_time_mult > 0.0f && U->rs > 0.0f && U->rs <= 8.0f && !sdf_skip_disabled()) ? 1u : 0u;
     a.far_r2 = a.skip_sdf ? sdf_far_r2(U->rs, U->delta_time_mult) : INFINITY;
     a.width = d->width; a.height = d->height; a.max_iters = d->max_iters; a.scene_flags = d->scene_flags;
+    if (ss > 1u) { a.ss_log2 = bh::ss::log2_k(ss); a.ss_out_width = d0->width; }
     a.format = d->format; a.layout = d->layout;
     a.shard_index = d->shard_index; a.shard_count = d->shard_count;
     a.tiles_x = (d->width + 7u) / 8u; a.tiles_y = (d->height + 7u) / 8u;
@@ -1536,6 +1583,46 @@ int bh_render_frames(bh_ctx* c, uint32_t n_frames, const bh_camera_uniform* cams
         if (os) os->valid = false;
         return hip_fail((hipError_t)e, "march kernel launch");
     }
+    return BH_OK;
+}
+
+// The supersampled march kernel's epilogue on the host: the functions of bh_ss.hpp that each lane of a wave
+// runs (ss_resolve_store, bh_march.hpp), run here wave by wave over 64-entry arrays -- one 8x8 tile of the
+// virtual frame per wave, invalid lanes 0, every lane taking each butterfly level together.
+int bh_ss_resolve_host(const float* samples, uint32_t width, uint32_t height, uint32_t ss, float* out) {
+    const uint32_t lk = bh::ss::log2_k(ss);
+    if (!samples || !out || lk > 3u) return bad_arg(__func__, __LINE__);
+    if (width == 0 || height == 0 || (uint64_t)width * ss > 65536u || (uint64_t)height * ss > 65536u)
+        return bad_arg(__func__, __LINE__);
+    const uint32_t vw = width * ss, vh = height * ss;
+    const uint32_t tiles_x = (vw + 7u) / 8u, tiles_y = (vh + 7u) / 8u;
+    for (uint32_t ty = 0; ty < tiles_y; ++ty)
+        for (uint32_t tx = 0; tx < tiles_x; ++tx) {
+            float v[3][64], nv[64];
+            bool valid[64];
+            for (uint32_t lane = 0; lane < 64u; ++lane) {
+                const uint32_t px = tx * 8u + (lane & 7u), py = ty * 8u + (lane >> 3);
+                valid[lane] = px < vw && py < vh;
+                for (int ch = 0; ch < 3; ++ch)
+                    v[ch][lane] = valid[lane] ? samples[((size_t)py * vw + px) * 4u + (size_t)ch] : 0.0f;
+            }
+            for (int ch = 0; ch < 3; ++ch) {
+                float* cur = v[ch];
+                for (uint32_t i = 0; i < bh::ss::levels(lk); ++i) {
+                    const uint32_t mask = bh::ss::level_mask(i, lk);
+                    for (uint32_t lane = 0; lane < 64u; ++lane)
+                        nv[lane] = bh::ss::level_add(cur[lane], mask, [&](uint32_t m) { return cur[lane ^ m]; });
+                    std::memcpy(cur, nv, sizeof nv);
+                }
+            }
+            for (uint32_t lane = 0; lane < 64u; ++lane) {
+                if (!(valid[lane] && bh::ss::writer(lane, lk))) continue;
+                const uint32_t px = tx * 8u + (lane & 7u), py = ty * 8u + (lane >> 3);
+                float* o = out + (size_t)bh::ss::out_index(px, py, lk, width) * 4u;
+                for (int ch = 0; ch < 3; ++ch) o[ch] = v[ch][lane] * bh::ss::scale(lk);
+                o[3] = 1.0f;
+            }
+        }
     return BH_OK;
 }
 

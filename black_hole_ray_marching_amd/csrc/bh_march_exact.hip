@@ -19,7 +19,14 @@
 namespace {
 template <uint32_t FMT>
 int launch(const bh::MarchArgs& a, uint32_t schedule, uint32_t* counters, uint32_t grid, hipStream_t s) {
-    if (schedule == BH_SCHED_TILE) {
+    if (schedule == BH_SCHED_TILE && a.ss_log2 != 0u) {  // bh_render_ss, ss > 1: the same folds
+        if (a.scene_flags == BH_SCENE_DEFAULT)
+            bh::BH_NS::launch_tile_ss_schedule<FMT, BH_SCENE_DEFAULT>(a, s);
+        else if (a.scene_flags == 0u)
+            bh::BH_NS::launch_tile_ss_schedule<FMT, 0u>(a, s);
+        else
+            bh::BH_NS::launch_tile_ss_schedule<FMT, bh::BH_NS::SF_DYN>(a, s);
+    } else if (schedule == BH_SCHED_TILE) {
         if (a.scene_flags == BH_SCENE_DEFAULT)  // the reference's scene: flags folded at compile time
             bh::BH_NS::launch_tile_schedule<FMT, BH_SCENE_DEFAULT>(a, s);
         else if (a.scene_flags == 0u)  // no surfaces (BASELINE config 1): the sdf folds to +inf

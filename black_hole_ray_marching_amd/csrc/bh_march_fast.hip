@@ -7,7 +7,12 @@
 namespace {
 template <uint32_t FMT>
 int launch(const bh::MarchArgs& a, uint32_t schedule, uint32_t* counters, uint32_t grid, hipStream_t s) {
-    if (schedule == BH_SCHED_TILE) {
+    if (schedule == BH_SCHED_TILE && a.ss_log2 != 0u) {  // bh_render_ss, ss > 1: the same folds
+        if (a.scene_flags == BH_SCENE_DEFAULT)
+            bh::fast::launch_tile_ss_schedule<FMT, BH_SCENE_DEFAULT>(a, s);
+        else
+            bh::fast::launch_tile_ss_schedule<FMT, bh::fast::SF_DYN>(a, s);
+    } else if (schedule == BH_SCHED_TILE) {
         if (a.scene_flags == BH_SCENE_DEFAULT)  // the reference's scene: flags folded at compile time
             bh::fast::launch_tile_schedule<FMT, BH_SCENE_DEFAULT>(a, s);
         else

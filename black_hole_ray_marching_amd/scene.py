@@ -217,6 +217,26 @@ def _ptr(t) -> int | None:
     return t.data_ptr()
 
 
+def _ss_arg(ss) -> int:
+    """`ss` as the C ABI takes it (a uint32); what is no such integer is refused as the library refuses a bad ss."""
+    if isinstance(ss, bool) or not isinstance(ss, (int, np.integer)) or not 0 <= int(ss) <= 0xFFFFFFFF:
+        raise BhError(_abi.BH_ERR_INVALID_ARG, f"render: ss must be 1, 2, 4 or 8, got {ss!r}")
+    return int(ss)
+
+
+def ss_resolve_host(samples: np.ndarray, ss: int) -> np.ndarray:
+    """bh_ss_resolve_host (host only): the supersampled kernel's lane code over an fp32 RGBA virtual frame
+    (ss*H, ss*W, 4) -> its (H, W, 4) resolve."""
+    s = np.ascontiguousarray(samples, np.float32)
+    k = _ss_arg(ss)
+    if s.ndim != 3 or s.shape[2] != 4 or k == 0 or s.shape[0] % k or s.shape[1] % k:
+        raise BhError(_abi.BH_ERR_INVALID_ARG, "ss_resolve_host: samples must be (ss*H, ss*W, 4)")
+    out = np.empty((s.shape[0] // k, s.shape[1] // k, 4), np.float32)
+    check(load().bh_ss_resolve_host(s.ctypes.data, out.shape[1], out.shape[0], k, out.ctypes.data),
+          "bh_ss_resolve_host")
+    return out
+
+
 def tile_bytes(layout: int, fmt: int) -> int:
     """Bytes of one 8x8 tile of a BH_LAYOUT_TILES* layout in format `fmt` (bh_tile_bytes)."""
     n = load().bh_tile_bytes(layout, fmt)
@@ -240,8 +260,8 @@ class FrameBatch:
     """A prepared bh_render_frames call (Scene.prepare_frames): its targets stay referenced, so the
     device pointers in its descriptors stay valid while the batch lives."""
 
-    def __init__(self, scene: "Scene", descs, keep) -> None:
-        self.scene, self.descs, self._keep = scene, descs, keep
+    def __init__(self, scene: "Scene", descs, keep, ss: int = 1) -> None:
+        self.scene, self.descs, self._keep, self.ss = scene, descs, keep, ss
         self.n = len(descs)
         self._cams = (_abi.bh_camera_uniform * self.n)()
 
@@ -258,6 +278,10 @@ class FrameBatch:
             raise BhError(_abi.BH_ERR_INVALID_ARG, "render_frames: per-frame lists must have one entry per frame")
         for i, c in enumerate(cameras):
             self._cams[i] = c.c
+        if self.ss != 1:
+            check(sc.lib.bh_render_frames_ss(sc._ctx, n, self._cams, C.byref(sc.uniforms.to_c()), self.descs,
+                                             self.ss, _stream_handle(stream)), "bh_render_frames_ss")
+            return
         check(sc.lib.bh_render_frames(sc._ctx, n, self._cams, C.byref(sc.uniforms.to_c()), self.descs,
                                       _stream_handle(stream)), "bh_render_frames")
 
@@ -349,14 +373,20 @@ class Scene:
     def render(self, output, blackout_output=None, *, fmt: int = BH_OUT_RGBA32F, stream=None,
                dbg_n_rk=None, dbg_fate=None, math: int | None = None, layout: int = BH_LAYOUT_ROWMAJOR,
                shard_index: int = 0, shard_count: int = 1, width: int | None = None,
-               height: int | None = None, schedule: int = 0, dbg_steps=None, partition=None) -> None:
+               height: int | None = None, schedule: int = 0, dbg_steps=None, partition=None, ss: int = 1) -> None:
         """Scene::render (src/scene.rs:470-522): one pass writing `col` and optionally `blackout_col`.
 
         `output`/`blackout_output`: caller-owned device buffers (torch tensors or raw pointers).
         Asynchronous on `stream` (a torch.cuda.Stream, a raw hipStream_t int, or None = current).
+        `ss` = k in {1, 2, 4, 8}: k x k rays per pixel, averaged in linear fp32 before the output encode
+        (bh_render_ss; width x height stays the output size).
         """
         d = self._desc(output, blackout_output, fmt, dbg_n_rk, dbg_fate, math, layout, shard_index, shard_count,
                        width, height, schedule, dbg_steps, partition)
+        if ss != 1:
+            check(self.lib.bh_render_ss(self._ctx, C.byref(self.camera_uniform.c), C.byref(self.uniforms.to_c()),
+                                        C.byref(d), _ss_arg(ss), _stream_handle(stream)), "bh_render_ss")
+            return
         check(self.lib.bh_render(self._ctx, C.byref(self.camera_uniform.c), C.byref(self.uniforms.to_c()),
                                  C.byref(d), _stream_handle(stream)), "bh_render")
 
@@ -364,19 +394,19 @@ class Scene:
                       dbg_n_rk=None, dbg_fate=None, dbg_steps=None, math: int | None = None,
                       layout: int = BH_LAYOUT_ROWMAJOR, shard_index: int = 0, shard_count: int = 1,
                       width: int | None = None, height: int | None = None, schedule: int = 0,
-                      partition=None) -> None:
+                      partition=None, ss: int = 1) -> None:
         """Several frames in one launch (bh_render_frames, up to BH_MAX_FRAMES): frame i renders with
         cameras[i] (CameraUniform; default: this scene's camera for every frame) into outputs[i] /
-        blackout_outputs[i]; each frame's result is exactly render()'s."""
+        blackout_outputs[i]; each frame's result is exactly render()'s (`ss` as render's)."""
         self.prepare_frames(outputs, blackout_outputs, fmt=fmt, dbg_n_rk=dbg_n_rk, dbg_fate=dbg_fate,
                             dbg_steps=dbg_steps, math=math, layout=layout, shard_index=shard_index,
                             shard_count=shard_count, width=width, height=height, schedule=schedule,
-                            partition=partition).render(cameras=cameras, stream=stream)
+                            partition=partition, ss=ss).render(cameras=cameras, stream=stream)
 
     def prepare_frames(self, outputs, blackout_outputs=None, *, fmt: int = BH_OUT_RGBA32F, dbg_n_rk=None,
                        dbg_fate=None, dbg_steps=None, math: int | None = None, layout: int = BH_LAYOUT_ROWMAJOR,
                        shard_index: int = 0, shard_count: int = 1, width: int | None = None,
-                       height: int | None = None, schedule: int = 0, partition=None) -> "FrameBatch":
+                       height: int | None = None, schedule: int = 0, partition=None, ss: int = 1) -> "FrameBatch":
         """A render_frames call prepared once for targets that are rendered into again and again (an
         offline camera path, the bench): the descriptors are validated and built here, and each
         FrameBatch.render is one bh_render_frames call -- at 256x256 a launch of 32 frames takes ~0.2
@@ -392,7 +422,7 @@ class Scene:
                                                        shard_index, shard_count, width, height, schedule, steps[i],
                                                        partition)
                                             for i in range(n)])
-        return FrameBatch(self, descs, (outputs, blackout_outputs, dbg_n_rk, dbg_fate, dbg_steps, partition))
+        return FrameBatch(self, descs, (outputs, blackout_outputs, dbg_n_rk, dbg_fate, dbg_steps, partition), _ss_arg(ss))
 
     def set_clock_probe(self, acc, stride: int = 256) -> None:
         """bh_set_clock_probe: arm (acc = a zeroed device buffer of 128 u64) or disarm (acc = None) the
@@ -615,7 +645,7 @@ def tiles_unpack_rgbm_partition(packed, out_col, out_blackout, partition: "Parti
           "bh_tiles_unpack_rgbm_partition")
 
 
-__all__ = ["Camera", "Partition", "Presenter", "partition_map", "tiles_unpack_rgbm_partition", "CameraController", "CameraUniform", "Uniforms", "Scene", "synthetic_sky", "shard_tile_count", "tiles_unpack",
+__all__ = ["Camera", "ss_resolve_host", "Partition", "Presenter", "partition_map", "tiles_unpack_rgbm_partition", "CameraController", "CameraUniform", "Uniforms", "Scene", "synthetic_sky", "shard_tile_count", "tiles_unpack",
            "tiles_unpack_rgb", "tiles_unpack_rgbm", "tile_bytes", "BH_LAYOUT_TILES_RGBM", "BH_LAYOUT_TILES_RGBM14",
            "BH_UNPACK_RGBM14",
            "srgb_encode_table", "load_sky", "bloom_plan_failures", "BH_OUT_BGRA8_SRGB",

@@ -277,6 +277,40 @@ int bh_render(bh_ctx* ctx, const bh_camera_uniform* camera, const bh_uniforms* u
 int bh_render_frames(bh_ctx* ctx, uint32_t n_frames, const bh_camera_uniform* cameras, const bh_uniforms* uniforms,
                      const bh_render_desc* descs, void* hip_stream);
 
+/* Supersampled render: ss x ss rays per output pixel, ss = k in {1, 2, 4, 8}, resolved inside the march
+ * kernel (not in the reference: it shoots one ray through each pixel centre).  desc->width x desc->height is
+ * the OUTPUT size.  The samples are the pixels of the VIRTUAL frame k*width x k*height -- exactly what
+ * bh_render produces for that size with the same camera uniform, uniforms, cap, scene flags and math mode,
+ * as linear fp32 values before any output encode -- so output pixel (x, y) averages virtual pixels
+ * (kx+i, ky+j), 0 <= i, j < k: the regular k x k grid inside the pixel.
+ *   Per sample: col_s and bo_s = dot(col_s, col_s) < 1 ? 0 : col_s (the blackout test runs per sample, as
+ *     fs_main runs it per fragment; never on the average).
+ *   Resolve, per channel r, g, b, in fp32, no FMA, in this order: a pairwise tree along x (level 1 adds
+ *     neighbours i and i^1, level 2 the pair sums i and i^2, level 3 -- k = 8 -- i and i^4), the same tree
+ *     along y over the row results, then one multiply by 1 / k^2 (exact).
+ *   Alpha is 1 (255).  Encode: the output format's existing one, applied to the resolved fp32 value (bit
+ *     copy for RGBA32F, round-to-nearest-even for RGBA16F, the sRGB encode in B, G, R, A order for BGRA8).
+ *   out_blackout == NULL: that target is neither resolved nor written.
+ * ss = 1 is bh_render / bh_render_frames exactly (the call is passed on).  ss outside {1, 2, 4, 8}, or
+ * ss * width or ss * height above 65536: BH_ERR_INVALID_ARG.  With ss > 1 the tile schedule's waves resolve
+ * their own 8x8 block of samples (k divides 8: a block holds whole pixels), so BH_ERR_UNSUPPORTED, with a
+ * sentence in bh_last_error(), for: a layout other than BH_LAYOUT_ROWMAJOR, shard_count != 1, a partition,
+ * a base schedule other than BH_SCHED_TILE, any dbg_* pointer.  The BH_SCHED_FLAG_* flags are allowed.
+ * bh_render_frames_ss: up to BH_MAX_FRAMES frames in one launch, as bh_render_frames.
+ * Order state and graph contract: the launch is the virtual frame's.  Its temporal-order state and its
+ * repeated-frame key are those of geometry (k*width, k*height) on the stream -- SHARED with a plain
+ * bh_render of k*width x k*height on the same stream, which marches the same tiles and rays at the same
+ * costs.  The graph contract is unchanged: the first render of that key allocates and is refused under
+ * capture. */
+int bh_render_ss(bh_ctx* ctx, const bh_camera_uniform* camera, const bh_uniforms* uniforms,
+                 const bh_render_desc* desc, uint32_t ss, void* hip_stream);
+int bh_render_frames_ss(bh_ctx* ctx, uint32_t n_frames, const bh_camera_uniform* cameras, const bh_uniforms* uniforms,
+                        const bh_render_desc* descs, uint32_t ss, void* hip_stream);
+/* Host only (no device needed): the supersampled kernel's own lane code (csrc/bh_ss.hpp: butterfly levels,
+ * writer lanes, output index) run wave by wave over an fp32 RGBA virtual frame (ss*height rows of ss*width
+ * pixels) -> the fp32 RGBA resolve, width x height, alpha 1.  BH_ERR_INVALID_ARG as above. */
+int bh_ss_resolve_host(const float* samples_rgba, uint32_t width, uint32_t height, uint32_t ss, float* out_rgba);
+
 /* Bloom::render (src/bloom.rs:53-71): the reference's Kawase bloom + remix chain over the scene's two
  * targets, on BGRA8-sRGB images (bh_render with BH_OUT_BGRA8_SRGB): `col` (full_image_input),
  * `blackout` (blackout_input) -> `out` (the surface), all width x height (1..65536 each, as bh_render),

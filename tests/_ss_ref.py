@@ -1,0 +1,72 @@
+"""Reference of the supersampled render (bh_render_ss) for tests/test_ss_host.py and tests/test_gpu_ss.py:
+the CPU oracle's fp32 render of the VIRTUAL frame kW x kH, resolved by a numpy restatement of the normative
+tree (include/bh_render.h), then encoded as the output format stores it.  Never the GPU's own output.
+
+Every oracle frame is rendered once per process and shared (read-only arrays)."""
+import functools
+
+import numpy as np
+
+import black_hole_ray_marching_amd as bh
+import oracle
+from tests._cases import camera_uniform, uniforms
+
+CAP, FLAGS = 64, 3
+SIZES = [(13, 7), (40, 24)]   # 13x7: the virtual frame ends inside a tile on both axes at every k; 40x24: whole
+KS = [2, 4, 8]                # and partial tiles, interior groups
+
+
+@functools.lru_cache(maxsize=None)
+def sky_ss() -> np.ndarray:
+    s = bh.synthetic_sky(256, 128, seed=0x5EED_B1AC_401E)
+    s.setflags(write=False)
+    return s
+
+
+def resolve_np(a: np.ndarray, k: int) -> np.ndarray:
+    """(kH, kW, 4) fp32 samples -> (H, W, 4): per channel a pairwise tree along x (neighbours, then pair sums,
+    ...), the same tree along y over the row results, one multiply by 1/k^2; alpha 1."""
+    v = np.asarray(a, np.float32)[..., :3]
+    n = k
+    while n > 1:
+        v = v[:, 0::2] + v[:, 1::2]
+        n //= 2
+    n = k
+    while n > 1:
+        v = v[0::2] + v[1::2]
+        n //= 2
+    v = v * np.float32(1.0 / (k * k))
+    assert v.dtype == np.float32
+    return np.concatenate([v, np.ones(v.shape[:2] + (1,), np.float32)], -1)
+
+
+@functools.lru_cache(maxsize=None)
+def oracle_virtual(cam: str, W: int, H: int, k: int):
+    """The oracle's (col, blackout_col, fate) of the virtual frame kW x kH with the camera uniform of W x H."""
+    cu, U = camera_uniform(cam, W, H), uniforms()
+    col, bo, _, fate = oracle.render_rows(cu.to_bytes(), bytes(U.to_c()), sky_ss(), k * W, k * H, CAP, FLAGS)
+    for x in (col, bo, fate):
+        x.setflags(write=False)
+    return col, bo, fate
+
+
+@functools.lru_cache(maxsize=None)
+def reference(cam: str, W: int, H: int, k: int):
+    """(col, blackout_col) fp32 (H, W, 4): the normative result of ss = k.  The blackout samples are the
+    oracle's per-fragment blackout_col: the test runs per sample, not on the average."""
+    col, bo, _ = oracle_virtual(cam, W, H, k)
+    assert not np.isnan(col).any() and not np.isnan(bo).any(), "the oracle frame holds a NaN"
+    rc, rb = resolve_np(col, k), resolve_np(bo, k)
+    rc.setflags(write=False)
+    rb.setflags(write=False)
+    return rc, rb
+
+
+def expected_bytes(fmt: int, x: np.ndarray) -> np.ndarray:
+    """The bytes `fmt` stores for the fp32 RGBA image x (alpha 1)."""
+    if fmt == bh.BH_OUT_RGBA32F:
+        return np.ascontiguousarray(x).view(np.uint8)
+    if fmt == bh.BH_OUT_RGBA16F:
+        return x.astype(np.float16).view(np.uint8)  # round to nearest even
+    e = oracle.srgb_encode(x[..., :3])
+    return np.stack([e[..., 2], e[..., 1], e[..., 0], np.full(e.shape[:2], 255, np.uint8)], -1)

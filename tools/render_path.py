@@ -29,6 +29,8 @@ p.add_argument("--max-iters", type=int, default=512)
 p.add_argument("--script", default="W:0-12,ArrowLeft:6-24,P:12-18")
 p.add_argument("--out", default="gpurun_out/path")
 p.add_argument("--no-png", action="store_true")
+p.add_argument("--ss", type=int, choices=[1, 2, 4, 8], default=1,
+               help="rays per pixel side: ss x ss samples averaged in linear fp32 before the sRGB encode (bh_render_ss)")
 p.add_argument("--sky", default=None, help="image file for the sky (e.g. the reference's space_4096x2048.jpg); "
                                             "default: the synthetic sky")
 args = p.parse_args()
@@ -54,7 +56,7 @@ for f in range(args.frames):
         ctrl.process_key(k, a <= f <= b)
     cam, moved = ctrl.update_camera(cam, args.dt)
     scene.update(cam)
-    scene.render(col, bo, fmt=bh.BH_OUT_BGRA8_SRGB)
+    scene.render(col, bo, fmt=bh.BH_OUT_BGRA8_SRGB, ss=args.ss)
     scene.bloom(col, bo, surf)
     if not args.no_png:
         write_png(out_dir / f"frame_{f:04d}.png", surf.cpu().numpy())
@@ -62,5 +64,5 @@ for f in range(args.frames):
 torch.cuda.synchronize()
 dt = time.perf_counter() - t0
 (out_dir / "path.json").write_text(json.dumps(log, indent=0))
-print(json.dumps({"frames": args.frames, "width": W, "height": H, "seconds": round(dt, 3),
+print(json.dumps({"frames": args.frames, "width": W, "height": H, "ss": args.ss, "seconds": round(dt, 3),
                   "frames_per_s_incl_png": round(args.frames / dt, 2), "out": str(out_dir)}))
