@@ -10,7 +10,7 @@ from ._abi import (BH_BLOOM_AUTO, BH_BLOOM_LITERAL, BH_FATE_BLACKOUT, BH_FATE_CA
                    BYTES_PER_PIXEL,
                    BhError, load)
 from .scene import (MAX_ITERATIONS, Camera, CameraController, CameraUniform, FrameBatch, Partition, Presenter, Scene, Uniforms, bloom_check, bloom_plan_failures, clock_mhz, load_sky,
-                    partition_map, shard_tile_count, srgb_encode_table, ss_resolve_host, tiles_unpack_rgbm_partition,
+                    partition_map, refine_cover_host, refine_mask_host, shard_tile_count, srgb_encode_table, ss_resolve_host, tiles_unpack_rgbm_partition,
                     synthetic_sky, tile_bytes, tiles_unpack, tiles_unpack_rgb, tiles_unpack_rgbm)
 
 __version__ = "0.4.0"

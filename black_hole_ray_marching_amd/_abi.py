@@ -71,6 +71,11 @@ class bh_render_desc(C.Structure):
                 ("dbg_steps", C.c_void_p), ("partition", C.c_void_p)]
 
 
+class bh_adaptive_desc(C.Structure):
+    _fields_ = [("ss", C.c_uint32), ("threshold", C.c_float), ("tile_mask", C.c_void_p),
+                ("refined_tiles", C.c_void_p)]
+
+
 class bh_presenter_desc(C.Structure):
     _fields_ = [(n, C.c_uint32) for n in ("width", "height", "max_iters", "scene_flags", "math", "levels", "batch",
                                           "bloom_cus", "depth", "march_streams")]
@@ -103,6 +108,13 @@ SIGNATURES = {
     "bh_render_frames_ss": (C.c_int, [C.c_void_p, C.c_uint32, C.POINTER(bh_camera_uniform), C.POINTER(bh_uniforms),
                                       C.POINTER(bh_render_desc), C.c_uint32, C.c_void_p]),
     "bh_ss_resolve_host": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p]),
+    "bh_render_adaptive": (C.c_int, [C.c_void_p, C.POINTER(bh_camera_uniform), C.POINTER(bh_uniforms),
+                                     C.POINTER(bh_render_desc), C.POINTER(bh_adaptive_desc), C.c_void_p]),
+    "bh_render_frames_adaptive": (C.c_int, [C.c_void_p, C.c_uint32, C.POINTER(bh_camera_uniform), C.POINTER(bh_uniforms),
+                                            C.POINTER(bh_render_desc), C.POINTER(bh_adaptive_desc), C.c_void_p]),
+    "bh_refine_mask_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_float,
+                                      C.c_void_p]),
+    "bh_refine_cover_host": (C.c_int, [C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]),
     "bh_shard_tile_count": (C.c_int64, [C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32]),
     "bh_tiles_unpack": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32,
                                   C.c_uint64, C.c_uint32, C.c_void_p]),

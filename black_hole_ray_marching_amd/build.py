@@ -46,6 +46,9 @@ TU_FLAGS = {
     # the fast (tolerance) kernels: no machine scheduling either (0.468 -> 0.440 ms headline, A/B r01)
     "bh_march_fast.hip": ["-ffp-contract=fast", "-fno-hip-fp32-correctly-rounded-divide-sqrt",
                           "-mllvm", "-enable-misched=0", "-mllvm", "-enable-post-misched=0"],
+    # the scheduled build of the adaptive render's work-list march alone, without machine LICM (see the file)
+    "bh_march_refine_lat.hip": ["-ffp-contract=off", "-fhip-fp32-correctly-rounded-divide-sqrt", "-fno-slp-vectorize",
+                                "-mllvm", "-disable-machine-licm"],
     "bh_tiles.hip": [],
     # post-RA scheduling off: fused bloom chain 0.556 -> 0.548 ms (A/B r01; pre-RA off too: 0.561)
     # no SLP vectorisation: packed-FP32 forms of the filter's adjacent channel ops cost more than the
@@ -79,7 +82,7 @@ def build_product(force: bool = False) -> Path:
     for src, flags in TU_FLAGS.items():
         s = CSRC / src
         o = OBJ / (s.stem + ".o")
-        deps = [s, *headers, Path(__file__)] + ([CSRC / "bh_march_exact.hip"] if src == "bh_march_exact_lat.hip" else [])
+        deps = [s, *headers, Path(__file__)] + ([CSRC / "bh_march_exact.hip"] if src in ("bh_march_exact_lat.hip", "bh_march_refine_lat.hip") else [])
         if force or _stale(o, deps):
             jobs.append([HIPCC, *COMMON, *flags, "-c", str(s), "-o", str(o)])
         objs.append(o)

@@ -101,6 +101,29 @@ static_assert(offsetof(MarchArgs, order) == 144 && offsetof(MarchArgs, sky) == 2
                   sizeof(FrameArgs) == 104 && sizeof(MarchArgs) == 304 + BH_INLINE_FRAMES * sizeof(FrameArgs),
               "MarchArgs: kernel argument layout changed");
 
+// The adaptive render's device-side work (bh_render_adaptive; bh_refine.hpp), a second kernel argument of
+// the two kernels that use it -- MarchArgs stays as the existing kernels were compiled against.  The detect
+// kernel (bh_tiles.hip) fills mask, list and counts from the plain frame in the frames' targets; the
+// work-list march (bh_march.hpp, march_refine_kernel) consumes the list.
+struct RefineArgs {
+    uint32_t* list;      // `capacity` entries of refine::ENTRY_WORDS words: frame, output tile
+    uint32_t* ctr;       // [0] entries appended at the front, [1] at the back; from word REFINE_HEAD0 on the
+                         // work-list march's head words, REFINE_HEAD_STRIDE apart (REFINE_CTR_WORDS words).  The two
+                         // entry counts are zeroed on the stream before the detect, the heads by the detect kernel
+    const uint8_t* tile_cost;  // optional: pass 1's cost of each output tile (frame 0's), the list's order
+    uint8_t* mask;       // n_frames * tiles_x * tiles_y bytes, frame-major: 1 = refined
+    uint32_t* refined;   // optional (the caller's): n_frames counts, zeroed on the stream before the detect
+    uint32_t width, height;     // the OUTPUT frame (MarchArgs' geometry is the virtual frame's)
+    uint32_t tiles_x, tiles_y;  // its 8x8 tile grid
+    uint32_t n_frames;
+    uint32_t capacity;   // entries the list holds: n_frames * tiles_x * tiles_y at least
+    uint32_t n_heads;    // 1..REFINE_HEADS head words in use (bh_march.hpp, march_refine_kernel)
+    float thr;           // refine::threshold(format, T)
+};
+
+constexpr uint32_t REFINE_HEADS = 8, REFINE_HEAD_STRIDE = 32, REFINE_HEAD0 = 32;  // 128-byte lines
+constexpr uint32_t REFINE_CTR_WORDS = REFINE_HEAD0 + REFINE_HEADS * REFINE_HEAD_STRIDE;
+
 // Shard ownership: tile (tx, ty) belongs to shard (tx + 3*ty) % S (SURVEY §8e diagonal interleave).
 // Row ty's first owned column for shard k.
 __host__ __device__ inline uint32_t shard_row_start(uint32_t ty, uint32_t k, uint32_t S) {
@@ -237,6 +260,16 @@ extern "C" __attribute__((visibility("hidden"))) int bh_launch_march_exact_lat(c
 extern "C" __attribute__((visibility("hidden"))) int bh_launch_march_fast(const bh::MarchArgs& a, uint32_t schedule,
                                                                         uint32_t* counters, uint32_t grid,
                                                                         hipStream_t s);
+// the adaptive render's work-list march (a.ss_log2 in 1..3, `waves` pulling waves) and its detect kernel
+extern "C" __attribute__((visibility("hidden"))) int bh_launch_refine_exact(const bh::MarchArgs& a, const bh::RefineArgs& r,
+                                                                          uint32_t waves, hipStream_t s);
+extern "C" __attribute__((visibility("hidden"))) int bh_launch_refine_exact_lat(const bh::MarchArgs& a,
+                                                                              const bh::RefineArgs& r, uint32_t waves,
+                                                                              hipStream_t s);
+extern "C" __attribute__((visibility("hidden"))) int bh_launch_refine_fast(const bh::MarchArgs& a, const bh::RefineArgs& r,
+                                                                         uint32_t waves, hipStream_t s);
+extern "C" __attribute__((visibility("hidden"))) int bh_launch_refine_detect(const bh::MarchArgs& a, const bh::RefineArgs& r,
+                                                                           hipStream_t s);
 extern "C" __attribute__((visibility("hidden"))) int bh_march_blocks_per_cu_exact(void);
 extern "C" __attribute__((visibility("hidden"))) int bh_march_blocks_per_cu_fast(void);
 extern "C" __attribute__((visibility("hidden"))) int bh_launch_build_order(const uint8_t* cost, uint32_t n_tiles,

@@ -19,6 +19,7 @@
 
 #include "bh_common.hpp"
 #include "bh_srgb.hpp"
+#include "bh_refine.hpp"
 #include "bh_ss.hpp"
 
 struct bh_ctx {
@@ -53,6 +54,17 @@ struct bh_ctx {
         uint8_t* tile_cost = nullptr;
         uint32_t* order = nullptr;
         uint32_t* counters = nullptr;        // ORDER_WORDS words (bh_common.hpp)
+        // the adaptive render's scratch for this geometry and stream (bh_render_adaptive; allocated by its
+        // first call of the key, or of more frames than before): the work list, its two counters and the
+        // mask of calls that pass no tile_mask, for refine_frames frames.  Same life as the buffers above.
+        uint32_t* refine_list = nullptr;
+        uint32_t* refine_ctr = nullptr;
+        uint8_t* refine_mask = nullptr;
+        uint32_t refine_frames = 0;
+        void free_buffers() {
+            (void)hipFree(tile_cost); (void)hipFree(order); (void)hipFree(counters);
+            (void)hipFree(refine_list); (void)hipFree(refine_ctr); (void)hipFree(refine_mask);
+        }
     };
     std::vector<OrderState> orders;
     uint64_t order_clock = 0;
@@ -600,11 +612,7 @@ int bh_destroy(bh_ctx* c) {
     if (c->enc_b) (void)hipFree(c->enc_b);
     if (c->enc_e) (void)hipFree(c->enc_e);
     if (c->counters) (void)hipFree(c->counters);
-    for (auto& o : c->orders) {
-        if (o.tile_cost) (void)hipFree(o.tile_cost);
-        if (o.order) (void)hipFree(o.order);
-        if (o.counters) (void)hipFree(o.counters);
-    }
+    for (auto& o : c->orders) o.free_buffers();
     for (auto& b : c->blooms) free_bloom_scratch(b);
     for (auto& t : c->frame_tables) free_frame_table(t);
     delete c;
@@ -1308,7 +1316,7 @@ static int order_state(bh_ctx* c, const bh_render_desc* d, uint64_t nt, hipStrea
             if (!c->orders[i].captured && (v == c->orders.size() || c->orders[i].last_use < c->orders[v].last_use)) v = i;
         if (v < c->orders.size()) {
             auto& o = c->orders[v];
-            (void)hipFree(o.tile_cost); (void)hipFree(o.order); (void)hipFree(o.counters);
+            o.free_buffers();
             c->orders.erase(c->orders.begin() + (long)v);
         }
     }
@@ -1397,7 +1405,8 @@ static bool sdf_skip_disabled() {
 }
 
 static int render_frames_ss(bh_ctx* c, uint32_t n_frames, const bh_camera_uniform* cams, const bh_uniforms* U,
-                            const bh_render_desc* descs, uint32_t ss, void* stream);
+                            const bh_render_desc* descs, uint32_t ss, void* stream,
+                            const bh::RefineArgs* refine = nullptr);
 
 int bh_render_frames(bh_ctx* c, uint32_t n_frames, const bh_camera_uniform* cams, const bh_uniforms* U,
                      const bh_render_desc* descs, void* stream) {
@@ -1409,6 +1418,22 @@ int bh_render_ss(bh_ctx* c, const bh_camera_uniform* cam, const bh_uniforms* U, 
     return bh_render_frames_ss(c, 1u, cam, U, d, ss, stream);
 }
 
+// What the resolve in the wave does not cover (include/bh_render.h), checked on every frame's desc: what the
+// launch needs instead, or null.
+static const char* ss_needs(const bh_render_desc* descs, uint32_t n_frames) {
+    for (uint32_t i = 0; i < n_frames; ++i) {
+        const bh_render_desc* e = &descs[i];
+        const char* why = e->layout != BH_LAYOUT_ROWMAJOR      ? "a row-major output (BH_LAYOUT_ROWMAJOR)"
+                          : e->shard_count != 1u               ? "the whole frame (shard_count 1)"
+                          : e->partition                       ? "no partition"
+                          : (e->schedule & 0xFFu) != BH_SCHED_TILE ? "the tile schedule (BH_SCHED_TILE)"
+                          : (e->dbg_n_rk || e->dbg_fate || e->dbg_steps) ? "no dbg_* outputs (they are per ray, not per pixel)"
+                                                               : nullptr;
+        if (why) return why;
+    }
+    return nullptr;
+}
+
 int bh_render_frames_ss(bh_ctx* c, uint32_t n_frames, const bh_camera_uniform* cams, const bh_uniforms* U,
                         const bh_render_desc* descs, uint32_t ss, void* stream) {
     const uint32_t lk = bh::ss::log2_k(ss);
@@ -1418,19 +1443,9 @@ int bh_render_frames_ss(bh_ctx* c, uint32_t n_frames, const bh_camera_uniform* c
     const bh_render_desc* d = &descs[0];
     if (d->width == 0 || d->height == 0 || (uint64_t)d->width * ss > 65536u || (uint64_t)d->height * ss > 65536u)
         return bad_arg(__func__, __LINE__);
-    // what the resolve in the wave does not cover (include/bh_render.h): checked on every frame's desc
-    for (uint32_t i = 0; i < n_frames; ++i) {
-        const bh_render_desc* e = &descs[i];
-        const char* why = e->layout != BH_LAYOUT_ROWMAJOR      ? "a row-major output (BH_LAYOUT_ROWMAJOR)"
-                          : e->shard_count != 1u               ? "the whole frame (shard_count 1)"
-                          : e->partition                       ? "no partition"
-                          : (e->schedule & 0xFFu) != BH_SCHED_TILE ? "the tile schedule (BH_SCHED_TILE)"
-                          : (e->dbg_n_rk || e->dbg_fate || e->dbg_steps) ? "no dbg_* outputs (they are per ray, not per pixel)"
-                                                               : nullptr;
-        if (why) {
-            g_last_error = std::string("bh_render_ss: a supersampled render (ss > 1) needs ") + why + ".";
-            return BH_ERR_UNSUPPORTED;
-        }
+    if (const char* why = ss_needs(descs, n_frames)) {
+        g_last_error = std::string("bh_render_ss: a supersampled render (ss > 1) needs ") + why + ".";
+        return BH_ERR_UNSUPPORTED;
     }
     return render_frames_ss(c, n_frames, cams, U, descs, ss, stream);
 }
@@ -1438,8 +1453,10 @@ int bh_render_frames_ss(bh_ctx* c, uint32_t n_frames, const bh_camera_uniform* c
 // bh_render_frames, and (ss = k > 1, arguments checked by bh_render_frames_ss) its supersampled form: the
 // launch is that of the virtual frame k*width x k*height -- geometry, order state, repeat-frame key and all
 // -- with log2 k and the output width for the kernel's resolve epilogue.
+// `refine` (ss > 1, bh_render_frames_adaptive): the same launch arguments, but no order state and, in place
+// of the march over every tile, the detect kernel and the march over the work list it leaves.
 static int render_frames_ss(bh_ctx* c, uint32_t n_frames, const bh_camera_uniform* cams, const bh_uniforms* U,
-                            const bh_render_desc* descs, uint32_t ss, void* stream) {
+                            const bh_render_desc* descs, uint32_t ss, void* stream, const bh::RefineArgs* refine) {
     if (!c || !cams || !U || !descs || n_frames == 0 || n_frames > BH_MAX_FRAMES) return bad_arg(__func__, __LINE__);
     const bh_render_desc* const d0 = &descs[0];
     bh_render_desc vd = *d0;  // the launch's desc: the virtual frame's at ss > 1 (per-frame outputs stay in descs[i])
@@ -1537,6 +1554,29 @@ static int render_frames_ss(bh_ctx* c, uint32_t n_frames, const bh_camera_unifor
         const int st = stage_frame_table(c, s, table.data(), n_frames, &a.frame_table);
         if (st != BH_OK) return st;
     }
+    if (refine) {
+        // the work-list march pulls with one wave per SIMD slot (WG_WAVES = 1: 32 workgroups fill a CU), never
+        // more waves than there could be items; a wave that finds no work left ends at once
+        const uint64_t items = ((uint64_t)refine->tiles_x * refine->tiles_y * n_frames) << (2u * a.ss_log2);
+        const uint32_t waves = (uint32_t)std::min<uint64_t>(items, 32ull * (c->cus ? c->cus : 256u));
+        hipError_t he = hipMemsetAsync(refine->ctr, 0, 2 * sizeof(uint32_t), s);  // the entry counts (the heads: detect)
+        if (he == hipSuccess && refine->refined) he = hipMemsetAsync(refine->refined, 0, n_frames * sizeof(uint32_t), s);
+        if (he != hipSuccess) return hip_fail(he, "work list reset");
+        int e = bh_launch_refine_detect(a, *refine, s);
+        if (e != 0) return hip_fail((hipError_t)e, "detect kernel launch");
+        // The refined tiles are the frame's long chains (disc edge, photon ring), a fraction of the virtual frame's
+        // tiles: the list's march is latency-bound where bh_render_ss of the same k is throughput-bound, so it
+        // runs the scheduled build unless BH_SCHED_FLAG_ISSUE_ORDER asks for the other (measured: DESIGN.md §7f).
+        // BH_REFINE_VARIANT_RULE (A/B): bh_render_ss's choice for the whole virtual frame instead.
+        static const bool by_rule = std::getenv("BH_REFINE_VARIANT_RULE") != nullptr;
+        const bool issue = by_rule ? march_variant_issue_order(d, a.n_tiles, a.n_frames, c->cus)
+                                   : (d->schedule & BH_SCHED_FLAG_ISSUE_ORDER) != 0u;
+        e = d->math != BH_MATH_EXACT ? bh_launch_refine_fast(a, *refine, waves, s)
+            : issue                  ? bh_launch_refine_exact(a, *refine, waves, s)
+                                     : bh_launch_refine_exact_lat(a, *refine, waves, s);
+        if (e != 0) return hip_fail((hipError_t)e, "work-list march launch");
+        return BH_OK;
+    }
     bh_ctx::OrderState* os = nullptr;
     if (sched == BH_SCHED_TILE && !(d->schedule & BH_SCHED_FLAG_STATIC_ORDER)) {
         // temporal order of this (geometry, shard, stream): allocated at its first render only
@@ -1623,6 +1663,173 @@ int bh_ss_resolve_host(const float* samples, uint32_t width, uint32_t height, ui
                 o[3] = 1.0f;
             }
         }
+    return BH_OK;
+}
+
+// ---- adaptive supersampling (include/bh_render.h; the rule and the work list: bh_refine.hpp) ------------
+static_assert(bh::refine::FMT_RGBA32F == BH_OUT_RGBA32F && bh::refine::FMT_RGBA16F == BH_OUT_RGBA16F &&
+                  bh::refine::FMT_BGRA8 == BH_OUT_BGRA8_SRGB, "bh_refine.hpp's formats are the ABI's");
+
+// The state of (geometry, whole frame, stream) if it exists (order_state's key, nothing created).
+static bh_ctx::OrderState* find_order_state(bh_ctx* c, const bh_render_desc* d, uint64_t nt, hipStream_t s) {
+    for (auto& o : c->orders)
+        if (o.width == d->width && o.height == d->height && o.shard_index == d->shard_index &&
+            o.shard_count == d->shard_count && o.partition == 0u && o.n_tiles == nt && o.stream == (void*)s)
+            return &o;
+    return nullptr;
+}
+
+int bh_render_adaptive(bh_ctx* c, const bh_camera_uniform* cam, const bh_uniforms* U, const bh_render_desc* d,
+                       const bh_adaptive_desc* ad, void* stream) {
+    return bh_render_frames_adaptive(c, 1u, cam, U, d, ad, stream);
+}
+
+int bh_render_frames_adaptive(bh_ctx* c, uint32_t n_frames, const bh_camera_uniform* cams, const bh_uniforms* U,
+                              const bh_render_desc* descs, const bh_adaptive_desc* ad, void* stream) {
+    static const char* const fn = "bh_render_adaptive";
+    if (!c || !cams || !U || !descs || !ad || n_frames == 0 || n_frames > BH_MAX_FRAMES) return bad_arg(fn, __LINE__);
+    const uint32_t ss = ad->ss, lk = bh::ss::log2_k(ss);
+    if (lk < 1u || lk > 3u) return bad_arg(fn, __LINE__);
+    if (!(ad->threshold >= 0.0f) || std::isinf(ad->threshold)) return bad_arg(fn, __LINE__);  // NaN fails the >=
+    const bh_render_desc* d = &descs[0];
+    if (d->width == 0 || d->height == 0 || (uint64_t)d->width * ss > 65536u || (uint64_t)d->height * ss > 65536u)
+        return bad_arg(fn, __LINE__);
+    if (const char* why = ss_needs(descs, n_frames)) {
+        g_last_error = std::string(fn) + ": an adaptive render needs " + why + ".";
+        return BH_ERR_UNSUPPORTED;
+    }
+    const uint32_t tiles_x = bh::refine::tiles_of(d->width), tiles_y = bh::refine::tiles_of(d->height);
+    const uint64_t nt = (uint64_t)tiles_x * tiles_y;
+    // the work items of a fully refined call, and the virtual frame's slots as bh_render_ss counts them
+    if (((nt * n_frames) << (2u * lk)) > 0xFFFF0000ull ||
+        (uint64_t)bh::refine::tiles_of(d->width * ss) * bh::refine::tiles_of(d->height * ss) * n_frames > 0xFFFFFFF0ull)
+        return bad_arg(fn, __LINE__);
+    hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+    bool capturing;
+    {
+        DeviceScope dev(c->device);
+        if (dev.err != hipSuccess) return hip_fail(dev.err, "hipSetDevice");
+        capturing = stream_capturing(s);
+    }
+    if (capturing) {
+        // nothing may be allocated: refused before pass 1 is queued, so the targets stay as they are
+        bh_ctx::OrderState* os = find_order_state(c, d, nt, s);
+        if (!os || os->refine_frames < n_frames) {
+            g_last_error = std::string(fn) + ": the first adaptive render of a (geometry, stream), or of more frames "
+                           "than before, allocates; render it once before capturing it into a graph";
+            return BH_ERR_UNSUPPORTED;
+        }
+    }
+    // pass 1: the plain frame, exactly bh_render_frames (every remaining argument check is its own)
+    int st = bh_render_frames(c, n_frames, cams, U, descs, stream);
+    if (st != BH_OK) return st;
+    DeviceScope dev(c->device);
+    if (dev.err != hipSuccess) return hip_fail(dev.err, "hipSetDevice");
+    bh_ctx::OrderState* os = nullptr;
+    if (capturing) {
+        os = find_order_state(c, d, nt, s);  // pass 1 creates no state under capture: still there
+        if (!os) return bad_arg(fn, __LINE__);
+        os->captured = true;
+        os->last_use = ++c->order_clock;
+    } else {
+        st = order_state(c, d, nt, s, false, &os);  // pass 1's own, or (BH_SCHED_FLAG_STATIC_ORDER) a new one
+        if (st != BH_OK) return st;
+        if (os->refine_frames < n_frames && os->captured) {
+            g_last_error = std::string(fn) + ": a captured graph holds this (geometry, stream)'s work list, which is "
+                           "too small for this many frames (bh_graph_release once the graph is destroyed)";
+            return BH_ERR_UNSUPPORTED;
+        }
+        if (os->refine_frames < n_frames) {
+            uint32_t* list = nullptr;
+            uint32_t* ctr = nullptr;
+            uint8_t* mask = nullptr;
+            const size_t entries = (size_t)nt * n_frames;
+            hipError_t he;
+            if ((he = hipMalloc(&list, entries * bh::refine::ENTRY_WORDS * sizeof(uint32_t))) != hipSuccess ||
+                (he = hipMalloc(&ctr, bh::REFINE_CTR_WORDS * sizeof(uint32_t))) != hipSuccess || (he = hipMalloc(&mask, entries)) != hipSuccess) {
+                (void)hipFree(list); (void)hipFree(ctr);
+                return he == hipErrorOutOfMemory ? BH_ERR_OUT_OF_MEMORY : hip_fail(he, "hipMalloc(work list)");
+            }
+            // hipFree waits for the device: no earlier call's kernels still use the smaller buffers
+            (void)hipFree(os->refine_list); (void)hipFree(os->refine_ctr); (void)hipFree(os->refine_mask);
+            os->refine_list = list; os->refine_ctr = ctr; os->refine_mask = mask;
+            os->refine_frames = n_frames;
+        }
+    }
+    bh::RefineArgs R;
+    std::memset(&R, 0, sizeof R);
+    R.list = os->refine_list; R.ctr = os->refine_ctr;
+    R.mask = ad->tile_mask ? ad->tile_mask : os->refine_mask;
+    R.refined = ad->refined_tiles;
+    // pass 1 left frame 0's tile costs in the state (or, for a repeated frame, found them there): the list's order
+    static const bool unordered = std::getenv("BH_REFINE_UNORDERED") != nullptr;  // A/B switch (diagnostics)
+    R.tile_cost = (os->valid && !(d->schedule & BH_SCHED_FLAG_STATIC_ORDER) && !unordered) ? os->tile_cost : nullptr;
+    R.width = d->width; R.height = d->height; R.tiles_x = tiles_x; R.tiles_y = tiles_y;
+    R.n_frames = n_frames;
+    R.capacity = (uint32_t)std::min<uint64_t>(nt * os->refine_frames, 0xFFFFFFFFull);
+    static const bool one_head = std::getenv("BH_REFINE_ONE_HEAD") != nullptr;  // A/B switch (diagnostics)
+    R.n_heads = one_head ? 1u : bh::REFINE_HEADS;
+    R.thr = bh::refine::threshold(d->format, ad->threshold);
+    return render_frames_ss(c, n_frames, cams, U, descs, ss, stream, &R);
+}
+
+// The detect kernel's decision on the host: bh_refine.hpp's lane function, tile by tile and lane by lane.
+int bh_refine_mask_host(const void* col, const void* blackout, uint32_t width, uint32_t height, uint32_t format,
+                        float threshold, uint8_t* tile_mask) {
+    if (!col || !tile_mask || width == 0 || height == 0 || width > 32768u || height > 32768u) return bad_arg(__func__, __LINE__);
+    if (format > BH_OUT_BGRA8_SRGB || !(threshold >= 0.0f) || std::isinf(threshold)) return bad_arg(__func__, __LINE__);
+    const uint32_t tiles_x = bh::refine::tiles_of(width), tiles_y = bh::refine::tiles_of(height);
+    const float thr = bh::refine::threshold(format, threshold);
+    for (uint32_t ty = 0; ty < tiles_y; ++ty)
+        for (uint32_t tx = 0; tx < tiles_x; ++tx) {
+            bool any = false;  // the wave's ballot
+            for (uint32_t lane = 0; lane < 64u; ++lane)
+                any |= bh::refine::lane_edge(format, col, blackout, width, height, tx, ty, lane, thr);
+            tile_mask[(size_t)ty * tiles_x + tx] = any ? 1u : 0u;
+        }
+    return BH_OK;
+}
+
+// The work-list march's stores on the host: the list a detect pass would leave for this mask (both ends used),
+// every work item mapped by bh_refine.hpp's item functions, every lane of its wave through bh_ss.hpp's writer
+// and output index.  An index outside the frame is counted nowhere and fails the call.
+int bh_refine_cover_host(uint32_t width, uint32_t height, uint32_t ss, const uint8_t* tile_mask, uint8_t* pixel_writes) {
+    const uint32_t lk = bh::ss::log2_k(ss);
+    if (!tile_mask || !pixel_writes || lk < 1u || lk > 3u) return bad_arg(__func__, __LINE__);
+    if (width == 0 || height == 0 || (uint64_t)width * ss > 65536u || (uint64_t)height * ss > 65536u)
+        return bad_arg(__func__, __LINE__);
+    const uint32_t tiles_x = bh::refine::tiles_of(width), tiles_y = bh::refine::tiles_of(height);
+    const uint32_t vw = width * ss, vh = height * ss;
+    const uint32_t vtiles_x = bh::refine::tiles_of(vw), vtiles_y = bh::refine::tiles_of(vh);
+    const size_t n_px = (size_t)width * height;
+    std::memset(pixel_writes, 0, n_px);
+    // filled from both ends as the detect kernel fills it (every third refined tile to the front)
+    const uint32_t capacity = tiles_x * tiles_y;
+    std::vector<uint32_t> list(capacity, 0xFFFFFFFFu);
+    uint32_t n_front = 0, n_back = 0;
+    for (uint32_t t = 0, n = 0; t < capacity; ++t)
+        if (tile_mask[t]) list[n++ % 3u == 0u ? n_front++ : capacity - 1u - n_back++] = t;
+    if (((uint64_t)(n_front + n_back) << (2u * lk)) > 0xFFFF0000ull) return bad_arg(__func__, __LINE__);
+    const uint32_t total = (n_front + n_back) << (2u * lk);
+    bool outside = false;
+    for (uint32_t item = 0; item < total; ++item) {
+        uint32_t vtx, vty;
+        const uint32_t slot = bh::refine::entry_slot(bh::refine::item_entry(item, lk), n_front, capacity);
+        if (!bh::refine::item_tile(list[slot], bh::refine::item_sub(item, lk), lk, tiles_x,
+                                   tiles_y, vtiles_x, vtiles_y, &vtx, &vty))
+            continue;
+        for (uint32_t lane = 0; lane < 64u; ++lane) {
+            const uint32_t px = bh::refine::lane_x(vtx, lane), py = bh::refine::lane_y(vty, lane);
+            if (!(px < vw && py < vh && bh::ss::writer(lane, lk))) continue;
+            const size_t idx = bh::ss::out_index(px, py, lk, width);
+            if (idx >= n_px) { outside = true; continue; }
+            if (pixel_writes[idx] != 255u) ++pixel_writes[idx];
+        }
+    }
+    if (outside) {
+        g_last_error = "bh_refine_cover_host: a store index outside the frame";
+        return BH_ERR_INTERNAL;
+    }
     return BH_OK;
 }
 

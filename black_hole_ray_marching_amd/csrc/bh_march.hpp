@@ -18,6 +18,7 @@
 #include "bh_common.hpp"
 #include "bh_crmath.hpp"
 #include "bh_srgb.hpp"
+#include "bh_refine.hpp"
 #include "bh_ss.hpp"
 
 #ifndef BH_FAST
@@ -1566,13 +1567,18 @@ __device__ __forceinline__ void ss_resolve_store(const MarchArgs& a, const float
     }
 }
 
-// One dispatch slot, marched by one wave.  SS: the supersampled form (march_tile_ss_kernel).
-template <uint32_t FMT, uint32_t SF, bool SS = false>
+// One dispatch slot, marched by one wave.  SS: the supersampled form (march_tile_ss_kernel).  ITEM (with SS):
+// a work item of the adaptive render (march_refine_kernel) -- `slot` is the frame and (item_tx, item_ty) the
+// tile of the virtual frame, both given by the caller's work list: no dispatch order, no cost feedback.
+template <uint32_t FMT, uint32_t SF, bool SS = false, bool ITEM = false>
 __device__ __forceinline__ void march_slot(const MarchArgs& A, uint32_t slot, const float* lut,
-                                           uint32_t lane) {
+                                           uint32_t lane, uint32_t item_tx = 0u, uint32_t item_ty = 0u) {
+    static_assert(SS || !ITEM, "work items are supersampled tiles");
     const uint32_t nf = A.n_frames;
     uint32_t fi = 0, j = slot;
-    if (nf > 1u) {
+    if constexpr (ITEM) {
+        fi = slot;
+    } else if (nf > 1u) {
         j = slot / nf;
         fi = slot - j * nf;
     }
@@ -1581,16 +1587,21 @@ __device__ __forceinline__ void march_slot(const MarchArgs& A, uint32_t slot, co
     // BH_INLINE_FRAMES frames read them from the device table (wave-uniform index: one load per wave)
     if (A.frame_table) select_camera(a, A.frame_table[fi]);
     else select_camera(a, A.frames[fi]);
-    if (fi != 0u) a.tile_cost = nullptr;
-    const uint32_t t = a.order ? a.order[j] : centre_out(j, a.n_tiles, a.order_block, a.order_centre);
+    if (ITEM || fi != 0u) a.tile_cost = nullptr;
+    uint32_t t = 0u, tx, ty;
+    if constexpr (ITEM) {
+        tx = item_tx;
+        ty = item_ty;
+    } else {
+    t = a.order ? a.order[j] : centre_out(j, a.n_tiles, a.order_block, a.order_centre);
     if (t >= a.n_tiles) return;  // defensive: a corrupt order must not address outside the shard
-    uint32_t tx, ty;
     if (a.tile_list) {  // weighted partition (bh_partition): the shard's tile list
         const uint32_t v = a.tile_list[t];
         tx = v & 0xFFFFu;
         ty = v >> 16;
     } else {
         shard_tile_coords(t, a.tiles_x, a.shard_index, a.shard_count, &tx, &ty);
+    }
     }
     const uint32_t px = tx * 8u + (lane & 7u), py = ty * 8u + (lane >> 3);
     const bool valid = px < a.width && py < a.height;
@@ -1714,6 +1725,59 @@ __global__ void __launch_bounds__(64 * WG_WAVES) march_tile_ss_kernel(MarchArgs 
     if (probe) c0 = clock_start();
     march_slot<FMT, SF, true>(A, slot, lut, threadIdx.x & 63u);
     if (probe) clock_end(A.clk, c0);
+}
+
+// The adaptive render's second pass (bh_render_adaptive; bh_refine.hpp): the supersampled march over a work
+// list that the detect kernel (bh_tiles.hip) left on the device.  The host never learns the list's length, so
+// the grid is a bounded number of waves (RefineArgs::capacity bounds the list, the launcher the grid) and each
+// wave pulls work items until they pass entries * k^2: lane 0's vector atomic on a head word, broadcast.  One
+// head word serves about 88 pulls per microsecond however many waves pull (MI355X), less than these waves ask
+// for, so the items are dealt to R.n_heads heads (item i to head i % n_heads, its pulls in order, each head on
+// a 128-byte line of its own): a wave starts on head blockIdx % n_heads -- workgroups go to the XCDs round
+// robin -- and moves to the next head when one is exhausted, after a plain look at it.  An
+// item marches one tile of the virtual frame with march_slot's supersampled code -- ray, march, samples,
+// resolve and stores are march_tile_ss_kernel's, so a refined pixel holds bh_render_ss's bytes -- and reads or
+// writes no order state (A.order, A.tile_cost and A.order_tot are null).  An entry or a virtual tile out of
+// range touches no memory.
+template <uint32_t FMT, uint32_t SF>
+__global__ void __launch_bounds__(64 * WG_WAVES) march_refine_kernel(MarchArgs A, RefineArgs R) {
+    __shared__ float lut[lds_tables<FMT>()];
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t lk = A.ss_log2;
+    const uint32_t n_front = __builtin_amdgcn_readfirstlane(
+        min(__hip_atomic_load(R.ctr, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT), R.capacity));
+    const uint32_t n_back = __builtin_amdgcn_readfirstlane(
+        min(__hip_atomic_load(R.ctr + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT), R.capacity - n_front));
+    const uint32_t total = (n_front + n_back) << (2u * lk);  // <= 0xFFFF0000 (bh_host.cpp)
+    if (total == 0u) return;  // nothing refined (the same for every wave of the launch): no table, no pull
+    load_tables<FMT, 64u * WG_WAVES>(A, lut);
+    __syncthreads();
+    const uint32_t nh = R.n_heads ? R.n_heads : 1u;
+    uint32_t q = (blockIdx.x * WG_WAVES + (threadIdx.x >> 6)) % nh, tried = 0u;
+    while (tried < nh) {  // wave-uniform throughout
+        uint32_t* head = R.ctr + REFINE_HEAD0 + REFINE_HEAD_STRIDE * q;
+        // pull n of head q is item n * nh + q; a head seen exhausted is not pulled from again
+        uint32_t n = 0xFFFFFFFFu;
+        if (tried == 0u || (uint64_t)__builtin_amdgcn_readfirstlane(__hip_atomic_load(head, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) * nh + q < total) {
+            if (lane == 0u) n = __hip_atomic_fetch_add(head, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            n = __builtin_amdgcn_readfirstlane(n);
+        }
+        const uint64_t item64 = (uint64_t)n * nh + q;
+        if (item64 >= total) {
+            q = q + 1u == nh ? 0u : q + 1u;
+            ++tried;
+            continue;
+        }
+        const uint32_t item = (uint32_t)item64;
+        const uint32_t* e = R.list + (size_t)refine::ENTRY_WORDS * refine::entry_slot(refine::item_entry(item, lk), n_front, R.capacity);
+        const uint32_t fi = __builtin_amdgcn_readfirstlane(e[0]), tile = __builtin_amdgcn_readfirstlane(e[1]);
+        uint32_t vtx, vty;
+        if (fi >= A.n_frames ||
+            !refine::item_tile(tile, refine::item_sub(item, lk), lk, R.tiles_x, R.tiles_y, A.tiles_x, A.tiles_y, &vtx, &vty))
+            continue;
+        march_slot<FMT, SF, true, true>(A, fi, lut, lane, vtx, vty);
+        __builtin_amdgcn_s_setprio(0);  // a tail wave raised it (march_ray); the next item starts as any wave does
+    }
 }
 
 // ---- schedule BH_SCHED_PERSISTENT: persistent waves with per-lane refill (A/B option) ------------
@@ -1909,6 +1973,12 @@ inline void launch_tile_ss_schedule(const MarchArgs& a, hipStream_t s) {
     const uint32_t waves = a.n_tiles * a.n_frames;
     const uint32_t blocks = (waves + (WG_WAVES - 1u)) / WG_WAVES;
     hipLaunchKernelGGL((march_tile_ss_kernel<FMT, SF>), dim3(blocks), dim3(64u * WG_WAVES), 0, s, a);
+}
+// ... and the adaptive render's work-list march: `waves` resident waves that pull (march_refine_kernel)
+template <uint32_t FMT, uint32_t SF>
+inline void launch_refine_schedule(const MarchArgs& a, const RefineArgs& r, uint32_t waves, hipStream_t s) {
+    const uint32_t blocks = (waves + (WG_WAVES - 1u)) / WG_WAVES;
+    hipLaunchKernelGGL((march_refine_kernel<FMT, SF>), dim3(blocks), dim3(64u * WG_WAVES), 0, s, a, r);
 }
 
 }  // namespace BH_NS

@@ -7,15 +7,18 @@
 //   bh_march_exact_lat.hip  namespace exact_lat  LLVM's machine schedulers: interleaved chains, the
 //                                                shorter latency per step of a lone tail wave.
 // bh_render picks one per frame (bh_host.cpp, march_variant).
+// A third build holds the adaptive render's work-list march alone (bh_march_refine_lat.hip).
 #define BH_FAST 0
 #ifndef BH_NS
 #define BH_NS exact
 #define BH_EXACT_LAUNCH bh_launch_march_exact
 #define BH_EXACT_BLOCKS bh_march_blocks_per_cu_exact
+#define BH_EXACT_REFINE bh_launch_refine_exact
 #define BH_EXACT_AUX 1
 #endif
 #include "bh_march.hpp"
 
+#ifndef BH_REFINE_ONLY
 namespace {
 template <uint32_t FMT>
 int launch(const bh::MarchArgs& a, uint32_t schedule, uint32_t* counters, uint32_t grid, hipStream_t s) {
@@ -55,12 +58,43 @@ extern "C" __attribute__((visibility("hidden"))) int BH_EXACT_LAUNCH(const bh::M
     }
 }
 
+#endif  // BH_REFINE_ONLY
+
+#ifdef BH_EXACT_REFINE
+// The adaptive render's work-list march (bh_render_adaptive): the supersampled kernels' folds.
+namespace {
+template <uint32_t FMT>
+int launch_refine(const bh::MarchArgs& a, const bh::RefineArgs& r, uint32_t waves, hipStream_t s) {
+    if (a.scene_flags == BH_SCENE_DEFAULT)
+        bh::BH_NS::launch_refine_schedule<FMT, BH_SCENE_DEFAULT>(a, r, waves, s);
+    else if (a.scene_flags == 0u)
+        bh::BH_NS::launch_refine_schedule<FMT, 0u>(a, r, waves, s);
+    else
+        bh::BH_NS::launch_refine_schedule<FMT, bh::BH_NS::SF_DYN>(a, r, waves, s);
+    return (int)hipGetLastError();
+}
+}  // namespace
+
+extern "C" __attribute__((visibility("hidden"))) int BH_EXACT_REFINE(const bh::MarchArgs& a, const bh::RefineArgs& r,
+                                                                     uint32_t waves, hipStream_t s) {
+    switch (a.format) {
+        case BH_OUT_RGBA32F: return launch_refine<BH_OUT_RGBA32F>(a, r, waves, s);
+        case BH_OUT_RGBA16F: return launch_refine<BH_OUT_RGBA16F>(a, r, waves, s);
+        default: return launch_refine<BH_OUT_BGRA8_SRGB>(a, r, waves, s);
+    }
+}
+
+#endif  // BH_EXACT_REFINE
+
+#ifndef BH_REFINE_ONLY
 // Resident 256-thread blocks per CU of the persistent kernel (sizes its grid: every block resident).
 extern "C" __attribute__((visibility("hidden"))) int BH_EXACT_BLOCKS(void) {
     int n = 0;
     if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, bh::BH_NS::march_persistent_kernel<BH_OUT_BGRA8_SRGB>, 256, 0) != hipSuccess) return 1;
     return n > 0 ? n : 1;
 }
+
+#endif  // BH_REFINE_ONLY
 
 #if defined(BH_DIAG_SLOW) && defined(BH_EXACT_AUX)
 // diagnostics build only: read and reset the fallback counters

@@ -39,6 +39,27 @@ extern "C" __attribute__((visibility("hidden"))) int bh_launch_march_fast(const 
     }
 }
 
+// The adaptive render's work-list march (bh_render_adaptive): the supersampled kernels' folds.
+namespace {
+template <uint32_t FMT>
+int launch_refine(const bh::MarchArgs& a, const bh::RefineArgs& r, uint32_t waves, hipStream_t s) {
+    if (a.scene_flags == BH_SCENE_DEFAULT)
+        bh::fast::launch_refine_schedule<FMT, BH_SCENE_DEFAULT>(a, r, waves, s);
+    else
+        bh::fast::launch_refine_schedule<FMT, bh::fast::SF_DYN>(a, r, waves, s);
+    return (int)hipGetLastError();
+}
+}  // namespace
+
+extern "C" __attribute__((visibility("hidden"))) int bh_launch_refine_fast(const bh::MarchArgs& a, const bh::RefineArgs& r,
+                                                                         uint32_t waves, hipStream_t s) {
+    switch (a.format) {
+        case BH_OUT_RGBA32F: return launch_refine<BH_OUT_RGBA32F>(a, r, waves, s);
+        case BH_OUT_RGBA16F: return launch_refine<BH_OUT_RGBA16F>(a, r, waves, s);
+        default: return launch_refine<BH_OUT_BGRA8_SRGB>(a, r, waves, s);
+    }
+}
+
 // Resident 256-thread blocks per CU of the persistent kernel (sizes its grid: every block resident).
 extern "C" __attribute__((visibility("hidden"))) int bh_march_blocks_per_cu_fast(void) {
     int n = 0;

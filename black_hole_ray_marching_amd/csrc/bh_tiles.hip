@@ -2,6 +2,7 @@
 // RCCL gather), and the temporal dispatch order of the tile schedule.  The unpack is
 // pure byte movement (HBM-bound): whole packed tiles in, full frame-row segments out.
 #include "bh_common.hpp"
+#include "bh_refine.hpp"
 
 namespace bh {
 
@@ -200,7 +201,60 @@ __global__ void __launch_bounds__(ORDER_THREADS) order_scatter_kernel(const uint
     }
 }
 
+// ---- adaptive render: the detect pass (bh_render_adaptive; the rule lives in bh_refine.hpp) ------------
+// One wave64 per 8x8 output tile and frame, lane = pixel: each lane reads its texel and its 4-neighbours
+// inside the frame (the tile plus a one-pixel halo, from the plain frame the march just stored: L2 hits)
+// in both targets and decides; the wave ballots, and lane 0 writes its tile's mask byte and, for a refined
+// tile, appends (frame, tile) to the work list with one atomic on an entry counter.  A wave writes for its
+// own tile only.  The list's order follows the atomics and varies from run to run; mask, counts and the
+// set of entries do not.
+constexpr uint32_t DETECT_WAVES = 4;
+template <uint32_t FMT>
+__global__ void __launch_bounds__(64 * DETECT_WAVES) refine_detect_kernel(MarchArgs A, RefineArgs R) {
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t w = __builtin_amdgcn_readfirstlane(blockIdx.x * DETECT_WAVES + (threadIdx.x >> 6));
+    const uint32_t nt = R.tiles_x * R.tiles_y;
+    if (w >= nt * R.n_frames) return;  // wave-uniform
+    // the work-list march's head words start at 0: written here, a kernel ahead of their first reader
+    if (w == 0u && lane < REFINE_HEADS) R.ctr[REFINE_HEAD0 + REFINE_HEAD_STRIDE * lane] = 0u;
+    const uint32_t f = w / nt, tile = w - f * nt;
+    const uint32_t ty = tile / R.tiles_x, tx = tile - ty * R.tiles_x;
+    const void* col;
+    const void* bo;
+    if (A.frame_table) { col = A.frame_table[f].out_col; bo = A.frame_table[f].out_blackout; }
+    else { col = A.frames[f].out_col; bo = A.frames[f].out_blackout; }
+    const bool e = refine::lane_edge(FMT, col, bo, R.width, R.height, tx, ty, lane, R.thr);
+    const bool any = __builtin_amdgcn_ballot_w64(e) != 0ull;
+    if (lane == 0u) {
+        R.mask[w] = any ? 1u : 0u;
+        if (any) {
+            // long marches to the front of the list, the others to its back (bh_refine.hpp, entry_slot)
+            const bool first = R.tile_cost && R.tile_cost[tile] >= refine::COST_FIRST;
+            const uint32_t pos = __hip_atomic_fetch_add(R.ctr + (first ? 0 : 1), 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            if (pos < R.capacity) {  // always: at most one entry per wave
+                const size_t slot = first ? pos : R.capacity - 1u - pos;
+                R.list[refine::ENTRY_WORDS * slot] = f;
+                R.list[refine::ENTRY_WORDS * slot + 1u] = tile;
+            }
+            if (R.refined) __hip_atomic_fetch_add(R.refined + f, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        }
+    }
+}
+
 }  // namespace bh
+
+extern "C" __attribute__((visibility("hidden"))) int bh_launch_refine_detect(const bh::MarchArgs& a, const bh::RefineArgs& r,
+                                                                           hipStream_t s) {
+    const uint64_t waves = (uint64_t)r.tiles_x * r.tiles_y * r.n_frames;
+    if (waves == 0 || waves > 0xFFFF0000ull) return (int)hipErrorInvalidValue;
+    const dim3 grid((uint32_t)((waves + bh::DETECT_WAVES - 1u) / bh::DETECT_WAVES)), block(64u * bh::DETECT_WAVES);
+    switch (a.format) {
+        case BH_OUT_RGBA32F: hipLaunchKernelGGL(bh::refine_detect_kernel<BH_OUT_RGBA32F>, grid, block, 0, s, a, r); break;
+        case BH_OUT_RGBA16F: hipLaunchKernelGGL(bh::refine_detect_kernel<BH_OUT_RGBA16F>, grid, block, 0, s, a, r); break;
+        default: hipLaunchKernelGGL(bh::refine_detect_kernel<BH_OUT_BGRA8_SRGB>, grid, block, 0, s, a, r); break;
+    }
+    return (int)hipGetLastError();
+}
 
 extern "C" __attribute__((visibility("hidden"))) int bh_launch_build_order(const uint8_t* cost, uint32_t n,
                                                                          uint32_t L, uint32_t c,

@@ -237,6 +237,48 @@ def ss_resolve_host(samples: np.ndarray, ss: int) -> np.ndarray:
     return out
 
 
+def _adaptive_desc(ss, adaptive, tile_mask, refined_tiles, n_frames: int, width: int, height: int):
+    """The bh_adaptive_desc of a render call (adaptive = T, not None); the optional device buffers are size-checked."""
+    try:
+        t = float(adaptive)
+    except (TypeError, ValueError):
+        raise BhError(_abi.BH_ERR_INVALID_ARG, f"render: adaptive must be a threshold (a float), got {adaptive!r}")
+    a = _abi.bh_adaptive_desc()
+    a.ss, a.threshold = _ss_arg(ss), t
+    _check_size(tile_mask, n_frames * ((width + 7) // 8) * ((height + 7) // 8), "tile_mask")
+    _check_size(refined_tiles, 4 * n_frames, "refined_tiles")
+    a.tile_mask, a.refined_tiles = _ptr(tile_mask), _ptr(refined_tiles)
+    return a
+
+
+def refine_mask_host(col: np.ndarray, blackout: np.ndarray | None, fmt: int, threshold: float) -> np.ndarray:
+    """bh_refine_mask_host (host only): the adaptive render's detect rule over one frame's stored target(s),
+    (H, W, 4) arrays of float32 / float16 / uint8 for RGBA32F / RGBA16F / BGRA8 -> the (tiles_y, tiles_x) mask."""
+    dt = {BH_OUT_RGBA32F: np.float32, _abi.BH_OUT_RGBA16F: np.float16, _abi.BH_OUT_BGRA8_SRGB: np.uint8}.get(fmt)
+    if dt is None:
+        raise BhError(_abi.BH_ERR_INVALID_ARG, f"refine_mask_host: unknown format {fmt!r}")
+    c = np.ascontiguousarray(col, dt)
+    b = None if blackout is None else np.ascontiguousarray(blackout, dt)
+    if c.ndim != 3 or c.shape[2] != 4 or (b is not None and b.shape != c.shape):
+        raise BhError(_abi.BH_ERR_INVALID_ARG, "refine_mask_host: targets must be (H, W, 4) and of one shape")
+    h, w = c.shape[:2]
+    mask = np.empty(((h + 7) // 8, (w + 7) // 8), np.uint8)
+    check(load().bh_refine_mask_host(c.ctypes.data, None if b is None else b.ctypes.data, w, h, fmt, float(threshold),
+                                     mask.ctypes.data), "bh_refine_mask_host")
+    return mask
+
+
+def refine_cover_host(width: int, height: int, ss: int, tile_mask: np.ndarray) -> np.ndarray:
+    """bh_refine_cover_host (host only): the number of stores each output pixel receives from the adaptive
+    render's second pass over `tile_mask` ((tiles_y, tiles_x) uint8) -> (height, width) uint8."""
+    m = np.ascontiguousarray(tile_mask, np.uint8)
+    if m.shape != ((height + 7) // 8, (width + 7) // 8):
+        raise BhError(_abi.BH_ERR_INVALID_ARG, "refine_cover_host: tile_mask must be (ceil(H / 8), ceil(W / 8))")
+    out = np.empty((height, width), np.uint8)
+    check(load().bh_refine_cover_host(width, height, _ss_arg(ss), m.ctypes.data, out.ctypes.data), "bh_refine_cover_host")
+    return out
+
+
 def tile_bytes(layout: int, fmt: int) -> int:
     """Bytes of one 8x8 tile of a BH_LAYOUT_TILES* layout in format `fmt` (bh_tile_bytes)."""
     n = load().bh_tile_bytes(layout, fmt)
@@ -260,8 +302,9 @@ class FrameBatch:
     """A prepared bh_render_frames call (Scene.prepare_frames): its targets stay referenced, so the
     device pointers in its descriptors stay valid while the batch lives."""
 
-    def __init__(self, scene: "Scene", descs, keep, ss: int = 1) -> None:
+    def __init__(self, scene: "Scene", descs, keep, ss: int = 1, adaptive=None) -> None:
         self.scene, self.descs, self._keep, self.ss = scene, descs, keep, ss
+        self.adaptive = adaptive  # a bh_adaptive_desc (bh_render_frames_adaptive), or None
         self.n = len(descs)
         self._cams = (_abi.bh_camera_uniform * self.n)()
 
@@ -278,6 +321,11 @@ class FrameBatch:
             raise BhError(_abi.BH_ERR_INVALID_ARG, "render_frames: per-frame lists must have one entry per frame")
         for i, c in enumerate(cameras):
             self._cams[i] = c.c
+        if self.adaptive is not None:
+            check(sc.lib.bh_render_frames_adaptive(sc._ctx, n, self._cams, C.byref(sc.uniforms.to_c()), self.descs,
+                                                   C.byref(self.adaptive), _stream_handle(stream)),
+                  "bh_render_frames_adaptive")
+            return
         if self.ss != 1:
             check(sc.lib.bh_render_frames_ss(sc._ctx, n, self._cams, C.byref(sc.uniforms.to_c()), self.descs,
                                              self.ss, _stream_handle(stream)), "bh_render_frames_ss")
@@ -373,16 +421,27 @@ class Scene:
     def render(self, output, blackout_output=None, *, fmt: int = BH_OUT_RGBA32F, stream=None,
                dbg_n_rk=None, dbg_fate=None, math: int | None = None, layout: int = BH_LAYOUT_ROWMAJOR,
                shard_index: int = 0, shard_count: int = 1, width: int | None = None,
-               height: int | None = None, schedule: int = 0, dbg_steps=None, partition=None, ss: int = 1) -> None:
+               height: int | None = None, schedule: int = 0, dbg_steps=None, partition=None, ss: int = 1,
+               adaptive: float | None = None, tile_mask=None, refined_tiles=None) -> None:
         """Scene::render (src/scene.rs:470-522): one pass writing `col` and optionally `blackout_col`.
 
         `output`/`blackout_output`: caller-owned device buffers (torch tensors or raw pointers).
         Asynchronous on `stream` (a torch.cuda.Stream, a raw hipStream_t int, or None = current).
         `ss` = k in {1, 2, 4, 8}: k x k rays per pixel, averaged in linear fp32 before the output encode
         (bh_render_ss; width x height stays the output size).
+        `adaptive` = T (with ss = k > 1): the plain frame, then only the 8x8 tiles that show an edge above T
+        are marched again with k x k rays and overwritten (bh_render_adaptive); `tile_mask` (uint8 device
+        buffer, one byte per tile) and `refined_tiles` (one uint32) optionally receive which and how many.
         """
         d = self._desc(output, blackout_output, fmt, dbg_n_rk, dbg_fate, math, layout, shard_index, shard_count,
                        width, height, schedule, dbg_steps, partition)
+        if adaptive is not None:
+            a = _adaptive_desc(ss, adaptive, tile_mask, refined_tiles, 1, d.width, d.height)
+            check(self.lib.bh_render_adaptive(self._ctx, C.byref(self.camera_uniform.c), C.byref(self.uniforms.to_c()),
+                                              C.byref(d), C.byref(a), _stream_handle(stream)), "bh_render_adaptive")
+            return
+        if tile_mask is not None or refined_tiles is not None:
+            raise BhError(_abi.BH_ERR_INVALID_ARG, "render: tile_mask and refined_tiles belong to an adaptive render")
         if ss != 1:
             check(self.lib.bh_render_ss(self._ctx, C.byref(self.camera_uniform.c), C.byref(self.uniforms.to_c()),
                                         C.byref(d), _ss_arg(ss), _stream_handle(stream)), "bh_render_ss")
@@ -394,19 +453,23 @@ class Scene:
                       dbg_n_rk=None, dbg_fate=None, dbg_steps=None, math: int | None = None,
                       layout: int = BH_LAYOUT_ROWMAJOR, shard_index: int = 0, shard_count: int = 1,
                       width: int | None = None, height: int | None = None, schedule: int = 0,
-                      partition=None, ss: int = 1) -> None:
+                      partition=None, ss: int = 1, adaptive: float | None = None, tile_mask=None,
+                      refined_tiles=None) -> None:
         """Several frames in one launch (bh_render_frames, up to BH_MAX_FRAMES): frame i renders with
         cameras[i] (CameraUniform; default: this scene's camera for every frame) into outputs[i] /
-        blackout_outputs[i]; each frame's result is exactly render()'s (`ss` as render's)."""
+        blackout_outputs[i]; each frame's result is exactly render()'s (`ss`, `adaptive` as render's;
+        `tile_mask` holds n masks frame after frame, `refined_tiles` n counts)."""
         self.prepare_frames(outputs, blackout_outputs, fmt=fmt, dbg_n_rk=dbg_n_rk, dbg_fate=dbg_fate,
                             dbg_steps=dbg_steps, math=math, layout=layout, shard_index=shard_index,
                             shard_count=shard_count, width=width, height=height, schedule=schedule,
-                            partition=partition, ss=ss).render(cameras=cameras, stream=stream)
+                            partition=partition, ss=ss, adaptive=adaptive, tile_mask=tile_mask,
+                            refined_tiles=refined_tiles).render(cameras=cameras, stream=stream)
 
     def prepare_frames(self, outputs, blackout_outputs=None, *, fmt: int = BH_OUT_RGBA32F, dbg_n_rk=None,
                        dbg_fate=None, dbg_steps=None, math: int | None = None, layout: int = BH_LAYOUT_ROWMAJOR,
                        shard_index: int = 0, shard_count: int = 1, width: int | None = None,
-                       height: int | None = None, schedule: int = 0, partition=None, ss: int = 1) -> "FrameBatch":
+                       height: int | None = None, schedule: int = 0, partition=None, ss: int = 1,
+                       adaptive: float | None = None, tile_mask=None, refined_tiles=None) -> "FrameBatch":
         """A render_frames call prepared once for targets that are rendered into again and again (an
         offline camera path, the bench): the descriptors are validated and built here, and each
         FrameBatch.render is one bh_render_frames call -- at 256x256 a launch of 32 frames takes ~0.2
@@ -422,7 +485,13 @@ class Scene:
                                                        shard_index, shard_count, width, height, schedule, steps[i],
                                                        partition)
                                             for i in range(n)])
-        return FrameBatch(self, descs, (outputs, blackout_outputs, dbg_n_rk, dbg_fate, dbg_steps, partition), _ss_arg(ss))
+        keep = (outputs, blackout_outputs, dbg_n_rk, dbg_fate, dbg_steps, partition, tile_mask, refined_tiles)
+        if adaptive is None:
+            if tile_mask is not None or refined_tiles is not None:
+                raise BhError(_abi.BH_ERR_INVALID_ARG, "render_frames: tile_mask and refined_tiles belong to an adaptive render")
+            return FrameBatch(self, descs, keep, _ss_arg(ss))
+        a = _adaptive_desc(ss, adaptive, tile_mask, refined_tiles, n, descs[0].width, descs[0].height)
+        return FrameBatch(self, descs, keep, _ss_arg(ss), a)
 
     def set_clock_probe(self, acc, stride: int = 256) -> None:
         """bh_set_clock_probe: arm (acc = a zeroed device buffer of 128 u64) or disarm (acc = None) the
@@ -645,7 +714,7 @@ def tiles_unpack_rgbm_partition(packed, out_col, out_blackout, partition: "Parti
           "bh_tiles_unpack_rgbm_partition")
 
 
-__all__ = ["Camera", "ss_resolve_host", "Partition", "Presenter", "partition_map", "tiles_unpack_rgbm_partition", "CameraController", "CameraUniform", "Uniforms", "Scene", "synthetic_sky", "shard_tile_count", "tiles_unpack",
+__all__ = ["Camera", "ss_resolve_host", "refine_mask_host", "refine_cover_host", "Partition", "Presenter", "partition_map", "tiles_unpack_rgbm_partition", "CameraController", "CameraUniform", "Uniforms", "Scene", "synthetic_sky", "shard_tile_count", "tiles_unpack",
            "tiles_unpack_rgb", "tiles_unpack_rgbm", "tile_bytes", "BH_LAYOUT_TILES_RGBM", "BH_LAYOUT_TILES_RGBM14",
            "BH_UNPACK_RGBM14",
            "srgb_encode_table", "load_sky", "bloom_plan_failures", "BH_OUT_BGRA8_SRGB",

@@ -311,6 +311,60 @@ int bh_render_frames_ss(bh_ctx* ctx, uint32_t n_frames, const bh_camera_uniform*
  * pixels) -> the fp32 RGBA resolve, width x height, alpha 1.  BH_ERR_INVALID_ARG as above. */
 int bh_ss_resolve_host(const float* samples_rgba, uint32_t width, uint32_t height, uint32_t ss, float* out_rgba);
 
+/* Adaptive supersampling: every pixel gets the plain one-ray value, and every 8x8 output tile that shows an
+ * edge is marched again with ss x ss rays per pixel and overwritten with the supersampled value.
+ * Normative definition.  For one frame of size W x H, format F, ss = k in {2, 4, 8} and threshold T, let
+ *   P = the bytes bh_render writes for that frame (both targets),
+ *   S = the bytes bh_render_ss with ss = k writes.
+ * Texel values: the stored colour channels of P, without alpha -- RGBA32F: the fp32 values as stored;
+ *   RGBA16F: each channel converted to fp32 (exact); BGRA8: the three colour bytes as integers.
+ * Neighbour distance of two 4-neighbours a and b (x +- 1 or y +- 1, both inside the frame, no wrap across
+ *   row ends): float formats, d = max over the 3 channels of |a_c - b_c|, one fp32 subtract each, then abs;
+ *   BGRA8, d = (float) max |a_c - b_c| over the integer bytes.  They DIFFER when d > T in the float formats,
+ *   when d > T * 255.0f (one fp32 multiply) in BGRA8; the comparison is strict.
+ * Edge pixels: a pixel that differs from any 4-neighbour in `col`; when out_blackout is non-NULL, also one
+ *   that differs from any 4-neighbour in `blackout_col`.  With out_blackout == NULL only `col` counts.
+ * Refined tiles: an 8x8 output tile (tx, ty) that holds at least one edge pixel (a differing pair that
+ *   straddles a tile boundary refines both tiles).
+ * Output: pixels of refined tiles hold S's bytes, all other pixels P's; both targets, alpha unchanged.
+ * Arguments: T must be finite and >= 0 and ss one of 2, 4, 8, else BH_ERR_INVALID_ARG; the size limits are
+ * bh_render_ss's; everything bh_render_ss refuses with BH_ERR_UNSUPPORTED is refused here the same way
+ * (layout, shards, partition, base schedule, dbg_* pointers), the sentence in bh_last_error() starting
+ * "bh_render_adaptive".
+ * tile_mask (optional, device): n_frames * tiles_x * tiles_y bytes, frame-major, row-major tiles of
+ * ceil(W / 8) x ceil(H / 8), 1 = refined.  refined_tiles (optional, device): n_frames counts.  Both are
+ * written on the stream; every byte of outputs, mask and counts is the same from run to run.
+ * How it runs: bh_render_frames on the stream (pass 1, with the W x H geometry's order state as ever), a
+ * detect kernel over the plain frame that leaves a work list on the device, and the supersampled march
+ * over that list (pass 2), which reads and writes no order state -- the virtual geometry's state, which
+ * bh_render_ss uses, is not touched.  The host never reads the list's length.
+ * Graph contract: the list and its counters belong to the (W x H geometry, stream) state of bh_render.  The
+ * first adaptive call of that key -- or the first of more frames than any before it -- allocates and is
+ * refused on a capturing stream with BH_ERR_UNSUPPORTED before anything is queued; later calls allocate
+ * nothing, never block the host and enqueue only capturable work (two memsets, the detect kernel, the
+ * march).  An error after pass 1 was queued leaves the stream ordered. */
+typedef struct {
+    uint32_t ss;             /* 2, 4 or 8 */
+    float threshold;         /* T above */
+    uint8_t* tile_mask;      /* optional, device */
+    uint32_t* refined_tiles; /* optional, device */
+} bh_adaptive_desc;
+int bh_render_adaptive(bh_ctx* ctx, const bh_camera_uniform* camera, const bh_uniforms* uniforms,
+                       const bh_render_desc* desc, const bh_adaptive_desc* adaptive, void* hip_stream);
+int bh_render_frames_adaptive(bh_ctx* ctx, uint32_t n_frames, const bh_camera_uniform* cameras,
+                              const bh_uniforms* uniforms, const bh_render_desc* descs,
+                              const bh_adaptive_desc* adaptive, void* hip_stream);
+/* Host only (no device needed): the detect kernel's own lane code (csrc/bh_refine.hpp) over one frame's
+ * row-major target(s) in `format` -> tile_mask, ceil(width / 8) * ceil(height / 8) bytes.  width and height
+ * up to 32768; BH_ERR_INVALID_ARG as above. */
+int bh_refine_mask_host(const void* col, const void* blackout_or_NULL, uint32_t width, uint32_t height,
+                        uint32_t format, float threshold, uint8_t* tile_mask);
+/* Host only: the stores of pass 2 for a mask -- the work items of its refined tiles mapped to tiles of the
+ * virtual frame (csrc/bh_refine.hpp), their lanes to output pixels (csrc/bh_ss.hpp) -> pixel_writes,
+ * width * height bytes: the number of stores each output pixel receives (1 inside refined tiles, else 0).
+ * BH_ERR_INTERNAL if a store index falls outside the frame. */
+int bh_refine_cover_host(uint32_t width, uint32_t height, uint32_t ss, const uint8_t* tile_mask, uint8_t* pixel_writes);
+
 /* Bloom::render (src/bloom.rs:53-71): the reference's Kawase bloom + remix chain over the scene's two
  * targets, on BGRA8-sRGB images (bh_render with BH_OUT_BGRA8_SRGB): `col` (full_image_input),
  * `blackout` (blackout_input) -> `out` (the surface), all width x height (1..65536 each, as bh_render),

@@ -1,0 +1,94 @@
+"""Reference of the adaptive supersampled render (bh_render_adaptive) for tests/test_refine_host.py and
+tests/test_gpu_adaptive.py: a numpy restatement of the normative rule (include/bh_render.h) over the stored
+bytes of a plain frame, and the composition where(mask, S_ref, P_ref) of the CPU oracle's plain frame with
+tests/_ss_ref.py's supersampled reference.  Never the GPU's own output.
+
+Every reference is built once per process and shared (read-only arrays)."""
+import functools
+
+import numpy as np
+
+import black_hole_ray_marching_amd as bh
+from tests._ss_ref import expected_bytes, oracle_virtual, reference
+
+T = 0.1
+CAMS = ["D", "E", "H"]
+SIZES = [(13, 7), (40, 24), (44, 27)]  # 13x7: two partial tiles; 40x24: whole tiles; 44x27: a partial last column and row
+KS = [2, 4, 8]
+DT = {bh.BH_OUT_RGBA32F: np.float32, bh.BH_OUT_RGBA16F: np.float16, bh.BH_OUT_BGRA8_SRGB: np.uint8}
+
+
+def texels(fmt: int, stored: np.ndarray) -> np.ndarray:
+    """(H, W, 4) stored texels (float32 / float16 / uint8 BGRA) -> the (H, W, 3) texel values the rule compares:
+    fp32 for the float formats (the fp16 -> fp32 conversion is exact), int32 bytes for BGRA8."""
+    a = np.asarray(stored)
+    assert a.dtype == DT[fmt] and a.ndim == 3 and a.shape[2] == 4
+    return a[..., :3].astype(np.int32) if fmt == bh.BH_OUT_BGRA8_SRGB else a[..., :3].astype(np.float32)
+
+
+def edge_pixels(fmt: int, stored: np.ndarray, t: float) -> np.ndarray:
+    """(H, W) bool: the pixel differs from a 4-neighbour inside the frame."""
+    v = texels(fmt, stored)
+    h, w = v.shape[:2]
+    if fmt == bh.BH_OUT_BGRA8_SRGB:
+        thr = np.float32(t) * np.float32(255.0)
+        dist = lambda p, q: np.abs(p - q).max(-1).astype(np.float32) > thr  # noqa: E731
+    else:
+        thr = np.float32(t)
+        dist = lambda p, q: np.fmax.reduce(np.abs(p - q), axis=-1) > thr  # noqa: E731  (fp32 subtract, abs, max)
+    e = np.zeros((h, w), bool)
+    dx = dist(v[:, 1:], v[:, :-1])  # (x, x-1) pairs of one row: no wrap
+    e[:, 1:] |= dx
+    e[:, :-1] |= dx
+    dy = dist(v[1:], v[:-1])
+    e[1:] |= dy
+    e[:-1] |= dy
+    return e
+
+
+def tile_mask(fmt: int, col: np.ndarray, blackout, t: float) -> np.ndarray:
+    """(tiles_y, tiles_x) uint8: the 8x8 tile holds an edge pixel of `col` or (when given) of `blackout`."""
+    e = edge_pixels(fmt, col, t)
+    if blackout is not None:
+        e |= edge_pixels(fmt, blackout, t)
+    h, w = e.shape
+    ty, tx = (h + 7) // 8, (w + 7) // 8
+    p = np.zeros((ty * 8, tx * 8), bool)
+    p[:h, :w] = e
+    return p.reshape(ty, 8, tx, 8).any(axis=(1, 3)).astype(np.uint8)
+
+
+def pixel_mask(mask: np.ndarray, w: int, h: int) -> np.ndarray:
+    """the tile mask per pixel, (H, W) bool"""
+    return np.repeat(np.repeat(mask.astype(bool), 8, 0), 8, 1)[:h, :w]
+
+
+def stored(fmt: int, x: np.ndarray) -> np.ndarray:
+    """the fp32 RGBA image as `fmt` stores it, (H, W, 4) of the format's dtype"""
+    b = expected_bytes(fmt, x)
+    return np.ascontiguousarray(b).view(DT[fmt]).reshape(x.shape[0], x.shape[1], 4)
+
+
+@functools.lru_cache(maxsize=None)
+def plain(cam: str, w: int, h: int, fmt: int = bh.BH_OUT_RGBA32F):
+    """(col, blackout_col) of the oracle's plain frame as `fmt` stores it"""
+    col, bo, _ = oracle_virtual(cam, w, h, 1)
+    assert not np.isnan(col).any() and not np.isnan(bo).any(), "the oracle frame holds a NaN"
+    out = stored(fmt, col), stored(fmt, bo)
+    for x in out:
+        x.setflags(write=False)
+    return out
+
+
+@functools.lru_cache(maxsize=None)
+def composed(cam: str, w: int, h: int, k: int, fmt: int = bh.BH_OUT_RGBA32F, t: float = T, blackout: bool = True):
+    """(col, blackout_col, mask): where(mask, S_ref, P_ref) in the format's stored form, and the numpy mask of
+    the plain frame's stored bytes (col only when blackout is False)."""
+    pc, pb = plain(cam, w, h, fmt)
+    rc, rb = reference(cam, w, h, k)
+    m = tile_mask(fmt, pc, pb if blackout else None, t)
+    pm = pixel_mask(m, w, h)[..., None]
+    out = np.where(pm, stored(fmt, rc), pc), np.where(pm, stored(fmt, rb), pb), m
+    for x in out:
+        x.setflags(write=False)
+    return out

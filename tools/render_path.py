@@ -31,9 +31,13 @@ p.add_argument("--out", default="gpurun_out/path")
 p.add_argument("--no-png", action="store_true")
 p.add_argument("--ss", type=int, choices=[1, 2, 4, 8], default=1,
                help="rays per pixel side: ss x ss samples averaged in linear fp32 before the sRGB encode (bh_render_ss)")
+p.add_argument("--adaptive", type=float, default=None, metavar="T",
+               help="with --ss > 1: supersample only the 8x8 tiles that show an edge above T (bh_render_adaptive)")
 p.add_argument("--sky", default=None, help="image file for the sky (e.g. the reference's space_4096x2048.jpg); "
                                             "default: the synthetic sky")
 args = p.parse_args()
+if args.adaptive is not None and args.ss == 1:
+    p.error("--adaptive needs --ss 2, 4 or 8")
 W, H = args.width, args.height
 keys = []
 for item in filter(None, args.script.split(",")):
@@ -56,7 +60,7 @@ for f in range(args.frames):
         ctrl.process_key(k, a <= f <= b)
     cam, moved = ctrl.update_camera(cam, args.dt)
     scene.update(cam)
-    scene.render(col, bo, fmt=bh.BH_OUT_BGRA8_SRGB, ss=args.ss)
+    scene.render(col, bo, fmt=bh.BH_OUT_BGRA8_SRGB, ss=args.ss, adaptive=args.adaptive)
     scene.bloom(col, bo, surf)
     if not args.no_png:
         write_png(out_dir / f"frame_{f:04d}.png", surf.cpu().numpy())
@@ -64,5 +68,5 @@ for f in range(args.frames):
 torch.cuda.synchronize()
 dt = time.perf_counter() - t0
 (out_dir / "path.json").write_text(json.dumps(log, indent=0))
-print(json.dumps({"frames": args.frames, "width": W, "height": H, "ss": args.ss, "seconds": round(dt, 3),
+print(json.dumps({"frames": args.frames, "width": W, "height": H, "ss": args.ss, "adaptive": args.adaptive, "seconds": round(dt, 3),
                   "frames_per_s_incl_png": round(args.frames / dt, 2), "out": str(out_dir)}))
