@@ -76,6 +76,14 @@ class bh_adaptive_desc(C.Structure):
                 ("refined_tiles", C.c_void_p)]
 
 
+BH_LENS_BLACKOUT, BH_LENS_SURFACE = -1.0, -2.0  # u of a lens record whose ray ended in the hole / on a surface
+
+
+class bh_shade_desc(C.Structure):
+    _fields_ = [("width", C.c_uint32), ("height", C.c_uint32), ("ss", C.c_uint32), ("format", C.c_uint32),
+                ("lens", C.c_void_p), ("sky", C.c_void_p), ("out_col", C.c_void_p), ("out_blackout", C.c_void_p)]
+
+
 class bh_presenter_desc(C.Structure):
     _fields_ = [(n, C.c_uint32) for n in ("width", "height", "max_iters", "scene_flags", "math", "levels", "batch",
                                           "bloom_cus", "depth", "march_streams")]
@@ -115,6 +123,13 @@ SIGNATURES = {
     "bh_refine_mask_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_float,
                                       C.c_void_p]),
     "bh_refine_cover_host": (C.c_int, [C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]),
+    "bh_render_lens": (C.c_int, [C.c_void_p, C.POINTER(bh_camera_uniform), C.POINTER(bh_uniforms),
+                                 C.POINTER(bh_render_desc), C.c_void_p, C.c_void_p]),
+    "bh_sky_create": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(C.c_void_p)]),
+    "bh_sky_destroy": (C.c_int, [C.c_void_p]),
+    "bh_shade_lens": (C.c_int, [C.c_void_p, C.POINTER(bh_shade_desc), C.c_void_p]),
+    "bh_lens_shade_host": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint32,
+                                     C.c_uint32, C.c_void_p, C.c_void_p]),
     "bh_shard_tile_count": (C.c_int64, [C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32]),
     "bh_tiles_unpack": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32,
                                   C.c_uint64, C.c_uint32, C.c_void_p]),

@@ -48,7 +48,9 @@ struct MarchArgs {
     // are 0 for every other launch, whose kernels never read them.
     uint32_t ss_log2;
     uint32_t ss_out_width;
-    uint32_t reserved_[1];
+    // The third: != 0 for bh_render_lens, whose kernels store a lens record per ray into out_col (row-major)
+    // instead of shading it.  Read by the launchers only, never by a kernel.
+    uint32_t lens;
     // frame
     uint32_t width, height, max_iters, scene_flags;
     uint32_t format, layout;
@@ -94,7 +96,8 @@ static_assert(sizeof(MarchArgs) + 8 <= 4096, "MarchArgs must fit the kernel argu
 // the layout the existing kernels were compiled against: the supersampling words took the place of three
 // unused ones and moved nothing
 static_assert(offsetof(MarchArgs, far_r2) == 72 && offsetof(MarchArgs, ss_log2) == 76 &&
-                  offsetof(MarchArgs, ss_out_width) == 80 && offsetof(MarchArgs, width) == 88,
+                  offsetof(MarchArgs, ss_out_width) == 80 && offsetof(MarchArgs, lens) == 84 &&
+                  offsetof(MarchArgs, width) == 88,
               "MarchArgs: the supersampling words must stay inside the former reserved_[3]");
 static_assert(offsetof(MarchArgs, order) == 144 && offsetof(MarchArgs, sky) == 200 && offsetof(MarchArgs, out_col) == 232 &&
                   offsetof(MarchArgs, n_frames) == 272 && offsetof(MarchArgs, frames) == 304 &&
@@ -119,6 +122,19 @@ struct RefineArgs {
     uint32_t capacity;   // entries the list holds: n_frames * tiles_x * tiles_y at least
     uint32_t n_heads;    // 1..REFINE_HEADS head words in use (bh_march.hpp, march_refine_kernel)
     float thr;           // refine::threshold(format, T)
+};
+
+// One bh_shade_lens launch (bh_lens.hip): the lens of the virtual frame ss*width x ss*height, the sky to
+// sample and the row-major targets of width x height.
+struct LensShadeArgs {
+    const bh_lens_px* lens;
+    const uint32_t* sky;       // Rgba8UnormSrgb texels, as MarchArgs::sky
+    const float* srgb_lut;     // 256 entries
+    const float* srgb_enc;     // 257 thresholds (BGRA8 output)
+    void* out_col;
+    void* out_blackout;        // or null
+    uint32_t width, height;    // the OUTPUT frame
+    uint32_t sky_w, sky_h;
 };
 
 constexpr uint32_t REFINE_HEADS = 8, REFINE_HEAD_STRIDE = 32, REFINE_HEAD0 = 32;  // 128-byte lines
@@ -270,6 +286,9 @@ extern "C" __attribute__((visibility("hidden"))) int bh_launch_refine_fast(const
                                                                          uint32_t waves, hipStream_t s);
 extern "C" __attribute__((visibility("hidden"))) int bh_launch_refine_detect(const bh::MarchArgs& a, const bh::RefineArgs& r,
                                                                            hipStream_t s);
+// the lens shade (bh_lens.hip): ss in {1, 2, 4, 8}, format a bh_out_format
+extern "C" __attribute__((visibility("hidden"))) int bh_launch_lens_shade(const bh::LensShadeArgs& a, uint32_t ss,
+                                                                        uint32_t format, hipStream_t s);
 extern "C" __attribute__((visibility("hidden"))) int bh_march_blocks_per_cu_exact(void);
 extern "C" __attribute__((visibility("hidden"))) int bh_march_blocks_per_cu_fast(void);
 extern "C" __attribute__((visibility("hidden"))) int bh_launch_build_order(const uint8_t* cost, uint32_t n_tiles,

@@ -21,6 +21,7 @@
 #include "bh_srgb.hpp"
 #include "bh_refine.hpp"
 #include "bh_ss.hpp"
+#include "bh_lens.hpp"
 
 struct bh_ctx {
     int device = 0;
@@ -117,6 +118,15 @@ struct bh_ctx {
     // shader-clock probe of the march launches (bh_set_clock_probe): device accumulators or null
     unsigned long long* clk = nullptr;
     uint32_t clk_mask = 0;
+    // the skies of bh_sky_create that are still alive (bh_destroy frees what is left)
+    std::vector<bh_sky*> skies;
+};
+
+// A sky beside the context's own (include/bh_render.h, bh_sky_create): immutable device texels.
+struct bh_sky {
+    bh_ctx* ctx = nullptr;
+    uint32_t* texels = nullptr;
+    uint32_t w = 0, h = 0;
 };
 
 // A weighted tile partition (include/bh_render.h, bh_partition_create).
@@ -615,6 +625,10 @@ int bh_destroy(bh_ctx* c) {
     for (auto& o : c->orders) o.free_buffers();
     for (auto& b : c->blooms) free_bloom_scratch(b);
     for (auto& t : c->frame_tables) free_frame_table(t);
+    for (bh_sky* k : c->skies) {
+        (void)hipFree(k->texels);
+        delete k;
+    }
     delete c;
     return BH_OK;
 }
@@ -1406,7 +1420,7 @@ static bool sdf_skip_disabled() {
 
 static int render_frames_ss(bh_ctx* c, uint32_t n_frames, const bh_camera_uniform* cams, const bh_uniforms* U,
                             const bh_render_desc* descs, uint32_t ss, void* stream,
-                            const bh::RefineArgs* refine = nullptr);
+                            const bh::RefineArgs* refine = nullptr, bool lens = false);
 
 int bh_render_frames(bh_ctx* c, uint32_t n_frames, const bh_camera_uniform* cams, const bh_uniforms* U,
                      const bh_render_desc* descs, void* stream) {
@@ -1455,8 +1469,10 @@ int bh_render_frames_ss(bh_ctx* c, uint32_t n_frames, const bh_camera_uniform* c
 // -- with log2 k and the output width for the kernel's resolve epilogue.
 // `refine` (ss > 1, bh_render_frames_adaptive): the same launch arguments, but no order state and, in place
 // of the march over every tile, the detect kernel and the march over the work list it leaves.
+// `lens` (ss = 1, one frame, exact math, bh_render_lens): the same launch with the lens epilogue; out_col is the lens.
 static int render_frames_ss(bh_ctx* c, uint32_t n_frames, const bh_camera_uniform* cams, const bh_uniforms* U,
-                            const bh_render_desc* descs, uint32_t ss, void* stream, const bh::RefineArgs* refine) {
+                            const bh_render_desc* descs, uint32_t ss, void* stream, const bh::RefineArgs* refine,
+                            bool lens) {
     if (!c || !cams || !U || !descs || n_frames == 0 || n_frames > BH_MAX_FRAMES) return bad_arg(__func__, __LINE__);
     const bh_render_desc* const d0 = &descs[0];
     bh_render_desc vd = *d0;  // the launch's desc: the virtual frame's at ss > 1 (per-frame outputs stay in descs[i])
@@ -1500,6 +1516,7 @@ static int render_frames_ss(bh_ctx* c, uint32_t n_frames, const bh_camera_unifor
     a.far_r2 = a.skip_sdf ? sdf_far_r2(U->rs, U->delta_time_mult) : INFINITY;
     a.width = d->width; a.height = d->height; a.max_iters = d->max_iters; a.scene_flags = d->scene_flags;
     if (ss > 1u) { a.ss_log2 = bh::ss::log2_k(ss); a.ss_out_width = d0->width; }
+    a.lens = lens ? 1u : 0u;
     a.format = d->format; a.layout = d->layout;
     a.shard_index = d->shard_index; a.shard_count = d->shard_count;
     a.tiles_x = (d->width + 7u) / 8u; a.tiles_y = (d->height + 7u) / 8u;
@@ -1663,6 +1680,124 @@ int bh_ss_resolve_host(const float* samples, uint32_t width, uint32_t height, ui
                 o[3] = 1.0f;
             }
         }
+    return BH_OK;
+}
+
+// ---- lens maps (include/bh_render.h; the shading of a record: bh_lens.hpp) ---------------------------------
+int bh_render_lens(bh_ctx* c, const bh_camera_uniform* cam, const bh_uniforms* U, const bh_render_desc* d,
+                   bh_lens_px* out_lens, void* stream) {
+    if (!c || !cam || !U || !d || !out_lens || (reinterpret_cast<uintptr_t>(out_lens) & 7u)) return bad_arg(__func__, __LINE__);
+    const char* why = d->math != BH_MATH_EXACT ? "exact math (BH_MATH_EXACT): fast math has no defined bits to promise"
+                      : (d->out_col || d->out_blackout) ? "no out_col or out_blackout (it writes only the lens)"
+                                                        : ss_needs(d, 1u);
+    if (why) {
+        g_last_error = std::string("bh_render_lens: a lens render needs ") + why + ".";
+        return BH_ERR_UNSUPPORTED;
+    }
+    // bh_render's launch of this frame -- the same geometry, order state and repeated-frame key -- with the
+    // lens in place of target 0; the format word is not read
+    bh_render_desc ld = *d;
+    ld.format = BH_OUT_RGBA32F;
+    ld.out_col = out_lens;
+    return render_frames_ss(c, 1u, cam, U, &ld, 1u, stream, nullptr, true);
+}
+
+int bh_sky_create(bh_ctx* c, const uint8_t* rgba8, uint32_t w, uint32_t h, bh_sky** out) {
+    if (!c || !rgba8 || !out || w == 0 || h == 0 || w > 32768u || h > 32768u) return bad_arg(__func__, __LINE__);
+    *out = nullptr;
+    DeviceScope dev(c->device);
+    if (dev.err != hipSuccess) return hip_fail(dev.err, "hipSetDevice");
+    bh_sky* k = new (std::nothrow) bh_sky();
+    if (!k) return BH_ERR_OUT_OF_MEMORY;
+    k->ctx = c;
+    k->w = w;
+    k->h = h;
+    const size_t bytes = (size_t)w * h * 4u;
+    hipError_t e = hipMalloc(&k->texels, bytes);
+    if (e == hipSuccess) e = hipMemcpy(k->texels, rgba8, bytes, hipMemcpyHostToDevice);
+    if (e != hipSuccess) {
+        if (k->texels) (void)hipFree(k->texels);
+        delete k;
+        return e == hipErrorOutOfMemory ? BH_ERR_OUT_OF_MEMORY : hip_fail(e, "bh_sky_create");
+    }
+    c->skies.push_back(k);
+    *out = k;
+    return BH_OK;
+}
+
+int bh_sky_destroy(bh_sky* k) {
+    if (!k) return BH_OK;
+    bh_ctx* c = k->ctx;
+    DeviceScope dev(c->device);
+    c->skies.erase(std::remove(c->skies.begin(), c->skies.end(), k), c->skies.end());
+    (void)hipFree(k->texels);
+    delete k;
+    return BH_OK;
+}
+
+static bool lens_shape_ok(uint32_t width, uint32_t height, uint32_t ss) {
+    return bh::ss::log2_k(ss) <= 3u && width != 0 && height != 0 && (uint64_t)width * ss <= 65536u &&
+           (uint64_t)height * ss <= 65536u;
+}
+
+// Validation and one kernel launch: no allocation, no synchronisation, no state (capturable from the first call).
+int bh_shade_lens(bh_ctx* c, const bh_shade_desc* d, void* stream) {
+    if (!c || !d || !d->lens || !d->out_col || (reinterpret_cast<uintptr_t>(d->lens) & 7u)) return bad_arg(__func__, __LINE__);
+    if (!lens_shape_ok(d->width, d->height, d->ss) || d->format > BH_OUT_BGRA8_SRGB) return bad_arg(__func__, __LINE__);
+    if (d->sky && d->sky->ctx != c) return bad_arg(__func__, __LINE__);
+    bh::LensShadeArgs a;
+    a.lens = d->lens;
+    a.sky = d->sky ? d->sky->texels : c->sky;
+    a.sky_w = d->sky ? d->sky->w : c->sky_w;
+    a.sky_h = d->sky ? d->sky->h : c->sky_h;
+    a.srgb_lut = c->lut;
+    a.srgb_enc = c->enc;
+    a.out_col = d->out_col;
+    a.out_blackout = d->out_blackout;
+    a.width = d->width;
+    a.height = d->height;
+    DeviceScope dev(c->device);
+    if (dev.err != hipSuccess) return hip_fail(dev.err, "hipSetDevice");
+    const int e = bh_launch_lens_shade(a, d->ss, d->format, reinterpret_cast<hipStream_t>(stream));
+    if (e != 0) return hip_fail((hipError_t)e, "lens shade kernel launch");
+    return BH_OK;
+}
+
+// The shade kernel's per-pixel function (bh_lens.hpp, shade_pixel) in a loop over the output frame.
+extern "C++" template <int K>
+static void lens_shade_rows(const bh_lens_px* lens, uint32_t width, uint32_t height, const bh::lens::SkyView& s,
+                            const float* lut, float* out_col, float* out_bo) {
+    for (uint32_t y = 0; y < height; ++y)
+        for (uint32_t x = 0; x < width; ++x) {
+            const bh::lens::Acc p = out_bo ? bh::lens::shade_pixel<K, true>(lens, width, x, y, s, lut)
+                                           : bh::lens::shade_pixel<K, false>(lens, width, x, y, s, lut);
+            const bh::lens::Rgb col = p.col, bo = p.bo;
+            const size_t o = ((size_t)y * width + x) * 4u;
+            out_col[o] = col.r; out_col[o + 1] = col.g; out_col[o + 2] = col.b; out_col[o + 3] = 1.0f;
+            if (out_bo) { out_bo[o] = bo.r; out_bo[o + 1] = bo.g; out_bo[o + 2] = bo.b; out_bo[o + 3] = 1.0f; }
+        }
+}
+
+int bh_lens_shade_host(const bh_lens_px* lens, uint32_t width, uint32_t height, uint32_t ss, const uint8_t* sky,
+                       uint32_t sky_w, uint32_t sky_h, float* out_col, float* out_bo) {
+    if (!lens || !sky || !out_col || !lens_shape_ok(width, height, ss)) return bad_arg(__func__, __LINE__);
+    if (sky_w == 0 || sky_h == 0 || sky_w > 32768u || sky_h > 32768u) return bad_arg(__func__, __LINE__);
+    float lut[256];
+    srgb_lut(lut);
+    std::vector<uint32_t> texels;  // the packed little-endian words the device reads (the bytes may be unaligned)
+    try {
+        texels.resize((size_t)sky_w * sky_h);
+    } catch (const std::bad_alloc&) {
+        return BH_ERR_OUT_OF_MEMORY;
+    }
+    std::memcpy(texels.data(), sky, texels.size() * 4u);
+    const bh::lens::SkyView s{texels.data(), sky_w, sky_h};
+    switch (ss) {
+        case 1u: lens_shade_rows<1>(lens, width, height, s, lut, out_col, out_bo); break;
+        case 2u: lens_shade_rows<2>(lens, width, height, s, lut, out_col, out_bo); break;
+        case 4u: lens_shade_rows<4>(lens, width, height, s, lut, out_col, out_bo); break;
+        default: lens_shade_rows<8>(lens, width, height, s, lut, out_col, out_bo); break;
+    }
     return BH_OK;
 }
 

@@ -1022,10 +1022,12 @@ __device__ __forceinline__ void march_step2(const MarchArgs& a, const Frame& f, 
     alive1 = alive1 & !e1;
 }
 
-// Colour of a finished ray (:329-345 for sky rays; :275/:281 blackout -> 0; :287 surface -> 1).
-__device__ __forceinline__ v3 shade(const MarchArgs& a, const float* lut, uint32_t fate, v3 rd) {
-    if (fate == BH_FATE_BLACKOUT) return mk(0.0f, 0.0f, 0.0f);
-    if (fate == BH_FATE_SURFACE) return mk(1.0f, 1.0f, 1.0f);
+// The shading of a sky ray has two halves: where its final direction points in the sky (:329-336, sky_uv),
+// and the sample there (:341-343).  shade() runs both; the lens epilogue (march_tile_lens_kernel) stores the
+// first half's result, and bh_shade_lens runs the second on it later, with any sky (bh_lens.hpp: the same
+// ops, written for host and device).
+// (u, v): the two arguments of the sample at :341
+__device__ __forceinline__ void sky_uv(v3 rd, float& u, float& v) {
 #if BH_FAST
     const v3 n = normalize(rd);                             // :330
     const float az = atan2f(n.z, n.x);                      // :332
@@ -1044,7 +1046,18 @@ __device__ __forceinline__ v3 shade(const MarchArgs& a, const float* lut, uint32
     const float x = crm::div_core(az + ONE_PI, crm::Rcp{TWO_PI, 1.0f / TWO_PI});  // RN(1/2pi) folded
 #endif
     const float y = (n.y + 1.0f) * 0.5f;                    // :336
-    v3 col = sample_sky(a, lut, x, 1.0f - y);               // :341
+    u = x;
+    v = 1.0f - y;
+}
+// Colour of a finished ray (:329-345 for sky rays; :275/:281 blackout -> 0; :287 surface -> 1).
+// (The sampling half stays in this function: as a function of its own -- shade_uv(a, lut, u, v) -- every
+// march kernel's register allocation came out different; this form leaves their machine code as it was.)
+__device__ __forceinline__ v3 shade(const MarchArgs& a, const float* lut, uint32_t fate, v3 rd) {
+    if (fate == BH_FATE_BLACKOUT) return mk(0.0f, 0.0f, 0.0f);
+    if (fate == BH_FATE_SURFACE) return mk(1.0f, 1.0f, 1.0f);
+    float u, v;
+    sky_uv(rd, u, v);
+    v3 col = sample_sky(a, lut, u, v);                      // :341
 #if BH_FAST
     col.y = col.y * __builtin_sqrtf(col.y);                 // :342
     col.z = col.z * __builtin_sqrtf(col.z);                 // :343
@@ -1054,6 +1067,17 @@ __device__ __forceinline__ v3 shade(const MarchArgs& a, const float* lut, uint32
 #endif
     return col;
 }
+#if !BH_FAST
+// The lens record of a finished ray (include/bh_render.h, bh_lens_px): a sentinel u for the two fates that
+// have a colour of their own, else the sky coordinates -- what shade() hands to its sample.  Exact math only.
+__device__ __forceinline__ float2 lens_record(uint32_t fate, v3 rd) {
+    if (fate == BH_FATE_BLACKOUT) return make_float2(BH_LENS_BLACKOUT, 0.0f);
+    if (fate == BH_FATE_SURFACE) return make_float2(BH_LENS_SURFACE, 0.0f);
+    float u, v;
+    sky_uv(rd, u, v);
+    return make_float2(u, v);
+}
+#endif
 
 #ifndef BH_SKY_LDS
 #define BH_SKY_LDS 0
@@ -1570,10 +1594,13 @@ __device__ __forceinline__ void ss_resolve_store(const MarchArgs& a, const float
 // One dispatch slot, marched by one wave.  SS: the supersampled form (march_tile_ss_kernel).  ITEM (with SS):
 // a work item of the adaptive render (march_refine_kernel) -- `slot` is the frame and (item_tx, item_ty) the
 // tile of the virtual frame, both given by the caller's work list: no dispatch order, no cost feedback.
-template <uint32_t FMT, uint32_t SF, bool SS = false, bool ITEM = false>
+// LENS (exact math, march_tile_lens_kernel): the epilogue stores the ray's lens record instead of shading it;
+// `lut` is not read.
+template <uint32_t FMT, uint32_t SF, bool SS = false, bool ITEM = false, bool LENS = false>
 __device__ __forceinline__ void march_slot(const MarchArgs& A, uint32_t slot, const float* lut,
                                            uint32_t lane, uint32_t item_tx = 0u, uint32_t item_ty = 0u) {
     static_assert(SS || !ITEM, "work items are supersampled tiles");
+    static_assert(!LENS || (!SS && !BH_FAST), "a lens is one record per ray, in exact math");
     const uint32_t nf = A.n_frames;
     uint32_t fi = 0, j = slot;
     if constexpr (ITEM) {
@@ -1644,12 +1671,20 @@ __device__ __forceinline__ void march_slot(const MarchArgs& A, uint32_t slot, co
         asm volatile("" : "+s"(fo));
         if (A.frame_table) select_outputs(a, A.frame_table[fo]);
         else select_outputs(a, A.frames[fo]);
+#if !BH_FAST
+        if constexpr (LENS) {
+            // out_col is the lens (bh_render_lens: row-major, whole frame): one 8-byte vector store per lane
+            reinterpret_cast<float2*>(a.out_col)[(size_t)py * a.width + px] = lens_record(fate, st.rd);
+        } else
+#endif
+        {
 #if BH_SKY_LDS && !BH_FAST
         const v3 col = shade_tile(a, lut, fate, st.rd, reinterpret_cast<uint32_t*>(&hist_lds<0>()[threadIdx.x >> 6]), lane);
 #else
         const v3 col = shade(a, lut, fate, st.rd);
 #endif
         write_pixel<FMT>(a, lut, out_index(a, t, lane, px, py), col, st.n_rk, fate, steps);
+        }
     }
     if (a.tile_cost) {
         // the next frame's cost and its bucket histogram (a no-return atomic: the wave does not wait);
@@ -1726,6 +1761,22 @@ __global__ void __launch_bounds__(64 * WG_WAVES) march_tile_ss_kernel(MarchArgs 
     march_slot<FMT, SF, true>(A, slot, lut, threadIdx.x & 63u);
     if (probe) clock_end(A.clk, c0);
 }
+
+#if !BH_FAST
+// The tile schedule's lens form (bh_render_lens): march_tile_kernel's waves -- order, cost feedback, cycle
+// fast-forward -- with the lens record as the epilogue: no sky, no tables, no encode, one kernel per
+// scene-flag fold.
+template <uint32_t SF>
+__global__ void __launch_bounds__(64 * WG_WAVES) march_tile_lens_kernel(MarchArgs A) {
+    const uint32_t slot = __builtin_amdgcn_readfirstlane(blockIdx.x * WG_WAVES + (threadIdx.x >> 6));
+    if (slot >= A.n_tiles * A.n_frames) return;  // wave-uniform
+    const bool probe = A.clk && ((slot + (slot >> 8)) & A.clk_mask) == 0u;
+    ClockStart c0{0u, 0u};
+    if (probe) c0 = clock_start();
+    march_slot<BH_OUT_RGBA32F, SF, false, false, true>(A, slot, nullptr, threadIdx.x & 63u);
+    if (probe) clock_end(A.clk, c0);
+}
+#endif
 
 // The adaptive render's second pass (bh_render_adaptive; bh_refine.hpp): the supersampled march over a work
 // list that the detect kernel (bh_tiles.hip) left on the device.  The host never learns the list's length, so
@@ -1974,6 +2025,15 @@ inline void launch_tile_ss_schedule(const MarchArgs& a, hipStream_t s) {
     const uint32_t blocks = (waves + (WG_WAVES - 1u)) / WG_WAVES;
     hipLaunchKernelGGL((march_tile_ss_kernel<FMT, SF>), dim3(blocks), dim3(64u * WG_WAVES), 0, s, a);
 }
+#if !BH_FAST
+// ... and its lens form (a.lens set, out_col the lens)
+template <uint32_t SF>
+inline void launch_tile_lens_schedule(const MarchArgs& a, hipStream_t s) {
+    const uint32_t waves = a.n_tiles * a.n_frames;
+    const uint32_t blocks = (waves + (WG_WAVES - 1u)) / WG_WAVES;
+    hipLaunchKernelGGL((march_tile_lens_kernel<SF>), dim3(blocks), dim3(64u * WG_WAVES), 0, s, a);
+}
+#endif
 // ... and the adaptive render's work-list march: `waves` resident waves that pull (march_refine_kernel)
 template <uint32_t FMT, uint32_t SF>
 inline void launch_refine_schedule(const MarchArgs& a, const RefineArgs& r, uint32_t waves, hipStream_t s) {

@@ -46,11 +46,22 @@ int launch(const bh::MarchArgs& a, uint32_t schedule, uint32_t* counters, uint32
     }
     return (int)hipGetLastError();
 }
+// bh_render_lens (a.lens, tile schedule): one kernel per scene-flag fold, whatever the format word says
+int launch_lens(const bh::MarchArgs& a, hipStream_t s) {
+    if (a.scene_flags == BH_SCENE_DEFAULT)
+        bh::BH_NS::launch_tile_lens_schedule<BH_SCENE_DEFAULT>(a, s);
+    else if (a.scene_flags == 0u)
+        bh::BH_NS::launch_tile_lens_schedule<0u>(a, s);
+    else
+        bh::BH_NS::launch_tile_lens_schedule<bh::BH_NS::SF_DYN>(a, s);
+    return (int)hipGetLastError();
+}
 }  // namespace
 
 extern "C" __attribute__((visibility("hidden"))) int BH_EXACT_LAUNCH(const bh::MarchArgs& a, uint32_t schedule,
                                                                              uint32_t* counters, uint32_t grid,
                                                                              hipStream_t s) {
+    if (a.lens != 0u) return schedule == BH_SCHED_TILE ? launch_lens(a, s) : (int)hipErrorInvalidValue;
     switch (a.format) {
         case BH_OUT_RGBA32F: return launch<BH_OUT_RGBA32F>(a, schedule, counters, grid, s);
         case BH_OUT_RGBA16F: return launch<BH_OUT_RGBA16F>(a, schedule, counters, grid, s);

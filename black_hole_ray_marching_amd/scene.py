@@ -237,6 +237,23 @@ def ss_resolve_host(samples: np.ndarray, ss: int) -> np.ndarray:
     return out
 
 
+def lens_shade_host(lens: np.ndarray, sky: np.ndarray, ss: int = 1):
+    """bh_lens_shade_host (host only): what the lens shade kernel runs, on the CPU.  `lens`: (ss*H, ss*W, 2)
+    float32 records (u, v); `sky`: (h, w, 4) uint8 RGBA8 sRGB -> (col, blackout_col), fp32 (H, W, 4)."""
+    ln = np.ascontiguousarray(lens, np.float32)
+    s = np.ascontiguousarray(sky, np.uint8)
+    k = _ss_arg(ss)
+    if ln.ndim != 3 or ln.shape[2] != 2 or s.ndim != 3 or s.shape[2] != 4:
+        raise BhError(_abi.BH_ERR_INVALID_ARG, "lens_shade_host: lens must be (ss*H, ss*W, 2), sky (h, w, 4)")
+    if k == 0 or ln.shape[0] % k or ln.shape[1] % k:
+        raise BhError(_abi.BH_ERR_INVALID_ARG, "lens_shade_host: the lens sides must be multiples of ss")
+    h, w = ln.shape[0] // k, ln.shape[1] // k
+    col, bo = np.empty((h, w, 4), np.float32), np.empty((h, w, 4), np.float32)
+    check(load().bh_lens_shade_host(ln.ctypes.data, w, h, k, s.ctypes.data, s.shape[1], s.shape[0], col.ctypes.data,
+                                    bo.ctypes.data), "bh_lens_shade_host")
+    return col, bo
+
+
 def _adaptive_desc(ss, adaptive, tile_mask, refined_tiles, n_frames: int, width: int, height: int):
     """The bh_adaptive_desc of a render call (adaptive = T, not None); the optional device buffers are size-checked."""
     try:
@@ -358,8 +375,11 @@ class Scene:
         check(self.lib.bh_create(sky.ctypes.data, sky.shape[1], sky.shape[0], device, C.byref(ctx)), "bh_create")
         self._ctx = ctx
         self.device = device
+        self._skies = []  # the live Sky objects of this scene (closed with it)
 
     def close(self) -> None:
+        for s in list(getattr(self, "_skies", [])):
+            s.close()
         if getattr(self, "_ctx", None):
             self.lib.bh_destroy(self._ctx)
             self._ctx = None
@@ -493,6 +513,39 @@ class Scene:
         a = _adaptive_desc(ss, adaptive, tile_mask, refined_tiles, n, descs[0].width, descs[0].height)
         return FrameBatch(self, descs, keep, _ss_arg(ss), a)
 
+    def render_lens(self, lens, *, width: int | None = None, height: int | None = None, schedule: int = 0,
+                    stream=None) -> None:
+        """bh_render_lens: march this scene's camera once into `lens`, a device buffer of height x width records
+        (u, v) of 8 bytes (e.g. a float32 tensor (H, W, 2)) -- the view, without any sky.  Exact math, whatever
+        the scene's math mode.  Shade it with shade(), as often and with as many skies as wanted."""
+        d = _abi.bh_render_desc()
+        d.width, d.height = width or self.width, height or self.height
+        d.max_iters, d.scene_flags = self.max_iters, self.scene_flags
+        d.math, d.layout, d.shard_count, d.schedule = BH_MATH_EXACT, BH_LAYOUT_ROWMAJOR, 1, schedule
+        if lens is None:
+            raise BhError(_abi.BH_ERR_INVALID_ARG, "render_lens: lens is required")
+        _check_size(lens, d.width * d.height * 8, "lens", "render_lens")
+        check(self.lib.bh_render_lens(self._ctx, C.byref(self.camera_uniform.c), C.byref(self.uniforms.to_c()),
+                                      C.byref(d), _ptr(lens), _stream_handle(stream)), "bh_render_lens")
+
+    def shade(self, lens, output, blackout_output=None, *, fmt: int = BH_OUT_RGBA32F, sky: "Sky | None" = None,
+              ss: int = 1, width: int | None = None, height: int | None = None, stream=None) -> None:
+        """bh_shade_lens: `lens` (render_lens of ss*width x ss*height) and a sky -> the bytes render() -- with
+        ss > 1, render(ss=ss) -- writes for that view with that sky.  `sky`: a Sky of this scene, or None for the
+        scene's own.  Asynchronous on `stream`; allocates nothing (capturable from the first call)."""
+        k = _ss_arg(ss)
+        d = _abi.bh_shade_desc()
+        d.width, d.height, d.ss, d.format = width or self.width, height or self.height, k, fmt
+        if sky is not None and (sky.scene is not self or not sky.handle):
+            raise BhError(_abi.BH_ERR_INVALID_ARG, "shade: sky must be an open Sky of this scene")
+        _check_size(lens, d.width * d.height * k * k * 8, "lens", "shade")
+        need = d.width * d.height * BYTES_PER_PIXEL.get(fmt, 0)
+        _check_size(output, need, "output", "shade")
+        _check_size(blackout_output, need, "blackout_output", "shade")
+        d.lens, d.sky = _ptr(lens), None if sky is None else sky.handle
+        d.out_col, d.out_blackout = _ptr(output), _ptr(blackout_output)
+        check(self.lib.bh_shade_lens(self._ctx, C.byref(d), _stream_handle(stream)), "bh_shade_lens")
+
     def set_clock_probe(self, acc, stride: int = 256) -> None:
         """bh_set_clock_probe: arm (acc = a zeroed device buffer of 128 u64) or disarm (acc = None) the
         shader-clock sampling of this scene's march launches; clock_mhz() reads the result."""
@@ -520,6 +573,36 @@ class Scene:
             _check_size(t, need, name, "bloom")
         check(self.lib.bh_bloom(self._ctx, _ptr(col), _ptr(blackout), width or self.width, height or self.height,
                                 levels, schedule, _ptr(out), _stream_handle(stream)), "bh_bloom")
+
+
+class Sky:
+    """bh_sky (include/bh_render.h): a sky beside the scene's own, for Scene.shade(sky=...).  `array`: (h, w, 4)
+    uint8 RGBA8 sRGB texels (synthetic_sky, load_sky).  It belongs to `scene`; Scene.close() closes it."""
+
+    def __init__(self, scene: "Scene", array: np.ndarray) -> None:
+        a = np.ascontiguousarray(array, dtype=np.uint8)
+        if a.ndim != 3 or a.shape[2] != 4:
+            raise ValueError("sky must be (H, W, 4) uint8 RGBA (Rgba8UnormSrgb texels)")
+        self.scene, self.width, self.height = scene, a.shape[1], a.shape[0]
+        h = C.c_void_p()
+        check(scene.lib.bh_sky_create(scene._ctx, a.ctypes.data, a.shape[1], a.shape[0], C.byref(h)), "bh_sky_create")
+        self.handle = h.value
+        scene._skies.append(self)
+
+    def close(self) -> None:
+        """Free the device texels (after the shades that read them have completed).  A no-op when already
+        closed, by hand or by Scene.close()."""
+        if getattr(self, "handle", None):
+            self.scene.lib.bh_sky_destroy(self.handle)
+            self.handle = None
+            if self in self.scene._skies:
+                self.scene._skies.remove(self)
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 class Presenter:
@@ -714,7 +797,7 @@ def tiles_unpack_rgbm_partition(packed, out_col, out_blackout, partition: "Parti
           "bh_tiles_unpack_rgbm_partition")
 
 
-__all__ = ["Camera", "ss_resolve_host", "refine_mask_host", "refine_cover_host", "Partition", "Presenter", "partition_map", "tiles_unpack_rgbm_partition", "CameraController", "CameraUniform", "Uniforms", "Scene", "synthetic_sky", "shard_tile_count", "tiles_unpack",
+__all__ = ["Camera", "Sky", "lens_shade_host", "ss_resolve_host", "refine_mask_host", "refine_cover_host", "Partition", "Presenter", "partition_map", "tiles_unpack_rgbm_partition", "CameraController", "CameraUniform", "Uniforms", "Scene", "synthetic_sky", "shard_tile_count", "tiles_unpack",
            "tiles_unpack_rgb", "tiles_unpack_rgbm", "tile_bytes", "BH_LAYOUT_TILES_RGBM", "BH_LAYOUT_TILES_RGBM14",
            "BH_UNPACK_RGBM14",
            "srgb_encode_table", "load_sky", "bloom_plan_failures", "BH_OUT_BGRA8_SRGB",

@@ -365,6 +365,63 @@ int bh_refine_mask_host(const void* col, const void* blackout_or_NULL, uint32_t 
  * BH_ERR_INTERNAL if a store index falls outside the frame. */
 int bh_refine_cover_host(uint32_t width, uint32_t height, uint32_t ss, const uint8_t* tile_mask, uint8_t* pixel_writes);
 
+/* Lens maps: march a view once, shade it with any sky (not in the reference, whose every frame marches).
+ * For a fixed camera the march's result per pixel -- where the ray ended and, for a sky ray, the two texture
+ * coordinates of its sample (src/black_hole_maybe.wgsl:334-341) -- is a function of camera, uniforms, cap and
+ * scene flags only, not of the sky or its size.  bh_render_lens stores it, 8 bytes per pixel; bh_shade_lens
+ * turns it into the bytes bh_render would have written with that sky, bit for bit.  Exact math only.
+ * The record (normative):
+ *   sky rays (fate BH_FATE_CAP or BH_FATE_ESCAPE): (u, v) = the two fp32 arguments of the sample at :341 from
+ *     the exact-math path: n = rd / sqrt(dot(rd, rd)), u = (RN_f32(atan2_f64(n.z, n.x)) + ONE_PI) / TWO_PI,
+ *     v = 1 - (n.y + 1) * 0.5.  A sky ray's u is never negative (az + pi is +0 or >= 2^-22).  NaNs are stored
+ *     as they come; the sampler's "NaN -> texel (0, 0)" rule applies at shade time.
+ *   the other two fates: the sentinels below in u, v = +0.
+ * Shading a record with a sky of w x h texels is the existing arithmetic and nothing else:
+ *   u == BH_LENS_BLACKOUT -> col (0, 0, 0); u == BH_LENS_SURFACE -> col (1, 1, 1); otherwise the bilinear
+ *   sample of :341 (Rgba8UnormSrgb, clamp to edge), then g, b <- c * sqrt(c) (:342-343);
+ *   blackout_col = dot(col, col) < 1 ? 0 : col, in fp32 before the encode; alpha 1.
+ * With ss = k in {2, 4, 8} the lens is that of the virtual frame k*width x k*height (bh_render_lens of that
+ *   size with the output frame's camera uniform): each record is shaded as above, the blackout test per sample,
+ *   the k x k block resolved by bh_render_ss's normative tree (pairwise along x, the same along y, one multiply
+ *   by 1 / k^2, fp32, no FMA), then the format's encode -- the bytes of bh_render_ss, the march paid once per
+ *   view instead of once per sky. */
+typedef struct { float u, v; } bh_lens_px;      /* 8 bytes, row-major, lens[y * width + x] */
+#define BH_LENS_BLACKOUT (-1.0f)                /* u of a ray with fate BH_FATE_BLACKOUT; v = +0 */
+#define BH_LENS_SURFACE  (-2.0f)                /* u of a ray with fate BH_FATE_SURFACE;  v = +0 */
+/* March the frame of `desc` and write only out_lens (device, width * height records, 8-byte aligned).  Taken
+ * from the desc: width, height, max_iters, scene_flags, math, schedule.  BH_ERR_UNSUPPORTED, with a sentence in
+ * bh_last_error(), for: math != BH_MATH_EXACT (fast math has no defined bits to promise), a layout other than
+ * BH_LAYOUT_ROWMAJOR, shard_count != 1, a partition, a base schedule other than BH_SCHED_TILE, any dbg_*
+ * pointer, a non-NULL out_col or out_blackout.  The BH_SCHED_FLAG_* flags are allowed.  It marches exactly
+ * bh_render's rays in bh_render's tile order and shares that geometry's order state and repeated-frame key on
+ * the stream, under bh_render's graph contract: the first call of a key allocates and is refused under capture. */
+int bh_render_lens(bh_ctx* ctx, const bh_camera_uniform* camera, const bh_uniforms* uniforms, const bh_render_desc* desc,
+                   bh_lens_px* out_lens, void* hip_stream);
+/* A sky beside the context's own: rgba8_srgb as bh_create's (w * h * 4 bytes, each side 1..32768), uploaded to
+ * the context's device before the call returns.  A bh_sky belongs to its context, is immutable, and must be
+ * destroyed before bh_destroy -- after the shades that read it have completed; bh_destroy frees any that are
+ * left (their handles are dangling from then on). */
+typedef struct bh_sky bh_sky;
+int bh_sky_create(bh_ctx* ctx, const uint8_t* rgba8_srgb, uint32_t w, uint32_t h, bh_sky** out);
+int bh_sky_destroy(bh_sky* sky);
+typedef struct {
+    uint32_t width, height, ss, format;   /* output size; ss in {1,2,4,8}; bh_out_format */
+    const bh_lens_px* lens;               /* (ss*height) x (ss*width) records, device, 8-byte aligned */
+    const bh_sky* sky;                    /* NULL = the context's own sky */
+    void* out_col; void* out_blackout;    /* row-major device images; out_blackout may be NULL */
+} bh_shade_desc;
+/* Shade a lens.  Asynchronous on the stream; allocates nothing and never synchronises, so it is capturable
+ * from its first call; keeps no state between calls.  BH_ERR_INVALID_ARG for: ss outside {1, 2, 4, 8}, a NULL
+ * or misaligned lens, a NULL out_col, a zero size, ss * width or ss * height above 65536, an unknown format, a
+ * sky of another context. */
+int bh_shade_lens(bh_ctx* ctx, const bh_shade_desc* desc, void* hip_stream);
+/* Host only (no device needed): what the shade kernel runs (csrc/bh_lens.hpp), on the CPU, for tests -- the
+ * render path never calls it.  lens: (ss*height) x (ss*width) records; sky_rgba8: sky_w x sky_h texels; the
+ * outputs are fp32 RGBA, width x height (the RGBA32F bytes of bh_shade_lens).  BH_ERR_INVALID_ARG as above. */
+int bh_lens_shade_host(const bh_lens_px* lens, uint32_t width, uint32_t height, uint32_t ss,
+                       const uint8_t* sky_rgba8, uint32_t sky_w, uint32_t sky_h,
+                       float* out_col_rgba, float* out_blackout_rgba_or_NULL);
+
 /* Bloom::render (src/bloom.rs:53-71): the reference's Kawase bloom + remix chain over the scene's two
  * targets, on BGRA8-sRGB images (bh_render with BH_OUT_BGRA8_SRGB): `col` (full_image_input),
  * `blackout` (blackout_input) -> `out` (the surface), all width x height (1..65536 each, as bh_render),

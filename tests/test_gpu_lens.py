@@ -1,0 +1,344 @@
+"""Lens maps on the GPU (bh_render_lens / bh_shade_lens; Scene.render_lens, Scene.shade, bh.Sky): the records
+equal the reference records of tests/_lens_ref.py (the CPU oracle's rays) and every shade of them equals the CPU
+oracle's frame with that sky -- for ss > 1 tests/_ss_ref.py's normative resolve of the oracle's virtual frame
+-- bit for bit.  The reference is never the GPU's own output; where a test also compares two GPU results
+(shade against Scene.render), both have been compared with the oracle first."""
+import ctypes as C
+
+import numpy as np
+import pytest
+
+import black_hole_ray_marching_amd as bh
+from black_hole_ray_marching_amd import _abi
+from tests._cases import camera_uniform, uniforms
+from tests._lens_ref import CAMS, SIZES, SKIES, frame, records, sky
+from tests._ss_ref import CAP, FLAGS, expected_bytes, sky_ss
+
+pytestmark = pytest.mark.gpu
+
+DT = {bh.BH_OUT_RGBA32F: "float32", bh.BH_OUT_RGBA16F: "float16", bh.BH_OUT_BGRA8_SRGB: "uint8"}
+FMTS = [bh.BH_OUT_RGBA32F, bh.BH_OUT_RGBA16F, bh.BH_OUT_BGRA8_SRGB]
+F32 = bh.BH_OUT_RGBA32F
+SENTINEL = 0xA5  # every byte of a buffer before a call
+GUARD = 64       # records after the last one that must keep their sentinels
+
+
+@pytest.fixture(scope="module")
+def torch_cuda():
+    torch = pytest.importorskip("torch")
+    if not torch.cuda.is_available():
+        pytest.skip("no GPU")
+    return torch
+
+
+def new_scene(math=bh.BH_MATH_EXACT):
+    return bh.Scene(16, 16, sky=sky_ss(), max_iters=CAP, scene_flags=FLAGS, math=math)
+
+
+@pytest.fixture(scope="module")
+def scene(torch_cuda):
+    s = new_scene()
+    s.test_skies = {"ctx": None, "96x40": bh.Sky(s, sky("96x40")), "1x1": bh.Sky(s, sky("1x1"))}
+    yield s
+    s.close()
+
+
+def target(torch, W, H, fmt):
+    t = torch.full((H, W, 4 * _abi.BYTES_PER_PIXEL[fmt] // 4), SENTINEL, dtype=torch.uint8, device="cuda")
+    return t.view(getattr(torch, DT[fmt]))
+
+
+def lens_buffer(torch, W, H):
+    """W * H records and GUARD more, every byte the sentinel"""
+    return torch.full((W * H + GUARD, 2), SENTINEL, dtype=torch.uint8, device="cuda").repeat(1, 4).view(torch.float32)
+
+
+def as_bytes(t):
+    return t.cpu().numpy().view(np.uint8)
+
+
+def untouched(*ts):
+    return all((as_bytes(t) == SENTINEL).all() for t in ts if t is not None)
+
+
+def render_lens(torch, sc, cam, W, H, k=1, **kw):
+    """the lens of the (virtual) frame kW x kH with the camera uniform of W x H, guard checked"""
+    sc.camera_uniform, sc.uniforms = camera_uniform(cam, W, H), uniforms()
+    buf = lens_buffer(torch, k * W, k * H)
+    assert buf.shape == (k * W * k * H + GUARD, 2) and untouched(buf)
+    sc.render_lens(buf, width=k * W, height=k * H, **kw)
+    torch.cuda.synchronize()
+    assert untouched(buf[k * W * k * H:]), "the guard region after the last record was written"
+    return buf[:k * W * k * H]
+
+
+def assert_records(lens, cam, W, H, what):
+    got = lens.cpu().numpy().reshape(H, W, 2).view(np.uint32)
+    want = records(cam, W, H)[0].view(np.uint32)
+    bad = (got != want).any(-1)
+    assert not bad.any(), f"{what}: {int(bad.sum())} records differ, first at {np.argwhere(bad)[:4].tolist()}"
+
+
+def assert_frame(got, want, what):
+    want = np.ascontiguousarray(want).view(np.uint8).reshape(got.shape)
+    bad = (got != want).any(-1)
+    assert not bad.any(), f"{what}: {int(bad.sum())} pixels differ, first at {np.argwhere(bad)[:4].tolist()}"
+
+
+def shade(torch, sc, lens, W, H, fmt=F32, sky_name="ctx", blackout=True, ss=1, **kw):
+    """(col bytes, blackout bytes or None) of Scene.shade into sentinel-filled targets"""
+    col = target(torch, W, H, fmt)
+    bo = target(torch, W, H, fmt) if blackout else None
+    sc.shade(lens, col, bo, fmt=fmt, sky=sc.test_skies[sky_name], ss=ss, width=W, height=H, **kw)
+    torch.cuda.synchronize()
+    return as_bytes(col), None if bo is None else as_bytes(bo)
+
+
+@pytest.mark.parametrize("W,H", SIZES)
+@pytest.mark.parametrize("cam", CAMS)
+def test_records_equal_the_reference(torch_cuda, cam, W, H):
+    """A fresh scene: the first call marches in the centre-out order, the second in the order learned from the
+    first's tile costs (a repeated frame), the third after a plain render of the same geometry (shared state)."""
+    sc = new_scene()
+    try:
+        for order in ("centre-out", "learned"):
+            assert_records(render_lens(torch_cuda, sc, cam, W, H), cam, W, H, f"{order} order")
+        col = target(torch_cuda, W, H, F32)
+        sc.render(col, width=W, height=H)
+        assert_records(render_lens(torch_cuda, sc, cam, W, H), cam, W, H, "after a plain render")
+        assert_frame(as_bytes(col), frame(cam, W, H, "ctx")[0], "the plain render between two lens renders")
+    finally:
+        sc.close()
+
+
+@pytest.mark.parametrize("flag", [bh.BH_SCHED_FLAG_ISSUE_ORDER, bh.BH_SCHED_FLAG_LATENCY, bh.BH_SCHED_FLAG_STATIC_ORDER])
+@pytest.mark.parametrize("W,H", SIZES)
+def test_records_from_each_exact_build(torch_cuda, scene, W, H, flag):
+    assert_records(render_lens(torch_cuda, scene, "E", W, H, schedule=bh.BH_SCHED_TILE | flag), "E", W, H, f"flag {flag:#x}")
+
+
+@pytest.mark.parametrize("W,H", SIZES)
+@pytest.mark.parametrize("cam", CAMS)
+def test_shade_equals_the_oracle(torch_cuda, scene, cam, W, H):
+    """One lens, the three skies, the three formats, with and without the blackout target."""
+    torch = torch_cuda
+    lens = render_lens(torch, scene, cam, W, H)
+    for sky_name in SKIES:
+        wc, wb = frame(cam, W, H, sky_name)
+        for fmt in FMTS:
+            col, bo = shade(torch, scene, lens, W, H, fmt, sky_name)
+            assert_frame(col, expected_bytes(fmt, wc), f"{sky_name} fmt {fmt} col")
+            assert_frame(bo, expected_bytes(fmt, wb), f"{sky_name} fmt {fmt} blackout_col")
+            other = target(torch, W, H, fmt)
+            col, bo = shade(torch, scene, lens, W, H, fmt, sky_name, blackout=False)
+            assert bo is None and untouched(other)
+            assert_frame(col, expected_bytes(fmt, wc), f"{sky_name} fmt {fmt} col alone")
+
+
+@pytest.mark.parametrize("fmt", FMTS)
+def test_shade_with_the_scene_sky_is_render(torch_cuda, scene, fmt):
+    torch = torch_cuda
+    W, H = 40, 24
+    lens = render_lens(torch, scene, "E", W, H)
+    col, bo = shade(torch, scene, lens, W, H, fmt)
+    rc, rb = target(torch, W, H, fmt), target(torch, W, H, fmt)
+    scene.render(rc, rb, fmt=fmt, width=W, height=H)
+    torch.cuda.synchronize()
+    assert np.array_equal(col, as_bytes(rc)) and np.array_equal(bo, as_bytes(rb))
+
+
+@pytest.mark.parametrize("W,H,k", [(13, 7, 2), (13, 7, 4), (13, 7, 8), (40, 24, 2), (40, 24, 4)])
+@pytest.mark.parametrize("cam", ["E", "H"])
+def test_shade_ss(torch_cuda, scene, cam, W, H, k):
+    """A lens of the virtual frame kW x kH shaded with ss = k: the normative resolve of the oracle's virtual
+    frame with the 96x40 sky in every format, and Scene.render(ss=k)'s bytes with the scene's sky."""
+    torch = torch_cuda
+    lens = render_lens(torch, scene, cam, W, H, k)
+    wc, wb = frame(cam, W, H, "96x40", k)
+    for fmt in FMTS:
+        col, bo = shade(torch, scene, lens, W, H, fmt, "96x40", ss=k)
+        assert_frame(col, expected_bytes(fmt, wc), f"fmt {fmt} col")
+        assert_frame(bo, expected_bytes(fmt, wb), f"fmt {fmt} blackout_col")
+    col, bo = shade(torch, scene, lens, W, H, F32, "96x40", blackout=False, ss=k)
+    assert_frame(col, expected_bytes(F32, wc), "col alone")
+    wc, wb = frame(cam, W, H, "ctx", k)
+    col, bo = shade(torch, scene, lens, W, H, F32, ss=k)
+    assert_frame(col, expected_bytes(F32, wc), "scene sky col")
+    assert_frame(bo, expected_bytes(F32, wb), "scene sky blackout_col")
+    rc, rb = target(torch, W, H, F32), target(torch, W, H, F32)
+    scene.render(rc, rb, width=W, height=H, ss=k)
+    torch.cuda.synchronize()
+    assert np.array_equal(col, as_bytes(rc)) and np.array_equal(bo, as_bytes(rb))
+
+
+def test_no_state_between_shades(torch_cuda, scene):
+    """One lens, the three skies back to back on one stream, then in reverse order: the same bytes."""
+    torch = torch_cuda
+    W, H = 40, 24
+    lens = render_lens(torch, scene, "E", W, H)
+    s = torch.cuda.Stream()
+    s.wait_stream(torch.cuda.current_stream())
+    runs = []
+    for order in (SKIES, SKIES[::-1]):
+        outs = {n: (target(torch, W, H, F32), target(torch, W, H, F32)) for n in order}
+        for n in order:
+            scene.shade(lens, *outs[n], sky=scene.test_skies[n], width=W, height=H, stream=s)
+        s.synchronize()
+        runs.append({n: (as_bytes(c), as_bytes(b)) for n, (c, b) in outs.items()})
+    for n in SKIES:
+        wc, wb = frame("E", W, H, n)
+        for run in runs:
+            assert_frame(run[n][0], wc, f"{n} col")
+            assert_frame(run[n][1], wb, f"{n} blackout_col")
+
+
+def test_graph(torch_cuda):
+    """A shade is capturable from its first call: captured on a single stream and replayed twice into
+    sentinel-filled targets it gives the reference bytes.  In the same capture a render_lens of a geometry that
+    was never rendered is refused with BH_ERR_UNSUPPORTED, as bh_render's would be, and writes nothing."""
+    torch = torch_cuda
+    W, H = 40, 24
+    sc = new_scene()
+    try:
+        other = bh.Sky(sc, sky("96x40"))
+        lens = render_lens(torch, sc, "E", W, H)
+        new_lens = lens_buffer(torch, 13, 7)
+        col, bo = target(torch, W, H, F32), target(torch, W, H, F32)
+        s = torch.cuda.Stream()
+        torch.cuda.synchronize()
+        g = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(g, stream=s):
+            with pytest.raises(bh.BhError) as e:
+                sc.render_lens(new_lens, width=13, height=7, stream=s)
+            assert e.value.status == _abi.BH_ERR_UNSUPPORTED
+            sc.shade(lens, col, bo, sky=other, width=W, height=H, stream=s)
+        wc, wb = frame("E", W, H, "96x40")
+        for _ in range(2):
+            for t in (col, bo):
+                t.view(torch.uint8).fill_(SENTINEL)
+            torch.cuda.synchronize()
+            g.replay()
+            torch.cuda.synchronize()
+            assert_frame(as_bytes(col), wc, "replay: col")
+            assert_frame(as_bytes(bo), wb, "replay: blackout_col")
+            assert untouched(new_lens)
+        del g
+        sc.graph_release()
+    finally:
+        sc.close()
+
+
+def _lens_desc(W, H, **kw):
+    d = _abi.bh_render_desc()
+    d.width, d.height, d.max_iters, d.scene_flags = W, H, CAP, FLAGS
+    d.math, d.layout, d.shard_count, d.schedule = bh.BH_MATH_EXACT, bh.BH_LAYOUT_ROWMAJOR, 1, bh.BH_SCHED_TILE
+    for k, v in kw.items():
+        setattr(d, k, v)
+    return d
+
+
+@pytest.mark.parametrize("what", ["math", "layout", "shard_count", "partition", "pair", "persistent", "dbg_n_rk",
+                                  "dbg_fate", "dbg_steps", "out_col", "out_blackout"])
+def test_render_lens_refuses_unsupported(torch_cuda, scene, what):
+    torch = torch_cuda
+    W, H = 40, 24
+    scene.camera_uniform, scene.uniforms = camera_uniform("E", W, H), uniforms()
+    lens = lens_buffer(torch, W, H)
+    side = torch.full((H, W, 16), SENTINEL, dtype=torch.uint8, device="cuda")
+    part = bh.Partition(W, H, [1]) if what == "partition" else None
+    try:
+        kw = {"math": dict(math=bh.BH_MATH_FAST), "layout": dict(layout=bh.BH_LAYOUT_TILES),
+              "shard_count": dict(shard_count=2, shard_index=1), "partition": dict(partition=part and part.handle),
+              "pair": dict(schedule=bh.BH_SCHED_PAIR), "persistent": dict(schedule=bh.BH_SCHED_PERSISTENT),
+              "dbg_n_rk": dict(dbg_n_rk=side.data_ptr()), "dbg_fate": dict(dbg_fate=side.data_ptr()),
+              "dbg_steps": dict(dbg_steps=side.data_ptr()), "out_col": dict(out_col=side.data_ptr()),
+              "out_blackout": dict(out_blackout=side.data_ptr())}[what]
+        d = _lens_desc(W, H, **kw)
+        st = scene.lib.bh_render_lens(scene._ctx, C.byref(scene.camera_uniform.c), C.byref(scene.uniforms.to_c()),
+                                      C.byref(d), lens.data_ptr(), torch.cuda.current_stream().cuda_stream)
+        assert st == _abi.BH_ERR_UNSUPPORTED
+        text = scene.lib.bh_last_error().decode()
+        assert text.startswith("bh_render_lens") and text.endswith(".") and " " in text
+        torch.cuda.synchronize()
+        assert untouched(lens, side)
+    finally:
+        if part is not None:
+            part.close()
+
+
+def test_render_lens_refuses_invalid_arguments(torch_cuda, scene):
+    torch = torch_cuda
+    W, H = 40, 24
+    scene.camera_uniform, scene.uniforms = camera_uniform("E", W, H), uniforms()
+    lens = lens_buffer(torch, W, H)
+    cam, U = C.byref(scene.camera_uniform.c), C.byref(scene.uniforms.to_c())
+    stream = torch.cuda.current_stream().cuda_stream
+    d = _lens_desc(W, H)
+    call = scene.lib.bh_render_lens
+    assert call(scene._ctx, cam, U, C.byref(d), None, stream) == _abi.BH_ERR_INVALID_ARG
+    assert call(scene._ctx, cam, U, C.byref(d), lens.data_ptr() + 4, stream) == _abi.BH_ERR_INVALID_ARG
+    assert call(scene._ctx, cam, U, None, lens.data_ptr(), stream) == _abi.BH_ERR_INVALID_ARG
+    assert call(None, cam, U, C.byref(d), lens.data_ptr(), stream) == _abi.BH_ERR_INVALID_ARG
+    for kw in (dict(width=0), dict(height=0), dict(width=65537), dict(max_iters=0), dict(scene_flags=4)):
+        assert call(scene._ctx, cam, U, C.byref(_lens_desc(W, H, **kw)), lens.data_ptr(), stream) == _abi.BH_ERR_INVALID_ARG, kw
+    torch.cuda.synchronize()
+    assert untouched(lens)
+
+
+def test_shade_refuses_invalid_arguments(torch_cuda, scene):
+    torch = torch_cuda
+    W, H = 40, 24
+    lens = render_lens(torch, scene, "E", W, H)
+    col, bo = target(torch, W, H, F32), target(torch, W, H, F32)
+    stream = torch.cuda.current_stream().cuda_stream
+
+    def desc(**kw):
+        d = _abi.bh_shade_desc()
+        d.width, d.height, d.ss, d.format = W, H, 1, F32
+        d.lens, d.out_col, d.out_blackout = lens.data_ptr(), col.data_ptr(), bo.data_ptr()
+        for k, v in kw.items():
+            setattr(d, k, v)
+        return d
+
+    other_scene = new_scene()
+    try:
+        foreign = bh.Sky(other_scene, sky("1x1"))
+        cases = [dict(ss=0), dict(ss=3), dict(ss=16), dict(lens=None), dict(lens=lens.data_ptr() + 4), dict(out_col=None),
+                 dict(width=0), dict(height=0), dict(width=32769, ss=2), dict(height=16385, ss=4), dict(width=65537),
+                 dict(format=3), dict(sky=foreign.handle)]
+        for kw in cases:
+            assert scene.lib.bh_shade_lens(scene._ctx, C.byref(desc(**kw)), stream) == _abi.BH_ERR_INVALID_ARG, kw
+        assert scene.lib.bh_shade_lens(scene._ctx, None, stream) == _abi.BH_ERR_INVALID_ARG
+        assert scene.lib.bh_shade_lens(None, C.byref(desc()), stream) == _abi.BH_ERR_INVALID_ARG
+        for ss in (0, 3, 16):
+            with pytest.raises(bh.BhError) as e:
+                scene.shade(lens, col, bo, ss=ss, width=W, height=H)
+            assert e.value.status == _abi.BH_ERR_INVALID_ARG
+        with pytest.raises(bh.BhError) as e:
+            scene.shade(lens, col, bo, sky=foreign, width=W, height=H)
+        assert e.value.status == _abi.BH_ERR_INVALID_ARG
+        torch.cuda.synchronize()
+        assert untouched(col, bo)
+        assert scene.lib.bh_shade_lens(scene._ctx, C.byref(desc()), stream) == _abi.BH_OK  # the desc itself is good
+        torch.cuda.synchronize()
+        assert_frame(as_bytes(col), frame("E", W, H, "ctx")[0], "col")
+    finally:
+        other_scene.close()
+
+
+def test_sky_close_after_scene_close(torch_cuda):
+    """Scene.close() closes its skies (bh_destroy would free them anyway); their own close() is then a no-op,
+    and a sky closed by hand leaves the scene's list."""
+    sc = new_scene()
+    a, b = bh.Sky(sc, sky("96x40")), bh.Sky(sc, sky("1x1"))
+    assert (a.width, a.height) == (96, 40) and sc._skies == [a, b]
+    b.close()
+    assert b.handle is None and sc._skies == [a]
+    b.close()
+    sc.close()
+    assert a.handle is None and sc._skies == []
+    a.close()
+    sc.close()
+    lib = bh.load()
+    assert lib.bh_sky_destroy(None) == _abi.BH_OK
+    assert lib.bh_sky_create(None, sky("1x1").ctypes.data, 1, 1, C.byref(C.c_void_p())) == _abi.BH_ERR_INVALID_ARG

@@ -5,7 +5,10 @@ driven by CameraController with a key script, PNG frames out.
     python tools/render_path.py --width 1024 --height 512 --frames 24 --dt 0.05 \\
         --script "W:0-12,ArrowLeft:6-24,P:12-18" --out gpurun_out/path
 Script: comma-separated KEY:first-last frame ranges (keys held down), reference key names (W A S D
-Space F ArrowUp/Down/Left/Right P O)."""
+Space F ArrowUp/Down/Left/Right P O).
+
+    python tools/render_path.py --sky-frames DIR --out frames/sky
+A moving sky behind a still camera instead: one frame per image in DIR, the view marched once into a lens map."""
 import argparse
 import json
 import sys
@@ -35,9 +38,15 @@ p.add_argument("--adaptive", type=float, default=None, metavar="T",
                help="with --ss > 1: supersample only the 8x8 tiles that show an edge above T (bh_render_adaptive)")
 p.add_argument("--sky", default=None, help="image file for the sky (e.g. the reference's space_4096x2048.jpg); "
                                             "default: the synthetic sky")
+p.add_argument("--sky-frames", default=None, metavar="DIR",
+               help="a moving sky behind a still camera: one output frame per image file in DIR (sorted by name), "
+                    "the default camera marched once into a lens map (bh_render_lens) and shaded with each image "
+                    "(bh_shade_lens); --script, --frames and --dt are not used")
 args = p.parse_args()
 if args.adaptive is not None and args.ss == 1:
     p.error("--adaptive needs --ss 2, 4 or 8")
+if args.sky_frames and args.adaptive is not None:
+    p.error("--sky-frames shades a lens map: there is no adaptive lens")
 W, H = args.width, args.height
 keys = []
 for item in filter(None, args.script.split(",")):
@@ -55,7 +64,25 @@ bo = torch.empty_like(col)
 surf = torch.empty_like(col)
 log = []
 t0 = time.perf_counter()
-for f in range(args.frames):
+if args.sky_frames:
+    images = sorted(q for q in Path(args.sky_frames).iterdir() if q.is_file())
+    if not images:
+        sys.exit(f"render_path: no image files in {args.sky_frames}")
+    k = args.ss
+    scene.update(cam)
+    lens = torch.empty((k * H, k * W, 2), dtype=torch.float32, device="cuda")
+    scene.render_lens(lens, width=k * W, height=k * H)  # the only march of the run
+    for f, path in enumerate(images):
+        frame_sky = bh.Sky(scene, bh.load_sky(path))
+        scene.shade(lens, col, bo, fmt=bh.BH_OUT_BGRA8_SRGB, sky=frame_sky, ss=k)
+        scene.bloom(col, bo, surf)
+        if not args.no_png:
+            write_png(out_dir / f"frame_{f:04d}.png", surf.cpu().numpy())
+        torch.cuda.synchronize()  # the shade has read the sky
+        frame_sky.close()
+        log.append({"frame": f, "sky": path.name, "pos": cam.pos, "dir": cam.dir, "moved": False})
+    args.frames = len(images)
+for f in range(0 if args.sky_frames else args.frames):
     for k, a, b in keys:
         ctrl.process_key(k, a <= f <= b)
     cam, moved = ctrl.update_camera(cam, args.dt)
