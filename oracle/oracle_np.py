@@ -97,11 +97,15 @@ def _sample(sky, lut, u, v):
     return out
 
 
-def get_col(ro0, rd0, U, sky, max_iters, flags):
+def get_col(ro0, rd0, U, sky, max_iters, flags, observe=None):
     """Vectorised get_col (src/black_hole_maybe.wgsl:259-345).
 
     ro0: (3,) float32 camera position; rd0: (N,3) float32 unit directions.
     U: dict with rs, delta_time_mult, blackout_eh, max_dist, distortion_power.
+    observe: optional callback, called once per loop iteration after the RK sums are formed and before
+    the state update, with the iteration's own values by keyword: alive (the rays that take this step), s,
+    ro, rd (the state going in), dt, cps (the photon-sphere helper's centre), stages (the four positions
+    rd_derivative is evaluated at) and sums (the six x/6 numerators).  It reads; it must not write.
     Returns (rgb (N,3) f32, n_rk (N,) int, fate (N,) int).
     """
     n = rd0.shape[0]
@@ -140,20 +144,29 @@ def get_col(ro0, rd0, U, sky, max_iters, flags):
         dd = np.fmin(dist * f32(0.9), dtm * r)                                      # :307-310
         dt = dd
         # get_delta_photon_rk4 (:134-151)
-        a1 = _accel(s, rox, roy, roz)
+        p1 = (rox, roy, roz)
+        a1 = _accel(s, *p1)
         rok1 = (dt * rdx, dt * rdy, dt * rdz)
         rdk1 = (dt * a1[0], dt * a1[1], dt * a1[2])
         rok2 = tuple(dt * (v + f32(0.5) * k) for v, k in zip((rdx, rdy, rdz), rdk1))
-        a2 = _accel(s, *(p + f32(0.5) * k for p, k in zip((rox, roy, roz), rok1)))
+        p2 = tuple(p + f32(0.5) * k for p, k in zip((rox, roy, roz), rok1))
+        a2 = _accel(s, *p2)
         rdk2 = tuple(dt * a for a in a2)
         rok3 = tuple(dt * (v + f32(0.5) * k) for v, k in zip((rdx, rdy, rdz), rdk2))
-        a3 = _accel(s, *(p + f32(0.5) * k for p, k in zip((rox, roy, roz), rok2)))
+        p3 = tuple(p + f32(0.5) * k for p, k in zip((rox, roy, roz), rok2))
+        a3 = _accel(s, *p3)
         rdk3 = tuple(dt * a for a in a3)
         rok4 = tuple(dt * (v + k) for v, k in zip((rdx, rdy, rdz), rdk3))
-        a4 = _accel(s, *(p + k for p, k in zip((rox, roy, roz), rok3)))
+        p4 = tuple(p + k for p, k in zip((rox, roy, roz), rok3))
+        a4 = _accel(s, *p4)
         rdk4 = tuple(dt * a for a in a4)
-        dro = [(((k1 + f32(2) * k2) + f32(2) * k3) + k4) / f32(6) for k1, k2, k3, k4 in zip(rok1, rok2, rok3, rok4)]
-        drd = [(((k1 + f32(2) * k2) + f32(2) * k3) + k4) / f32(6) for k1, k2, k3, k4 in zip(rdk1, rdk2, rdk3, rdk4)]
+        sro = [((k1 + f32(2) * k2) + f32(2) * k3) + k4 for k1, k2, k3, k4 in zip(rok1, rok2, rok3, rok4)]
+        srd = [((k1 + f32(2) * k2) + f32(2) * k3) + k4 for k1, k2, k3, k4 in zip(rdk1, rdk2, rdk3, rdk4)]
+        dro = [x / f32(6) for x in sro]
+        drd = [x / f32(6) for x in srd]
+        if observe is not None:
+            observe(alive=alive.copy(), s=s, ro=p1, rd=(rdx, rdy, rdz), dt=dt, cps=(cpx, cpy, cpz),
+                    stages=(p1, p2, p3, p4), sums=tuple(sro) + tuple(srd))
         rox = np.where(alive, rox + dro[0], rox); roy = np.where(alive, roy + dro[1], roy)
         roz = np.where(alive, roz + dro[2], roz)
         rdx = np.where(alive, rdx + drd[0], rdx); rdy = np.where(alive, rdy + drd[1], rdy)
@@ -189,10 +202,10 @@ def pixel_dirs(cam_world_tri, width, height):
     return np.stack([d[0] / ln, d[1] / ln, d[2] / ln], axis=1)
 
 
-def render(cam_pos, cam_world_tri, U, sky, width, height, max_iters, flags):
-    """Full frame: returns col (H,W,4), blackout (H,W,4), n_rk (H,W), fate (H,W)."""
+def render(cam_pos, cam_world_tri, U, sky, width, height, max_iters, flags, observe=None):
+    """Full frame: returns col (H,W,4), blackout (H,W,4), n_rk (H,W), fate (H,W).  observe: see get_col."""
     rd0 = pixel_dirs(cam_world_tri, width, height)
-    rgb, n_rk, fate = get_col(np.asarray(cam_pos, f32), rd0, U, sky, max_iters, flags)
+    rgb, n_rk, fate = get_col(np.asarray(cam_pos, f32), rd0, U, sky, max_iters, flags, observe)
     col = np.concatenate([rgb, np.ones((rgb.shape[0], 1), f32)], axis=1)
     keep = ~(_dot(rgb[:, 0], rgb[:, 1], rgb[:, 2], rgb[:, 0], rgb[:, 1], rgb[:, 2]) < f32(1))  # :366
     bo = np.where(keep[:, None], col, np.array([0, 0, 0, 1], f32))

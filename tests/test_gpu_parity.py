@@ -14,6 +14,8 @@ import pytest
 import black_hole_ray_marching_amd as bh
 import oracle
 from tests._cases import camera_uniform, uniforms
+from tests._gpu_common import SCHEDULES, assert_bitexact, gpu_render, oracle_render
+from tests._gpu_common import bgra8_expected as _bgra8_expected
 
 pytestmark = pytest.mark.gpu
 
@@ -32,36 +34,6 @@ def torch_cuda():
 @pytest.fixture(scope="module")
 def scene_small(torch_cuda, sky_small):
     return bh.Scene(16, 16, sky=sky_small)
-
-
-def gpu_render(torch, scene, cu, U, W, H, cap, flags, math, fmt=bh.BH_OUT_RGBA32F, blackout=True, schedule=0):
-    scene.camera_uniform = cu
-    scene.uniforms = U
-    scene.max_iters, scene.scene_flags = cap, flags
-    ch_dtype = torch.float32 if fmt == bh.BH_OUT_RGBA32F else torch.float16
-    col = torch.full((H, W, 4), float("nan"), dtype=ch_dtype, device="cuda")
-    bo = torch.full((H, W, 4), float("nan"), dtype=ch_dtype, device="cuda") if blackout else None
-    nrk = torch.full((H, W), 0xFFFF, dtype=torch.int32, device="cuda").to(torch.int16)
-    fate = torch.full((H, W), 0xFF, dtype=torch.uint8, device="cuda")
-    scene.render(col, bo, fmt=fmt, math=math, dbg_n_rk=nrk, dbg_fate=fate, width=W, height=H, schedule=schedule)
-    torch.cuda.synchronize()
-    return (col.cpu().numpy(), None if bo is None else bo.cpu().numpy(),
-            nrk.cpu().numpy().view(np.uint16), fate.cpu().numpy())
-
-
-def oracle_render(cu, U, sky, W, H, cap, flags, row0=0, row1=None):
-    return oracle.render_rows(cu.to_bytes(), bytes(U.to_c()), sky, W, H, cap, flags, row0, row1)
-
-
-def assert_bitexact(g, o):
-    gc, gb, gn, gf = g
-    oc, ob, on, of = o
-    assert np.array_equal(gf, of), f"fate mismatch at {np.argwhere(gf != of)[:5]}"
-    assert np.array_equal(gn, on), f"n_rk mismatch at {np.argwhere(gn != on)[:5]}"
-    bad = gc.view(np.uint32) != oc.view(np.uint32)
-    assert not bad.any(), f"col mismatch at {np.argwhere(bad)[:5]}: {gc[bad][:4]} vs {oc[bad][:4]}"
-    if gb is not None:
-        assert np.array_equal(gb.view(np.uint32), ob.view(np.uint32))
 
 
 def fast_stats(g, o):
@@ -104,12 +76,6 @@ CASES = [
     ("B", 64, 40, 512, 3, {"rs": 8.0}),
     ("A", 48, 32, 512, 3, {"rs": 9.0, "delta_time_mult": 0.7}),
 ]
-
-
-# every schedule, and both builds of the exact kernels (source order / machine-scheduled; the small
-# test frames pick the latter by default)
-SCHEDULES = [bh.BH_SCHED_PAIR, bh.BH_SCHED_TILE | bh.BH_SCHED_FLAG_ISSUE_ORDER,
-             bh.BH_SCHED_TILE | bh.BH_SCHED_FLAG_LATENCY, bh.BH_SCHED_PERSISTENT | bh.BH_SCHED_FLAG_ISSUE_ORDER]
 
 
 @pytest.mark.parametrize("schedule", SCHEDULES)
@@ -500,13 +466,6 @@ def test_cycle_fast_forward_is_exact(torch_cuda, cam):
         o = oracle_render(camera_uniform(cam, W, H), uniforms(), sky, W, H, cap, 3, int(r0), int(r0) + 1)
         assert_bitexact(tuple(x[r0:r0 + 1] for x in t[:4]), o)
     scene.close()
-
-
-def _bgra8_expected(col_f32):
-    enc = oracle.srgb_encode(col_f32[..., :3])
-    out = np.empty(col_f32.shape[:-1] + (4,), np.uint8)
-    out[..., 0], out[..., 1], out[..., 2], out[..., 3] = enc[..., 2], enc[..., 1], enc[..., 0], 255
-    return out
 
 
 @pytest.mark.parametrize("schedule", SCHEDULES)
