@@ -4,6 +4,11 @@
   oracle/libbh_oracle.so                        test infrastructure: CPU oracle (gcc, OpenMP)
 
 Run `python -m black_hole_ray_marching_amd.build` or call build_all().
+
+A variant of the product for an A/B (other flags for some units, or another revision's sources) goes to a
+directory of its own, from the same list of units and flags:
+    python -m black_hole_ray_marching_amd.build --out DIR [--extra bh_march_exact.hip="-mllvm -amdgpu-..."]... [--csrc DIR]
+writes DIR/libbh_render.so and its objects (DIR/*.o, what tools/kernel_text_cmp.py compares).
 """
 from __future__ import annotations
 
@@ -59,7 +64,12 @@ TU_FLAGS = {
     "bh_bloom.hip": ["-ffp-contract=off", "-fno-slp-vectorize", "-mllvm", "-enable-post-misched=0",
                      "-mllvm", "-pragma-unroll-threshold=200000"],  # the quad pass's 8 taps x 9 read forms
     "bh_selftest.hip": ["-ffp-contract=off", "-fhip-fp32-correctly-rounded-divide-sqrt"],
+    # the host side of the ABI: arithmetic whose bits are tested (camera, frame constants, bloom plans, mirrors)
     "bh_host.cpp": ["-ffp-contract=off", "-x", "hip"],
+    "bh_camera.cpp": ["-ffp-contract=off", "-x", "hip"],
+    "bh_bloom_host.cpp": ["-ffp-contract=off", "-x", "hip"],
+    "bh_tiles_host.cpp": ["-ffp-contract=off", "-x", "hip"],
+    "bh_mirror.cpp": ["-ffp-contract=off", "-x", "hip"],
     "bh_present.cpp": ["-x", "hip"],
 }
 
@@ -77,26 +87,34 @@ def _stale(target: Path, deps: list[Path]) -> bool:
     return any(d.stat().st_mtime > t for d in deps)
 
 
-def build_product(force: bool = False) -> Path:
-    OBJ.mkdir(exist_ok=True)
-    headers = list(CSRC.glob("*.hpp")) + [ROOT / "include" / "bh_render.h"]
+def build_product(force: bool = False, out_dir: Path | None = None, extra: dict[str, list[str]] | None = None,
+                  csrc: Path = CSRC) -> Path:
+    """The product library.  out_dir: objects and library into that directory instead of the package (a variant
+    build); extra: per unit, flags after TU_FLAGS' own; csrc: another tree's sources (with ../../include beside it)."""
+    obj_dir = Path(out_dir) if out_dir else OBJ
+    lib = obj_dir / LIB.name if out_dir else LIB
+    obj_dir.mkdir(parents=True, exist_ok=True)
+    extra = extra or {}
+    if set(extra) - set(TU_FLAGS):
+        raise ValueError(f"no such unit: {sorted(set(extra) - set(TU_FLAGS))} (units: {list(TU_FLAGS)})")
+    headers = list(csrc.glob("*.hpp")) + [csrc.parent.parent / "include" / "bh_render.h"]
     objs, jobs = [], []
     for src, flags in TU_FLAGS.items():
-        s = CSRC / src
-        o = OBJ / (s.stem + ".o")
-        deps = [s, *headers, Path(__file__)] + ([CSRC / "bh_march_exact.hip"] if src in ("bh_march_exact_lat.hip", "bh_march_refine_lat.hip") else [])
+        s = csrc / src
+        o = obj_dir / (s.stem + ".o")
+        deps = [s, *headers, Path(__file__)] + ([csrc / "bh_march_exact.hip"] if src in ("bh_march_exact_lat.hip", "bh_march_refine_lat.hip") else [])
         if force or _stale(o, deps):
-            jobs.append([HIPCC, *COMMON, *flags, "-c", str(s), "-o", str(o)])
+            jobs.append([HIPCC, *COMMON, *flags, *extra.get(src, []), "-c", str(s), "-o", str(o)])
         objs.append(o)
     # the translation units compile independently: in parallel (BH_BUILD_JOBS, default min(cpus, 8))
     n = int(os.environ.get("BH_BUILD_JOBS", "0")) or min(os.cpu_count() or 1, 8)
     with ThreadPoolExecutor(max_workers=max(1, n)) as ex:
         list(ex.map(_run, jobs))
-    if force or _stale(LIB, objs):
-        tmp = LIB.with_suffix(".so.tmp")
+    if force or _stale(lib, objs):
+        tmp = lib.with_suffix(".so.tmp")
         _run([HIPCC, "-shared", f"--offload-arch={ARCH}", "-o", str(tmp), *map(str, objs)])
-        os.replace(tmp, LIB)
-    return LIB
+        os.replace(tmp, lib)
+    return lib
 
 
 def build_oracle(force: bool = False) -> Path:
@@ -128,6 +146,22 @@ def build_all(force: bool = False) -> None:
 
 
 if __name__ == "__main__":
-    build_all(force="--force" in sys.argv)
-    print(LIB)
-    print(ORACLE_LIB)
+    import argparse
+    import shlex
+
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("--force", action="store_true", help="rebuild everything")
+    ap.add_argument("--out", type=Path, help="build only the product library, into this directory (a variant)")
+    ap.add_argument("--extra", action="append", default=[], metavar='UNIT="FLAGS"',
+                    help="with --out: more flags for one unit, after its own (may repeat)")
+    ap.add_argument("--csrc", type=Path, default=CSRC, help="with --out: the csrc directory of another tree")
+    args = ap.parse_args()
+    if args.out:
+        extra = {u: shlex.split(f) for u, _, f in (e.partition("=") for e in args.extra)}
+        print(build_product(args.force, args.out, extra, args.csrc.resolve()))
+    else:
+        if args.extra or args.csrc != CSRC:
+            ap.error("--extra and --csrc build a variant: give --out")
+        build_all(force=args.force)
+        print(LIB)
+        print(ORACLE_LIB)

@@ -5,14 +5,13 @@
 #include <stdint.h>
 
 #include <string>
-#include <vector>
 
 #include "../../include/bh_render.h"
 
 namespace bh {
 
 // Frames whose arguments travel inline in the kernel argument; a bh_render_frames call of more
-// (up to BH_MAX_FRAMES) stages them in a device table (bh_host.cpp, FrameTable).
+// (up to BH_MAX_FRAMES) stages them in a device table (bh_host.hpp, FrameTable).
 constexpr uint32_t BH_INLINE_FRAMES = 32;
 static_assert(BH_INLINE_FRAMES <= BH_MAX_FRAMES, "inline frames");
 
@@ -266,159 +265,11 @@ __device__ __forceinline__ uint32_t wave_max_u32(uint32_t v) {
 }
 }  // namespace bh
 
-// Launchers (defined in the .hip translation units).
-extern "C" __attribute__((visibility("hidden"))) int bh_launch_march_exact(const bh::MarchArgs& a, uint32_t schedule,
-                                                                         uint32_t* counters, uint32_t grid,
-                                                                         hipStream_t s);
-extern "C" __attribute__((visibility("hidden"))) int bh_launch_march_exact_lat(const bh::MarchArgs& a, uint32_t schedule,
-                                                                             uint32_t* counters, uint32_t grid,
-                                                                             hipStream_t s);
-extern "C" __attribute__((visibility("hidden"))) int bh_launch_march_fast(const bh::MarchArgs& a, uint32_t schedule,
-                                                                        uint32_t* counters, uint32_t grid,
-                                                                        hipStream_t s);
-// the adaptive render's work-list march (a.ss_log2 in 1..3, `waves` pulling waves) and its detect kernel
-extern "C" __attribute__((visibility("hidden"))) int bh_launch_refine_exact(const bh::MarchArgs& a, const bh::RefineArgs& r,
-                                                                          uint32_t waves, hipStream_t s);
-extern "C" __attribute__((visibility("hidden"))) int bh_launch_refine_exact_lat(const bh::MarchArgs& a,
-                                                                              const bh::RefineArgs& r, uint32_t waves,
-                                                                              hipStream_t s);
-extern "C" __attribute__((visibility("hidden"))) int bh_launch_refine_fast(const bh::MarchArgs& a, const bh::RefineArgs& r,
-                                                                         uint32_t waves, hipStream_t s);
-extern "C" __attribute__((visibility("hidden"))) int bh_launch_refine_detect(const bh::MarchArgs& a, const bh::RefineArgs& r,
-                                                                           hipStream_t s);
-// the lens shade (bh_lens.hip): ss in {1, 2, 4, 8}, format a bh_out_format
-extern "C" __attribute__((visibility("hidden"))) int bh_launch_lens_shade(const bh::LensShadeArgs& a, uint32_t ss,
-                                                                        uint32_t format, hipStream_t s);
-extern "C" __attribute__((visibility("hidden"))) int bh_march_blocks_per_cu_exact(void);
-extern "C" __attribute__((visibility("hidden"))) int bh_march_blocks_per_cu_fast(void);
-extern "C" __attribute__((visibility("hidden"))) int bh_launch_build_order(const uint8_t* cost, uint32_t n_tiles,
-                                                                         uint32_t block, uint32_t centre,
-                                                                         uint32_t* counters, uint32_t* order,
-                                                                         hipStream_t s);
-extern "C" __attribute__((visibility("hidden"))) int bh_launch_tiles_unpack_rgbm(const void* packed, void* out, void* out_bo,
-                                                                               uint32_t width, uint32_t height,
-                                                                               uint32_t shard_count, uint64_t stride_tiles,
-                                                                               const uint32_t* tile_loc,
-                                                                               uint32_t format, uint32_t rows_in_flight,
-                                                                               hipStream_t s);
-extern "C" __attribute__((visibility("hidden"))) int bh_launch_tiles_unpack_rgb(const void* packed, void* out, uint32_t width,
-                                                                              uint32_t height, uint32_t shard_count,
-                                                                              uint64_t stride_tiles, uint32_t format, uint32_t rows_in_flight,
-                                                                              hipStream_t s);
-// base codes of the table form of the sRGB encoder (bh_srgb.hpp), built from its 257 thresholds
-extern "C" __attribute__((visibility("hidden"))) void bh_srgb_bucket_table(const float* T257, uint8_t* B);
-extern "C" __attribute__((visibility("hidden"))) bool bh_srgb_code_table(const float* T257, uint32_t* E);
 // bh_bloom.hip pass shaders (bh::bloom::Shader)
 constexpr uint32_t bh_bloom_shader_copy = 0, bh_bloom_shader_down = 1, bh_bloom_shader_up = 2, bh_bloom_shader_remix = 3;
-// the separable plan of an 8-tap pass (bh_bloom.hip): 8 * (ow + oh) entries of 4 words; returns the largest
-// block footprint side (or -1)
-extern "C" __attribute__((visibility("hidden"))) int bh_bloom_sep_plan(uint32_t ow, uint32_t oh, uint32_t tw,
-                                                                     uint32_t th, uint32_t rx, uint32_t ry,
-                                                                     uint32_t* outp, uint32_t org);
-// an up pass from its separable plan with an epilogue (bh_bloom.hip SepEpi: 0 plain, 1 Y, 2 final)
-extern "C" __attribute__((visibility("hidden"))) int bh_launch_bloom_sep(const float* lut, const float* enc,
-                                                                        const uint8_t* buckets, const uint32_t* codes,
-                                                                        const uint32_t* a, uint32_t aw, uint32_t ah,
-                                                                        uint32_t rx, uint32_t ry,
-                                                                        const uint32_t* sep, int ext, uint32_t epi,
-                                                                        const uint32_t* own0, const uint32_t* own1,
-                                                                        const uint32_t* same, uint32_t* out, uint32_t* aux,
-                                                                        uint32_t ow, uint32_t oh, uint32_t org, bool fix,
-                                                                        const uint32_t* stc, uint32_t* strips,
-                                                                        uint32_t strip_w, bool* strips_written,
-                                                                        hipStream_t s);
-// the fix-up pass of a fused epilogue; stc / strips: the final epilogue's column strips (the up pass wrote them)
-extern "C" __attribute__((visibility("hidden"))) int bh_launch_bloom_fixup(const float* lut, const float* enc,
-                                                                          const uint8_t* buckets, const uint32_t* codes,
-                                                                          uint32_t epi, const uint32_t* a, const uint32_t* b,
-                                                                          const uint32_t* c, const uint32_t* same,
-                                                                          const uint32_t* list, uint32_t n_cols,
-                                                                          uint32_t n_rows, uint32_t* out, uint32_t w,
-                                                                          uint32_t h, int32_t residual_org, const uint32_t* recs,
-                                                                          const uint32_t* stc, const uint32_t* strips,
-                                                                          uint32_t strip_w, hipStream_t s);
-// the column strips' table of a same-size plan's inexact columns; returns the number of strip columns
-extern "C" __attribute__((visibility("hidden"))) uint32_t bh_bloom_strip_table(uint32_t w, const uint32_t* list, uint32_t nc,
-                                                                         uint32_t* stc);
-// the fix-up kernel's records of a list (8 words per entry: the index and the plan entries of it and its neighbours)
-extern "C" __attribute__((visibility("hidden"))) void bh_bloom_fixup_records(uint32_t w, uint32_t h, const uint32_t* plan,
-                                                                           const uint32_t* list, uint32_t nc, uint32_t nr,
-                                                                           uint32_t* out);
-// two downsamples a -> mw x mh -> out in one pass (the intermediate level not stored)
-extern "C" __attribute__((visibility("hidden"))) int bh_launch_bloom_down2(const float* lut, const float* enc,
-                                                                          const uint8_t* buckets, const uint32_t* codes,
-                                                                          const uint32_t* a, uint32_t aw, uint32_t ah,
-                                                                          uint32_t mw, uint32_t mh, uint32_t* out,
-                                                                          uint32_t ow, uint32_t oh, hipStream_t s);
-// the same-size plan of a w x h frame (bh_bloom.hip): (w + h) uint2 entries; the plan remixes
-extern "C" __attribute__((visibility("hidden"))) bool bh_bloom_same_plan(uint32_t w, uint32_t h, uint32_t* outp);
-extern "C" __attribute__((visibility("hidden"))) int bh_launch_bloom_remix_plan(const float* lut, const float* enc,
-                                                                               const uint8_t* buckets,
-                                                                               const uint32_t* codes, const uint32_t* a,
-                                                                               const uint32_t* b, const uint32_t* plan,
-                                                                               uint32_t* out, uint32_t w, uint32_t h,
-                                                                               hipStream_t s);
-extern "C" __attribute__((visibility("hidden"))) int bh_launch_bloom_same_copy(const float* lut, const float* enc,
-                                                                              const uint8_t* buckets,
-                                                                              const uint32_t* codes, const uint32_t* src,
-                                                                              const uint32_t* plan, uint32_t* out,
-                                                                              uint32_t w, uint32_t h, hipStream_t s);
-extern "C" __attribute__((visibility("hidden"))) int bh_launch_bloom_remix2_plan(const float* lut, const float* enc,
-                                                                                const uint8_t* buckets,
-                                                                                const uint32_t* codes,
-                                                                                const uint32_t* col, const uint32_t* Y,
-                                                                                const uint32_t* Bt, const uint32_t* plan,
-                                                                                uint32_t* out, uint32_t w, uint32_t h,
-                                                                                hipStream_t s);
-// host-side bound checks of the bloom kernels' index arithmetic (bh_bloom.hip): a separable plan for the form
-// bh_launch_bloom_sep takes, a same-size plan with its fix-up list; false with the first violation in *why.
-// Dry mode (bh_bloom_check): between begin and end the bloom launchers check their launch instead of launching.
-extern "C" __attribute__((visibility("hidden"))) bool bh_bloom_sep_verify(uint32_t ow, uint32_t oh, uint32_t tw,
-                                                                        uint32_t th, uint32_t rx, uint32_t ry,
-                                                                        const uint32_t* plan, int ext, uint32_t org, bool fix,
-                                                                        std::string* why);
-extern "C" __attribute__((visibility("hidden"))) bool bh_bloom_sep_fix_ok(int ext, uint32_t ow, uint32_t oh, uint32_t epi);
-// the quad grid origin of the in-block fix for a same-size plan, and its residual (crossing) columns / rows
-extern "C" __attribute__((visibility("hidden"))) uint32_t bh_bloom_same_org(uint32_t w, uint32_t h, const uint32_t* plan,
-                                                                          std::vector<uint32_t>* cols,
-                                                                          std::vector<uint32_t>* rows,
-                                                                          std::vector<uint32_t>* cols2,
-                                                                          std::vector<uint32_t>* rows2);
-extern "C" __attribute__((visibility("hidden"))) bool bh_bloom_same_verify(uint32_t w, uint32_t h, const uint32_t* plan,
-                                                                         uint32_t nc, uint32_t nr, std::string* why);
-// bh_host.cpp for the other host translation units: the thread's last error, an argument failure, a ctx's device
+
+// bh_host.cpp for the host translation units that see only the public ABI (bh_present.cpp): the thread's last
+// error, an argument failure, a ctx's device.  Every other host-only declaration lives in bh_host.hpp.
 extern "C" __attribute__((visibility("hidden"))) void bh_set_last_error(const std::string& msg);
 extern "C" __attribute__((visibility("hidden"))) int bh_bad_arg(const char* fn, int line);
 extern "C" __attribute__((visibility("hidden"))) int bh_ctx_device(const bh_ctx* c);
-extern "C" __attribute__((visibility("hidden"))) bool bh_bloom_records_verify(uint32_t w, uint32_t h, const uint32_t* plan,
-                                                                            const uint32_t* list, uint32_t nc, uint32_t nr,
-                                                                            const uint32_t* rec, const uint32_t* stc,
-                                                                            uint32_t strip_w, std::string* why);
-extern "C" __attribute__((visibility("hidden"))) void bh_bloom_dry_begin(void);
-extern "C" __attribute__((visibility("hidden"))) bool bh_bloom_dry_end(uint64_t* launches, uint64_t* checks,
-                                                                     std::string* fail, std::string* plan);
-extern "C" __attribute__((visibility("hidden"))) bool bh_bloom_dry(void);
-// whether bh_launch_bloom_pass runs an up pass of this shape from its separable plan (bh_bloom.hip)
-extern "C" __attribute__((visibility("hidden"))) bool bh_bloom_up_uses_sep(uint32_t ow, uint32_t oh, uint32_t aw,
-                                                                         uint32_t ah, uint32_t rx, uint32_t ry);
-extern "C" __attribute__((visibility("hidden"))) int bh_launch_bloom_pass(uint32_t shader, const float* lut,
-                                                                         const float* enc, const uint8_t* buckets,
-                                                                         const uint32_t* codes, const uint32_t* a,
-                                                                         uint32_t aw, uint32_t ah, const uint32_t* b,
-                                                                         uint32_t rx, uint32_t ry, uint32_t* out,
-                                                                         uint32_t ow, uint32_t oh, const uint32_t* sep, int sep_ext,
-                                                                         hipStream_t s);
-extern "C" __attribute__((visibility("hidden"))) int bh_launch_bloom_y(const float* lut, const float* enc,
-                                                                      const uint8_t* buckets, const uint32_t* codes,
-                                                                      const uint32_t* X, uint32_t* Y, uint32_t w,
-                                                                      uint32_t h, uint32_t* d2out, bool* d2_done,
-                                                                      hipStream_t s);
-extern "C" __attribute__((visibility("hidden"))) int bh_launch_bloom_final(const float* lut, const float* enc,
-                                                                          const uint8_t* buckets, const uint32_t* codes,
-                                                                          const uint32_t* col, const uint32_t* Y,
-                                                                          const uint32_t* U0, uint32_t rx, uint32_t ry,
-                                                                          uint32_t* out, uint32_t w, uint32_t h,
-                                                                          hipStream_t s);
-extern "C" __attribute__((visibility("hidden"))) int bh_launch_tiles_unpack(const void* packed, void* out, uint32_t width, uint32_t height,
-                                      uint32_t shard_count, uint64_t shard_stride_tiles,
-                                      uint32_t bytes_per_pixel, hipStream_t s);

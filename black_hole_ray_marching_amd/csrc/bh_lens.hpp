@@ -1,5 +1,5 @@
 // bh_lens.hpp — shading a lens map (include/bh_render.h, bh_lens_px): host and device share every function
-// here.  The shade kernel (bh_lens.hip) runs them per output pixel, bh_lens_shade_host (bh_host.cpp) runs the
+// here.  The shade kernel (bh_lens.hip) runs them per output pixel, bh_lens_shade_host (bh_mirror.cpp) runs the
 // very same functions in a loop on the CPU.  Both translation units are built without contraction, the device
 // one with correctly rounded fp32 sqrt, so every op here rounds once, as the same op of the march kernel's
 // shading does (bh_march.hpp: sample_sky, pow15_x, write_pixel's blackout test, ss_resolve's tree).

@@ -2041,5 +2041,68 @@ inline void launch_refine_schedule(const MarchArgs& a, const RefineArgs& r, uint
     hipLaunchKernelGGL((march_refine_kernel<FMT, SF>), dim3(blocks), dim3(64u * WG_WAVES), 0, s, a, r);
 }
 
+// ---- one launcher for every build of these kernels (bh_march_exact.hip, bh_march_fast.hip) -----------------
+// A launcher is a template, so a unit holds the kernels of the launchers it calls and no others; hidden, like
+// the entry points that call them.
+// f(SF) with the launch's scene flags as a compile-time constant where the build folds them: the reference's
+// scene always; no surfaces (BASELINE config 1: the sdf folds to +inf) with FOLD_NONE, which the exact builds
+// set and the fast build does not; otherwise SF_DYN, the kernels that read the flags.
+template <uint32_t V>
+struct Const { static constexpr uint32_t value = V; };
+template <bool FOLD_NONE, class F>
+__attribute__((visibility("hidden"))) inline void with_scene_fold(uint32_t flags, F&& f) {
+    if (flags == BH_SCENE_DEFAULT) return f(Const<BH_SCENE_DEFAULT>{});
+    if constexpr (FOLD_NONE)
+        if (flags == 0u) return f(Const<0u>{});
+    f(Const<SF_DYN>{});
+}
+// f(FMT) with the launch's output format as a compile-time constant
+template <class F>
+__attribute__((visibility("hidden"))) inline int with_format(uint32_t format, F&& f) {
+    switch (format) {
+        case BH_OUT_RGBA32F: return f(Const<BH_OUT_RGBA32F>{});
+        case BH_OUT_RGBA16F: return f(Const<BH_OUT_RGBA16F>{});
+        default: return f(Const<BH_OUT_BGRA8_SRGB>{});
+    }
+}
+// The march over every tile under `schedule` (a bh_schedule without its flags); counters, grid: the persistent
+// schedule's.  Returns a hipError_t.
+template <bool FOLD_NONE>
+__attribute__((visibility("hidden"))) inline int launch_march(const MarchArgs& a, uint32_t schedule, uint32_t* counters, uint32_t grid, hipStream_t s) {
+#if !BH_FAST
+    if (a.lens != 0u) {  // bh_render_lens (tile schedule): one kernel per scene-flag fold, whatever the format word says
+        if (schedule != BH_SCHED_TILE) return (int)hipErrorInvalidValue;
+        with_scene_fold<FOLD_NONE>(a.scene_flags, [&](auto sf) { launch_tile_lens_schedule<decltype(sf)::value>(a, s); });
+        return (int)hipGetLastError();
+    }
+#endif
+    return with_format(a.format, [&](auto fmt) {
+        constexpr uint32_t FMT = decltype(fmt)::value;
+        if (schedule == BH_SCHED_TILE && a.ss_log2 != 0u) {  // bh_render_ss, ss > 1: the same folds
+            with_scene_fold<FOLD_NONE>(a.scene_flags, [&](auto sf) { launch_tile_ss_schedule<FMT, decltype(sf)::value>(a, s); });
+        } else if (schedule == BH_SCHED_TILE) {
+            with_scene_fold<FOLD_NONE>(a.scene_flags, [&](auto sf) { launch_tile_schedule<FMT, decltype(sf)::value>(a, s); });
+        } else if (schedule == BH_SCHED_PAIR) {
+            const uint32_t pairs = (a.n_tiles + 1u) / 2u;
+            hipLaunchKernelGGL(march_pair_kernel<FMT>, dim3((pairs + 3u) / 4u), dim3(256), 0, s, a);
+        } else {
+            hipError_t e = hipMemsetAsync(counters, 0, NQ * CTR_STRIDE * sizeof(uint32_t), s);
+            if (e != hipSuccess) return (int)e;
+            hipLaunchKernelGGL(march_persistent_kernel<FMT>, dim3(grid), dim3(256), 0, s, a, counters);
+        }
+        return (int)hipGetLastError();
+    });
+}
+// The adaptive render's work-list march (bh_render_adaptive): the supersampled kernels' folds.
+template <bool FOLD_NONE>
+__attribute__((visibility("hidden"))) inline int launch_refine(const MarchArgs& a, const RefineArgs& r, uint32_t waves, hipStream_t s) {
+    return with_format(a.format, [&](auto fmt) {
+        with_scene_fold<FOLD_NONE>(a.scene_flags, [&](auto sf) {
+            launch_refine_schedule<decltype(fmt)::value, decltype(sf)::value>(a, r, waves, s);
+        });
+        return (int)hipGetLastError();
+    });
+}
+
 }  // namespace BH_NS
 }  // namespace bh

@@ -1,0 +1,150 @@
+// bh_mirror.cpp — CPU mirrors of device code, the references of the tests: each runs the very functions its
+// kernel runs per lane (bh_ss.hpp, bh_lens.hpp, bh_refine.hpp) in loops over the frame.  Nothing here renders.
+#include <cmath>
+#include <cstring>
+#include <new>
+
+#include "bh_host.hpp"
+#include "bh_lens.hpp"
+#include "bh_refine.hpp"
+#include "bh_ss.hpp"
+
+extern "C" {
+
+// The supersampled march kernel's epilogue on the host: the functions of bh_ss.hpp that each lane of a wave
+// runs (ss_resolve_store, bh_march.hpp), run here wave by wave over 64-entry arrays -- one 8x8 tile of the
+// virtual frame per wave, invalid lanes 0, every lane taking each butterfly level together.
+int bh_ss_resolve_host(const float* samples, uint32_t width, uint32_t height, uint32_t ss, float* out) {
+    const uint32_t lk = bh::ss::log2_k(ss);
+    if (!samples || !out || lk > 3u) return bad_arg(__func__, __LINE__);
+    if (!frame_shape_ok(width, height, ss)) return bad_arg(__func__, __LINE__);
+    const uint32_t vw = width * ss, vh = height * ss;
+    const uint32_t tiles_x = (vw + 7u) / 8u, tiles_y = (vh + 7u) / 8u;
+    for (uint32_t ty = 0; ty < tiles_y; ++ty)
+        for (uint32_t tx = 0; tx < tiles_x; ++tx) {
+            float v[3][64], nv[64];
+            bool valid[64];
+            for (uint32_t lane = 0; lane < 64u; ++lane) {
+                const uint32_t px = tx * 8u + (lane & 7u), py = ty * 8u + (lane >> 3);
+                valid[lane] = px < vw && py < vh;
+                for (int ch = 0; ch < 3; ++ch)
+                    v[ch][lane] = valid[lane] ? samples[((size_t)py * vw + px) * 4u + (size_t)ch] : 0.0f;
+            }
+            for (int ch = 0; ch < 3; ++ch) {
+                float* cur = v[ch];
+                for (uint32_t i = 0; i < bh::ss::levels(lk); ++i) {
+                    const uint32_t mask = bh::ss::level_mask(i, lk);
+                    for (uint32_t lane = 0; lane < 64u; ++lane)
+                        nv[lane] = bh::ss::level_add(cur[lane], mask, [&](uint32_t m) { return cur[lane ^ m]; });
+                    std::memcpy(cur, nv, sizeof nv);
+                }
+            }
+            for (uint32_t lane = 0; lane < 64u; ++lane) {
+                if (!(valid[lane] && bh::ss::writer(lane, lk))) continue;
+                const uint32_t px = tx * 8u + (lane & 7u), py = ty * 8u + (lane >> 3);
+                float* o = out + (size_t)bh::ss::out_index(px, py, lk, width) * 4u;
+                for (int ch = 0; ch < 3; ++ch) o[ch] = v[ch][lane] * bh::ss::scale(lk);
+                o[3] = 1.0f;
+            }
+        }
+    return BH_OK;
+}
+
+// The shade kernel's per-pixel function (bh_lens.hpp, shade_pixel) in a loop over the output frame.
+extern "C++" template <int K>
+static void lens_shade_rows(const bh_lens_px* lens, uint32_t width, uint32_t height, const bh::lens::SkyView& s,
+                            const float* lut, float* out_col, float* out_bo) {
+    for (uint32_t y = 0; y < height; ++y)
+        for (uint32_t x = 0; x < width; ++x) {
+            const bh::lens::Acc p = out_bo ? bh::lens::shade_pixel<K, true>(lens, width, x, y, s, lut)
+                                           : bh::lens::shade_pixel<K, false>(lens, width, x, y, s, lut);
+            const bh::lens::Rgb col = p.col, bo = p.bo;
+            const size_t o = ((size_t)y * width + x) * 4u;
+            out_col[o] = col.r; out_col[o + 1] = col.g; out_col[o + 2] = col.b; out_col[o + 3] = 1.0f;
+            if (out_bo) { out_bo[o] = bo.r; out_bo[o + 1] = bo.g; out_bo[o + 2] = bo.b; out_bo[o + 3] = 1.0f; }
+        }
+}
+
+int bh_lens_shade_host(const bh_lens_px* lens, uint32_t width, uint32_t height, uint32_t ss, const uint8_t* sky,
+                       uint32_t sky_w, uint32_t sky_h, float* out_col, float* out_bo) {
+    if (!lens || !sky || !out_col || bh::ss::log2_k(ss) > 3u || !frame_shape_ok(width, height, ss)) return bad_arg(__func__, __LINE__);
+    if (sky_w == 0 || sky_h == 0 || sky_w > 32768u || sky_h > 32768u) return bad_arg(__func__, __LINE__);
+    float lut[256];
+    srgb_lut(lut);
+    std::vector<uint32_t> texels;  // the packed little-endian words the device reads (the bytes may be unaligned)
+    try {
+        texels.resize((size_t)sky_w * sky_h);
+    } catch (const std::bad_alloc&) {
+        return BH_ERR_OUT_OF_MEMORY;
+    }
+    std::memcpy(texels.data(), sky, texels.size() * 4u);
+    const bh::lens::SkyView s{texels.data(), sky_w, sky_h};
+    switch (ss) {
+        case 1u: lens_shade_rows<1>(lens, width, height, s, lut, out_col, out_bo); break;
+        case 2u: lens_shade_rows<2>(lens, width, height, s, lut, out_col, out_bo); break;
+        case 4u: lens_shade_rows<4>(lens, width, height, s, lut, out_col, out_bo); break;
+        default: lens_shade_rows<8>(lens, width, height, s, lut, out_col, out_bo); break;
+    }
+    return BH_OK;
+}
+
+// The detect kernel's decision on the host: bh_refine.hpp's lane function, tile by tile and lane by lane.
+int bh_refine_mask_host(const void* col, const void* blackout, uint32_t width, uint32_t height, uint32_t format,
+                        float threshold, uint8_t* tile_mask) {
+    if (!col || !tile_mask || width == 0 || height == 0 || width > 32768u || height > 32768u) return bad_arg(__func__, __LINE__);
+    if (format > BH_OUT_BGRA8_SRGB || !(threshold >= 0.0f) || std::isinf(threshold)) return bad_arg(__func__, __LINE__);
+    const uint32_t tiles_x = bh::refine::tiles_of(width), tiles_y = bh::refine::tiles_of(height);
+    const float thr = bh::refine::threshold(format, threshold);
+    for (uint32_t ty = 0; ty < tiles_y; ++ty)
+        for (uint32_t tx = 0; tx < tiles_x; ++tx) {
+            bool any = false;  // the wave's ballot
+            for (uint32_t lane = 0; lane < 64u; ++lane)
+                any |= bh::refine::lane_edge(format, col, blackout, width, height, tx, ty, lane, thr);
+            tile_mask[(size_t)ty * tiles_x + tx] = any ? 1u : 0u;
+        }
+    return BH_OK;
+}
+
+// The work-list march's stores on the host: the list a detect pass would leave for this mask (both ends used),
+// every work item mapped by bh_refine.hpp's item functions, every lane of its wave through bh_ss.hpp's writer
+// and output index.  An index outside the frame is counted nowhere and fails the call.
+int bh_refine_cover_host(uint32_t width, uint32_t height, uint32_t ss, const uint8_t* tile_mask, uint8_t* pixel_writes) {
+    const uint32_t lk = bh::ss::log2_k(ss);
+    if (!tile_mask || !pixel_writes || lk < 1u || lk > 3u) return bad_arg(__func__, __LINE__);
+    if (!frame_shape_ok(width, height, ss)) return bad_arg(__func__, __LINE__);
+    const uint32_t tiles_x = bh::refine::tiles_of(width), tiles_y = bh::refine::tiles_of(height);
+    const uint32_t vw = width * ss, vh = height * ss;
+    const uint32_t vtiles_x = bh::refine::tiles_of(vw), vtiles_y = bh::refine::tiles_of(vh);
+    const size_t n_px = (size_t)width * height;
+    std::memset(pixel_writes, 0, n_px);
+    // filled from both ends as the detect kernel fills it (every third refined tile to the front)
+    const uint32_t capacity = tiles_x * tiles_y;
+    std::vector<uint32_t> list(capacity, 0xFFFFFFFFu);
+    uint32_t n_front = 0, n_back = 0;
+    for (uint32_t t = 0, n = 0; t < capacity; ++t)
+        if (tile_mask[t]) list[n++ % 3u == 0u ? n_front++ : capacity - 1u - n_back++] = t;
+    if (((uint64_t)(n_front + n_back) << (2u * lk)) > 0xFFFF0000ull) return bad_arg(__func__, __LINE__);
+    const uint32_t total = (n_front + n_back) << (2u * lk);
+    bool outside = false;
+    for (uint32_t item = 0; item < total; ++item) {
+        uint32_t vtx, vty;
+        const uint32_t slot = bh::refine::entry_slot(bh::refine::item_entry(item, lk), n_front, capacity);
+        if (!bh::refine::item_tile(list[slot], bh::refine::item_sub(item, lk), lk, tiles_x,
+                                   tiles_y, vtiles_x, vtiles_y, &vtx, &vty))
+            continue;
+        for (uint32_t lane = 0; lane < 64u; ++lane) {
+            const uint32_t px = bh::refine::lane_x(vtx, lane), py = bh::refine::lane_y(vty, lane);
+            if (!(px < vw && py < vh && bh::ss::writer(lane, lk))) continue;
+            const size_t idx = bh::ss::out_index(px, py, lk, width);
+            if (idx >= n_px) { outside = true; continue; }
+            if (pixel_writes[idx] != 255u) ++pixel_writes[idx];
+        }
+    }
+    if (outside) {
+        bh_set_last_error("bh_refine_cover_host: a store index outside the frame");
+        return BH_ERR_INTERNAL;
+    }
+    return BH_OK;
+}
+
+}  // extern "C"

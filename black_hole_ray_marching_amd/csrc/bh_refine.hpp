@@ -2,7 +2,7 @@
 // tiles of a plain frame show an edge, and which tiles of the virtual frame (bh_ss.hpp) re-march them.
 // Host and device share every function here: the detect kernel (bh_tiles.hip) and the work-list march
 // (bh_march.hpp, march_refine_kernel) run them per lane / per wave, bh_refine_mask_host and
-// bh_refine_cover_host (bh_host.cpp) run the very same functions lane by lane.
+// bh_refine_cover_host (bh_mirror.cpp) run the very same functions lane by lane.
 //
 // The rule (normative, include/bh_render.h): a pixel is an edge pixel when it differs from one of its
 // 4-neighbours inside the frame (x +- 1 or y +- 1; a row's end has no neighbour in the next row) in one of

@@ -65,3 +65,7 @@ __device__ __forceinline__ uint32_t srgb_bgra8(float r, float g, float b, const 
 }
 
 }  // namespace bh
+
+// The host's builders of B and E from the 257 thresholds (bh_host.cpp; the self-test builds its own copies)
+extern "C" __attribute__((visibility("hidden"))) void bh_srgb_bucket_table(const float* T257, uint8_t* B);
+extern "C" __attribute__((visibility("hidden"))) bool bh_srgb_code_table(const float* T257, uint32_t* E);

@@ -38,7 +38,7 @@ def shard_tile_count(width: int, height: int, k: int, S: int) -> int:
 
 def partition_owners(weights) -> list[int]:
     """Owner of each residue v of (tx + 3*ty) mod M, M = sum(weights), for a weighted partition
-    (bh_host.cpp partition_owners: smooth weighted round robin)."""
+    (bh_tiles_host.cpp partition_owners: smooth weighted round robin)."""
     M = sum(int(w) for w in weights)
     if M <= 0 or M > 4096:
         raise ValueError("weights must sum to 1..4096")

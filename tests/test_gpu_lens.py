@@ -326,6 +326,34 @@ def test_shade_refuses_invalid_arguments(torch_cuda, scene):
         other_scene.close()
 
 
+def test_every_render_refuses_a_frame_shape_outside_the_index_range(torch_cuda, scene):
+    """The one shape check of the render entry points (frame_shape_ok, csrc/bh_host.hpp): a side 0, or ss * side
+    one past 65536, is BH_ERR_INVALID_ARG from bh_render_frames_ss, bh_render_frames_adaptive and bh_shade_lens for
+    every ss, and from bh_render_lens (no ss).  Only the status: nothing is launched, the 8x8 targets keep their bytes."""
+    torch = torch_cuda
+    scene.camera_uniform, scene.uniforms = camera_uniform("E", 8, 8), uniforms()
+    cam, U = C.byref(scene.camera_uniform.c), C.byref(scene.uniforms.to_c())
+    stream = torch.cuda.current_stream().cuda_stream
+    col, bo, lens = target(torch, 8, 8, F32), target(torch, 8, 8, F32), lens_buffer(torch, 8, 8)
+    lib, ctx, bad = scene.lib, scene._ctx, _abi.BH_ERR_INVALID_ARG
+    for ss in (2, 4, 8):
+        for W, H in ((65536 // ss + 1, 1), (1, 65536 // ss + 1), (0, 1), (1, 0)):
+            case = (W, H, ss)
+            d = _lens_desc(W, H, format=F32, out_col=col.data_ptr(), out_blackout=bo.data_ptr())
+            assert lib.bh_render_frames_ss(ctx, 1, cam, U, C.byref(d), ss, stream) == bad, case
+            ad = _abi.bh_adaptive_desc()
+            ad.ss, ad.threshold = ss, 0.05
+            assert lib.bh_render_frames_adaptive(ctx, 1, cam, U, C.byref(d), C.byref(ad), stream) == bad, case
+            sd = _abi.bh_shade_desc()
+            sd.width, sd.height, sd.ss, sd.format = W, H, ss, F32
+            sd.lens, sd.out_col, sd.out_blackout = lens.data_ptr(), col.data_ptr(), bo.data_ptr()
+            assert lib.bh_shade_lens(ctx, C.byref(sd), stream) == bad, case
+    for W, H in ((65537, 1), (1, 65537), (0, 1), (1, 0)):
+        assert lib.bh_render_lens(ctx, cam, U, C.byref(_lens_desc(W, H)), lens.data_ptr(), stream) == bad, (W, H)
+    torch.cuda.synchronize()
+    assert untouched(col, bo, lens)
+
+
 def test_sky_close_after_scene_close(torch_cuda):
     """Scene.close() closes its skies (bh_destroy would free them anyway); their own close() is then a no-op,
     and a sky closed by hand leaves the scene's list."""

@@ -376,7 +376,7 @@ def test_temporal_order_is_a_permutation_across_blocks(torch_cuda, sky_small, W,
 
 def test_repeated_frames_skip_the_order_build_and_stay_exact(torch_cuda, sky_small):
     """A launch whose frame repeats the one the dispatch order was learned from runs no order build and
-    writes no costs (bh_host.cpp, OrderState::order_key); every path keeps the counters holding the
+    writes no costs (bh_host.cpp learned_order, OrderState::order_key); every path keeps the counters holding the
     histogram of the stored costs, also in graphs captured either way (a march alone, or build + writing
     march) and replayed between eager renders of other cameras.  Every frame covers every tile once
     (NaN-filled targets, a partial last order block) and equals the static order's bytes."""

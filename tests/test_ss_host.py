@@ -79,3 +79,28 @@ def test_resolve_host_ss1_is_a_copy_with_alpha_one():
     got = bh.ss_resolve_host(a, 1)
     assert_same_bits(got[..., :3], a[..., :3])
     assert (got[..., 3] == 1.0).all()
+
+
+def _shape_cases():
+    """(width, height, ss) just outside the frames the kernels index: a side 0, or ss * side one past 65536"""
+    for ss in (2, 4, 8):
+        yield 65536 // ss + 1, 1, ss
+        yield 1, 65536 // ss + 1, ss
+        yield 0, 1, ss
+        yield 1, 0, ss
+
+
+def test_host_mirrors_refuse_a_bad_frame_shape_before_reading():
+    """bh_ss_resolve_host, bh_lens_shade_host and bh_refine_cover_host share one shape check (frame_shape_ok,
+    csrc/bh_host.hpp), made before anything is read: the buffers here hold one element each."""
+    lib = bh.load()
+    one = np.zeros(4, np.float32)   # one sample, one lens record and more, one pixel
+    byte = np.zeros(1, np.uint8)
+    sky = np.zeros(4, np.uint8)
+    for W, H, ss in _shape_cases():
+        case = (W, H, ss)
+        assert lib.bh_ss_resolve_host(one.ctypes.data, W, H, ss, one.ctypes.data) == _abi.BH_ERR_INVALID_ARG, case
+        assert lib.bh_lens_shade_host(one.ctypes.data, W, H, ss, sky.ctypes.data, 1, 1, one.ctypes.data,
+                                      None) == _abi.BH_ERR_INVALID_ARG, case
+        assert lib.bh_refine_cover_host(W, H, ss, byte.ctypes.data, byte.ctypes.data) == _abi.BH_ERR_INVALID_ARG, case
+    assert not one.any() and not byte.any()

@@ -1,11 +1,14 @@
-"""Where a march wave's lifetime goes (diagnostic; needs a library built with -DBH_DIAG_PHASES=1, e.g.
-`tools/build_variant.sh phases -DBH_DIAG_PHASES=1`, run with BH_LIB=tools/variants/phases.so).
+"""Where a march wave's lifetime goes (diagnostic; needs a library whose exact march units were built with
+-DBH_DIAG_PHASES=1, e.g.
+    python -m black_hole_ray_marching_amd.build --out tools/variants/phases \
+        --extra bh_march_exact.hip=-DBH_DIAG_PHASES=1 --extra bh_march_exact_lat.hip=-DBH_DIAG_PHASES=1
+run with BH_LIB=tools/variants/phases/libbh_render.so).
 
 The clock-probed waves (one in `stride`) add the shader cycles of five phases to their XCD's
 accumulator (bh_march.hpp, BH_DIAG_PHASES): tables staged, tile + pixel ray, march, shading + store,
 cost bookkeeping.  Prints the mean cycles per sampled wave and each phase's share of the lifetime, for
 the headline workload (4096x2048, cap 512, camera A, 32 frames per launch, RGBA16F, two targets).
-    BH_LIB=tools/variants/phases.so python tools/probe_phases.py [--launches 20]
+    BH_LIB=tools/variants/phases/libbh_render.so python tools/probe_phases.py [--launches 20]
 config 1 (256x256, cap 64, no surfaces, 256 frames per launch):
     ... tools/probe_phases.py --width 256 --height 256 --cap 64 --frames 256 --no-surfaces --stride 4"""
 import argparse
