@@ -68,6 +68,8 @@ TU_FLAGS = {
     "bh_host.cpp": ["-ffp-contract=off", "-x", "hip"],
     "bh_camera.cpp": ["-ffp-contract=off", "-x", "hip"],
     "bh_bloom_host.cpp": ["-ffp-contract=off", "-x", "hip"],
+    # plain C++ (no HIP): the bloom's plan builders replay the kernels' f32 arithmetic, IEEE and uncontracted
+    "bh_bloom_plan.cpp": ["-ffp-contract=off"],
     "bh_tiles_host.cpp": ["-ffp-contract=off", "-x", "hip"],
     "bh_mirror.cpp": ["-ffp-contract=off", "-x", "hip"],
     "bh_present.cpp": ["-x", "hip"],

@@ -19,18 +19,11 @@
 // coalesced stores; the 256-entry decode table and the 257 encode thresholds in LDS.
 #include <hip/hip_runtime.h>
 
-#include <algorithm>
-#include <climits>
-#include <cmath>
-#include <cstdarg>
-#include <cstdio>
 #include <cstdlib>
-#include <cstring>
-#include <string>
 #include <type_traits>
-#include <vector>
 #include <utility>
 
+#include "bh_bloom_plan.hpp"
 #include "bh_common.hpp"
 #include "bh_crmath.hpp"
 #include "bh_srgb.hpp"
@@ -212,29 +205,6 @@ struct Taps {
     __device__ __forceinline__ float dv_min() const { return dv(6); }
     __device__ __forceinline__ float dv_max() const { return dv(2); }
 };
-// tap i's offset multiplier along an axis (Taps::du / dv), and floor / remainder in eighths (the
-// standard plans, see quad_tap_std)
-__host__ __device__ constexpr int tap_m(int axis, int i) {
-    return (int)(((axis ? 0x10123432u : 0x12343210u) >> (4 * i)) & 15u) - 2;
-}
-__host__ __device__ constexpr int fdiv8(int v) { return v >= 0 ? v / 8 : -((7 - v) / 8); }
-__host__ __device__ constexpr int fmod8(int v) { return v - 8 * fdiv8(v); }
-
-// The structured form of an 8-tap pass, proven by the host for every pixel of a launch
-// (bh_bloom_tap_plan): along each axis tap i's unclamped texel coordinate u*n - 0.5 equals x + o_i + f_i
-// exactly, with an integer offset o_i and a weight f_i of 0 (point) or 1/2 (half).  The bilinear sample
-// then reads texels clamp(x + o_i) and clamp(x + o_i + 1) at constant offsets, and its lerps reduce
-// exactly: with weights 1/2 (products by 1/2 exact for the decoded texels, which are 0 or >= 2^-12)
-//   (t0 * 0.5 + t1 * 0.5) == (t0 + t1) * 0.5,   both axes: ((t00 + t10) + (t01 + t11)) * 0.25,
-// and with weight 0 the lerp returns t0 (t * 1 + t' * 0 == t).  Clamping agrees at the edges: a
-// coordinate clamped to -1 or n has weight 0 and selects the edge texel, which both reads of a half
-// tap then clamp to (t + t) * 0.5 == t).
-struct TapPlan {
-    int32_t ox[8], oy[8];
-    uint32_t hx, hy;                 // bit i: tap i's weight along x (y) is 1/2, else 0
-    int32_t lo_x, hi_x, lo_y, hi_y;  // the footprint's offsets: min o_i, max (o_i + half_i)
-    uint32_t valid;
-};
 // A block's staged footprint for a TapPlan: entry (y - y0) * FP + (x - x0) of the tile holds texel
 // (clamp(x), clamp(y)) for the logical coordinates [x0, x0 + FP) x [y0, y0 + FP): decoded (float4), or
 // with RAW the BGRA8 word (4 B instead of 16: the final pass's 44 x 44 footprint then takes 7.6 KiB of
@@ -353,8 +323,9 @@ __device__ __forceinline__ F4 remix(F4 c0, F4 c1) {
             __builtin_fmaf(c1.a, 0.5f, c0.a)};
 }
 
-enum Shader : uint32_t { SH_COPY = bh_bloom_shader_copy, SH_DOWN = bh_bloom_shader_down, SH_UP = bh_bloom_shader_up,
-                         SH_REMIX = bh_bloom_shader_remix };
+static_assert(SH_COPY == bh_bloom_shader_copy && SH_DOWN == bh_bloom_shader_down && SH_UP == bh_bloom_shader_up &&
+                  SH_REMIX == bh_bloom_shader_remix,
+              "bh_bloom_plan.hpp's Shader is the ABI's bh_bloom_shader");
 
 // The texel range one axis of a 16-pixel block samples through 8 taps: every rounding step of
 // sample_coord is monotone in the texcoord, so the extreme taps of the first and last pixel bound it.
@@ -459,9 +430,6 @@ __device__ __forceinline__ void with_source(Tables tb, CTex t, Lds& L, float4* t
 
 // occupancy floor for the 8-tap kernels: the unrolled taps otherwise take 160 VGPRs (3 waves/SIMD)
 #define BLOOM_BOUNDS __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1)))
-constexpr int FP_UP = 24;     // staged footprint of a generic up pass (taps within a few texels)
-constexpr int FP_Y = 24;      // blur1 at full size: taps within +-3 texels (22 x 22)
-constexpr int FP_FINAL = 44;  // the last up pass at res / 4: taps within +-12 texels (42 x 42)
 
 // ---- separable plan of an 8-tap pass (any frame size) -------------------------------------------
 // A tap's texel coordinate along x depends only on the pixel's column (texcoord(x) + du_i, then
@@ -470,21 +438,16 @@ constexpr int FP_FINAL = 44;  // the last up pass at res / 4: taps within +-12 t
 // contraction) and the kernel reads it instead of recomputing it per pixel: the general sampler's lerps
 // on the general sampler's texels, the same bits.  Used by the up passes whose TapPlan / Up2Plan proofs
 // fail (frame sizes other than powers of two).
-// Entry per tap and column (then per tap and row): the UNCLAMPED floor f of the sampler's coordinate t
-// (t clamped to [-1, n] as sample_coord does, so f is in [-1, n]) and the weights fa = t - f (in [0, 1]: a t just
-// below an integer rounds t - f up to 1),
-// ia = 1 - fa.  The block stages its footprint with clamp-to-edge addressing -- tile entry (ly, lx)
-// holds texel (clamp(lo_y + ly), clamp(lo_x + lx)) -- so sample()'s texels clamp(f) and clamp(f + 1)
-// are tile entries f - lo and f + 1 - lo: a tap's four reads are one base offset plus 0, 1, FP, FP + 1.
-struct SepEntry { int32_t f; float fa, ia; int32_t pad; };
-static_assert(sizeof(SepEntry) == 16, "one ds_read_b128 per entry");
+// Entry per tap and column (then per tap and row): SepEntry (bh_bloom_plan.hpp).  The block stages its footprint
+// with clamp-to-edge addressing -- tile entry (ly, lx) holds texel (clamp(lo_y + ly), clamp(lo_x + lx)) -- so
+// sample()'s texels clamp(f) and clamp(f + 1) are tile entries f - lo and f + 1 - lo: a tap's four reads are one
+// base offset plus 0, 1, FP, FP + 1.
 
-// Epilogues of the separable up pass.  PLAIN: out = q(up8).  Y (the general fused chain's first stage,
+// Epilogues of the separable up pass (SepEpi).  PLAIN: out = q(up8).  Y (the general fused chain's first stage,
 // source X): U = q(up8(X)) to `aux` for every pixel, and Y = q(X + 0.5 U) to `out` for the pixels whose
-// column and row sample exactly (same-size plan weight 0; the rest: fixup_kernel).  FINAL (source U0
+// column and row sample exactly (same-size plan weight 0; the rest: fixup_gather_kernel).  FINAL (source U0
 // = the blur's last up input, res = res[L]): B = q(up8(U0)) to `aux`, and for exact pixels
 // out = q(col + 0.5 q(Y + 0.5 B)) (own0 = col, own1 = Y).
-enum SepEpi : uint32_t { EPI_PLAIN = 0, EPI_Y = 1, EPI_FINAL = 2 };
 
 // bilinear of texels (t00, t10, t01, t11) with weights (fa, fb): sample()'s operations in its order
 __device__ __forceinline__ F4 lerp_plan(const float4& t00, const float4& t10, const float4& t01, const float4& t11,
@@ -502,9 +465,8 @@ __device__ __forceinline__ F4 lerp_plan(const float4& t00, const float4& t10, co
 // the wide footprint of the final pass: 44 x 48 words = 8.4 KiB instead of 33 KiB), decoded when a tap
 // reads them.  FS: the tile's row stride, a multiple of 16 float4 for the decoded tile (ds_read_b128 lane
 // groups take two rows: see FS_YQ; in a same-size pass lane l reads column ~l & 15 of row ~l >> 4) and 16
-// mod 32 words for the raw one (ds_read_b32: lanes 0-15 row r, 16-31 row r + 1 land on the other banks).
-template <int FP, bool RAW>
-constexpr int sep_stride() { return RAW ? (FP + 16) / 32 * 32 + 16 : (FP + 15) / 16 * 16; }
+// mod 32 words for the raw one (ds_read_b32: lanes 0-15 row r, 16-31 row r + 1 land on the other banks):
+// sep_stride (bh_bloom_plan.hpp).
 template <int FP, uint32_t EPI, bool RAW = false, int FS = sep_stride<FP, RAW>()>
 __global__ void BLOOM_BOUNDS up_sep_kernel(Tables tb, CTex a, uint32_t rx, uint32_t ry, const SepEntry* __restrict__ sep,
                                            Tex out, CTex own0, CTex own1, const uint2* __restrict__ same, Tex aux) {
@@ -668,24 +630,8 @@ __device__ __forceinline__ float q_ia(const QEntry& e) { return 1.0f - e.fa; }
 __device__ __forceinline__ QEntry q_entry(int32_t f, int32_t pad, const SepEntry& e) {
     return {(int16_t)f, (int16_t)pad, e.fa};
 }
-// The raw 60-word tile's row stride (any stride keeps the quad rows' bank parity: the next quad row is
-// 2 FS + 1 words further, an odd number).  64 instead of 80: 15 KiB of tile instead of 19
-constexpr int SEPQ_FS60 = 64;
 // an occupancy floor of 6 waves per EU for the quad kernel
 #define SEPQ_BOUNDS __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(6)))
-template <int FP, bool RAW>
-constexpr int sepq_stride() { return RAW ? (FP + 16) / 32 * 32 + 16 : (FP + 15) / 16 * 16; }
-// FIX (EPI_Y only): the block also recomputes its inexact pixels whose same-size sample stays inside the
-// block -- S(X) from the staged tile, S(U1) from the block's own U words exchanged through LDS after a
-// barrier -- so the fix-up pass keeps only the columns and rows whose sample crosses a block edge (none for
-// the grid origin the host picks, bh_bloom_same_plan_org).  org: the block grid's origin, blocks start at
-// 32 k - (org & 0xFFFF) columns and 32 k - (org >> 16) rows (even offsets: a quad never straddles the frame
-// edge).
-// With EPI_FINAL (FIX2 below) the fix reaches two texels: out = remix(S(col), S(F)) with F = q(remix(S(Y),
-// S(B))) at the sample's texels, each of them exact (F is then the exact epilogue's own z) or itself sampled
-// -- B from the block's words, Y and col from the block's own words, all through LDS.  Its three barriers
-// come after the taps, so the dead tile holds the B, Y and F words and the dead plan entries the col words.
-constexpr uint32_t FIX_WORDS = 32u * 33u;  // one padded 32 x 32 array of words
 // The epilogue's own texels are loaded after the tile is staged ("late"), so that the launch's first waves
 // load only their footprints (its opening burst is HBM-bound) and the own texels arrive during the taps; the
 // block's opaque test then covers the footprint only, and the epilogue decodes the own texels' alpha unless
@@ -695,20 +641,13 @@ constexpr uint32_t FIX_WORDS = 32u * 33u;  // one padded 32 x 32 array of words
 // a per-round row, and an out-of-footprint lane stores into a spare tile slot instead of branching; where rows
 // of FP lanes take fewer rounds (FP = 40: 7 instead of 10) the element index is split by the constant FP
 // instead.
-template <int FP, bool RAW, int FS>
-constexpr bool sepq_fix2_fits() {
-    return sizeof(std::conditional_t<RAW, uint32_t, float4>) * (FP * FS + FP / 2) >= 3u * FIX_WORDS * 4u;
-}
-template <int FP, uint32_t EPI, bool RAW, int FS = sepq_stride<FP, RAW>(), bool FIX = false>
+template <int FP, uint32_t EPI, bool RAW, int FS>
 __global__ void SEPQ_BOUNDS up_sepq_kernel(Tables tb, CTex a, uint32_t rx, uint32_t ry,
                                                       const SepEntry* __restrict__ sep, Tex out, CTex own0, CTex own1,
-                                                      const uint2* __restrict__ same, Tex aux, uint32_t org,
+                                                      const uint2* __restrict__ same, Tex aux,
                                                       const uint32_t* __restrict__ stc, uint32_t* __restrict__ strips,
                                                       uint32_t strip_w) {
-    // FIX2: the final epilogue's fix (an instantiation whose tile cannot hold its words never takes it; the
-    // host does not request it there, bh_bloom_sep_fix_ok)
-    constexpr bool FIX1 = FIX && EPI == EPI_Y, FIX2 = FIX && EPI == EPI_FINAL && sepq_fix2_fits<FP, RAW, FS>();
-    constexpr bool LATE = EPI != EPI_PLAIN && !FIX2;
+    constexpr bool LATE = EPI != EPI_PLAIN;
     using TileT = std::conditional_t<RAW, uint32_t, float4>;
     __shared__ Lds L;
     // + 1: the spare slot of the row-wise staging's out-of-footprint lanes
@@ -719,16 +658,7 @@ __global__ void SEPQ_BOUNDS up_sepq_kernel(Tables tb, CTex a, uint32_t rx, uint3
     __shared__ __attribute__((aligned(16))) QEntry cr[2][8][2][16];
     auto& colp = cr[0];
     auto& rowp = cr[1];
-    static_assert(sizeof(cr) >= 32u * 32u * 4u, "FIX2's col words");
-    __shared__ uint32_t ublk[FIX1 ? 32 : 1][FIX1 ? 33 : 1];  // the block's U words (FIX1)
-    __shared__ uint32_t okc[FIX2 ? 32 : 1], okr[FIX2 ? 32 : 1];  // FIX2: F of the block column / row computable
-    // FIX2: the same-size plan entries of the block's columns and rows, staged with the footprint (in registers
-    // across the taps they pushed the final pass past its 80 VGPRs into scratch)
-    __shared__ uint2 sce[FIX2 ? 32 : 1], sre[FIX2 ? 32 : 1];
-    // the block's first column / row (negative for the first block of a grid with an origin offset: wrapped,
-    // so x < ow fails for the columns left of the frame) and the first ones inside the frame
-    const uint32_t bx = xcd_block().x * 32u - (org & 0xFFFFu), by = xcd_block().y * 32u - (org >> 16);
-    const uint32_t bxf = (int32_t)bx < 0 ? 0u : bx, byf = (int32_t)by < 0 ? 0u : by;
+    const uint32_t bx = xcd_block().x * 32u, by = xcd_block().y * 32u;  // the block's first column / row
     const uint32_t ow = EPI == EPI_PLAIN ? out.w : aux.w, oh = EPI == EPI_PLAIN ? out.h : aux.h;
     const uint32_t qx = threadIdx.x & 15u, qy = threadIdx.x >> 4;
     const uint32_t x0 = bx + 2u * qx, y0 = by + 2u * qy;  // the quad's first pixel
@@ -736,9 +666,9 @@ __global__ void SEPQ_BOUNDS up_sepq_kernel(Tables tb, CTex a, uint32_t rx, uint3
     const crm::Rcp Rw = crm::rcp_refined((float)ow), Rh = crm::rcp_refined((float)oh);
     const Taps k(rx, ry);
     const uint32_t xl = min(bx + 31u, ow - 1u), yl = min(by + 31u, oh - 1u);
-    const int32_t lo_x = (int32_t)floorf(sample_coord(texcoord(bxf, Rw) + k.du_min(), a.w));
+    const int32_t lo_x = (int32_t)floorf(sample_coord(texcoord(bx, Rw) + k.du_min(), a.w));
     const int32_t hi_x = (int32_t)floorf(sample_coord(texcoord(xl, Rw) + k.du_max(), a.w));
-    const int32_t lo_y = (int32_t)floorf(sample_coord(texcoord(byf, Rh) + k.dv_min(), a.h));
+    const int32_t lo_y = (int32_t)floorf(sample_coord(texcoord(by, Rh) + k.dv_min(), a.h));
     const int32_t hi_y = (int32_t)floorf(sample_coord(texcoord(yl, Rh) + k.dv_max(), a.h));
     const int32_t cx = min(hi_x - lo_x + 2, FP), cy = min(hi_y - lo_y + 2, FP);  // the host sizes FP: no cut
     const int32_t wm = (int32_t)a.w - 1, hm = (int32_t)a.h - 1;
@@ -774,22 +704,17 @@ __global__ void SEPQ_BOUNDS up_sepq_kernel(Tables tb, CTex a, uint32_t rx, uint3
     for (int h = 0; h < 2; ++h) {
         const uint32_t i = (threadIdx.x >> 5) & 7u, j = threadIdx.x & 31u;
         if (h == 0) {
-            const SepEntry e = sep[i * ow + (uint32_t)clampi((int32_t)(bx + j), 0, (int32_t)ow - 1)];
+            const SepEntry e = sep[i * ow + min(bx + j, ow - 1u)];
             colp[i][j & 1u][j >> 1] = q_entry(e.f - lo_x, 0, e);
         } else {
-            const SepEntry e = sep[8u * ow + i * oh + (uint32_t)clampi((int32_t)(by + j), 0, (int32_t)oh - 1)];
+            const SepEntry e = sep[8u * ow + i * oh + min(by + j, oh - 1u)];
             const int32_t ly = e.f - lo_y;
             rowp[i][j & 1u][j >> 1] = q_entry(ly * FS + (ly >> 1), ly, e);
         }
     }
-    if constexpr (FIX2) {  // every block column's and row's entry (clamped: one outside the frame is never read)
-        if (threadIdx.x < 32u) sce[threadIdx.x] = same[clampi((int32_t)(bx + threadIdx.x), 0, (int32_t)ow - 1)];
-        else if (threadIdx.x < 64u) sre[threadIdx.x - 32u] = same[ow + clampi((int32_t)(by + threadIdx.x - 32u), 0, (int32_t)oh - 1)];
-    }
-    // own texels of the epilogue (four pixels), loaded before the tables (LATE: after the staging), used last
+    // own texels of the epilogue (four pixels), loaded after the staging (LATE), used last
     uint32_t o0[2][2], o1[2][2];
     bool in[2][2], exact[2][2];
-    uint2 scx[2] = {}, scy[2] = {};  // same-size plan entries of the quad's columns and rows (FIX1)
     uint32_t m = 0xFF000000u;
 #pragma unroll
     for (int b = 0; b < 2; ++b)
@@ -797,25 +722,10 @@ __global__ void SEPQ_BOUNDS up_sepq_kernel(Tables tb, CTex a, uint32_t rx, uint3
         for (int c = 0; c < 2; ++c) {
             const uint32_t x = x0 + c, y = y0 + b;
             in[b][c] = x < ow && y < oh;
-            const uint32_t pix = (in[b][c] ? y : 0u) * ow + (in[b][c] ? x : 0u);
             o0[b][c] = o1[b][c] = 0xFF000000u;
             exact[b][c] = false;
-            if constexpr (EPI != EPI_PLAIN) {
-                if constexpr (!LATE) {
-                    o0[b][c] = own0.px[pix];
-                    if constexpr (EPI == EPI_FINAL) o1[b][c] = own1.px[pix];
-                }
-                if constexpr (FIX2) {
-                    // exact[] after the staging barrier, from sce / sre
-                } else if constexpr (FIX1) {
-                    if (b == 0) scx[c] = same[in[b][c] ? x : 0u];
-                    if (c == 0) scy[b] = same[ow + (in[b][c] ? y : 0u)];
-                    exact[b][c] = in[b][c] && scx[c].y == 0u && scy[b].y == 0u;
-                } else {
-                    exact[b][c] = in[b][c] && same[in[b][c] ? x : 0u].y == 0u && same[ow + (in[b][c] ? y : 0u)].y == 0u;
-                }
-            }
-            m = min(m, min(o0[b][c], o1[b][c]));
+            if constexpr (EPI != EPI_PLAIN)
+                exact[b][c] = in[b][c] && same[in[b][c] ? x : 0u].y == 0u && same[ow + (in[b][c] ? y : 0u)].y == 0u;
         }
     load_tables(tb, L);
 #pragma unroll
@@ -833,12 +743,6 @@ __global__ void SEPQ_BOUNDS up_sepq_kernel(Tables tb, CTex a, uint32_t rx, uint3
         m = min(m, v ? raw[r] : 0xFF000000u);
     }
     const bool a1 = barrier_and(m >= 0xFF000000u);
-    if constexpr (FIX2) {
-#pragma unroll
-        for (int b = 0; b < 2; ++b)
-#pragma unroll
-            for (int c = 0; c < 2; ++c) exact[b][c] = in[b][c] && sce[2u * qx + c].y == 0u && sre[2u * qy + b].y == 0u;
-    }
     if constexpr (LATE) {
 #pragma unroll
         for (int b = 0; b < 2; ++b)
@@ -850,12 +754,8 @@ __global__ void SEPQ_BOUNDS up_sepq_kernel(Tables tb, CTex a, uint32_t rx, uint3
             }
         __builtin_amdgcn_sched_barrier(0);  // issued here, awaited in the epilogue
     }
-    // a quad whose first pixel is outside is outside as a whole (even origin offsets); it has no taps, but
-    // with FIX its lanes still meet the block's barriers
-    const bool live = in[0][0];
-    uint32_t bw[2][2] = {}, fw[2][2] = {};  // FIX2: the quad's B words and (exact pixels) F words
-    if (!FIX1 && !FIX2 && !live) return;
-    {
+    // a quad whose first pixel is outside is outside as a whole: it has no taps
+    if (!in[0][0]) return;
     auto run = [&](auto A1c) {
         constexpr bool A1 = decltype(A1c)::value;
         auto texel = [&](int32_t o) {
@@ -877,7 +777,6 @@ __global__ void SEPQ_BOUNDS up_sepq_kernel(Tables tb, CTex a, uint32_t rx, uint3
             q.a = A1 ? 1.0f : (t00.w * ia + t10.w * fa) * ib + (t01.w * ia + t11.w * fa) * fb;
             return q;
         };
-        if (live) {
         F4 s[2][2];
 #pragma unroll
         for (int i = 0; i < 8; ++i) {
@@ -941,7 +840,7 @@ __global__ void SEPQ_BOUNDS up_sepq_kernel(Tables tb, CTex a, uint32_t rx, uint3
         // an inexact column (stc: 1 + its strip column, bh_bloom_strip_table) also stores its col, Y and U
         // words column-major, (image * strip_w + strip column) * oh + row
         uint32_t st[2] = {0u, 0u};
-        if constexpr (EPI == EPI_FINAL && !FIX2) {
+        if constexpr (EPI == EPI_FINAL) {
             if (stc) {
                 st[0] = stc[min(x0, ow - 1u)];
                 st[1] = stc[min(x0 + 1u, ow - 1u)];
@@ -971,7 +870,7 @@ __global__ void SEPQ_BOUNDS up_sepq_kernel(Tables tb, CTex a, uint32_t rx, uint3
                 } else {
                     const uint32_t ue = enc(L, u);
                     aux.px[pix] = ue;
-                    if constexpr (EPI == EPI_FINAL && !FIX2) {
+                    if constexpr (EPI == EPI_FINAL) {
                         if (st[c] != 0u) {
                             const size_t img = (size_t)strip_w * oh;
                             uint32_t* const p = strips + (size_t)(st[c] - 1u) * oh + (y0 + b);
@@ -980,16 +879,12 @@ __global__ void SEPQ_BOUNDS up_sepq_kernel(Tables tb, CTex a, uint32_t rx, uint3
                             p[2u * img] = ue;
                         }
                     }
-                    if constexpr (FIX1) ublk[2u * qy + b][2u * qx + c] = ue;
-                    if constexpr (FIX2) bw[b][c] = ue;
                     if (exact[b][c]) {
                         const F4 uq = dec<AO>(L, ue);
                         if constexpr (EPI == EPI_Y) {
                             out.px[pix] = enc(L, remix(dec<AO>(L, o0[b][c]), uq));
                         } else {
-                            // z = q(Y + 0.5 B): F at this exact pixel, kept as its word for FIX2
-                            const uint32_t zq = enc(L, remix(dec<AO>(L, o1[b][c]), uq));
-                            if constexpr (FIX2) fw[b][c] = zq;
+                            const uint32_t zq = enc(L, remix(dec<AO>(L, o1[b][c]), uq));  // z = q(Y + 0.5 B)
                             out.px[pix] = enc(L, remix(dec<AO>(L, o0[b][c]), dec<AO>(L, zq)));
                         }
                     }
@@ -998,126 +893,10 @@ __global__ void SEPQ_BOUNDS up_sepq_kernel(Tables tb, CTex a, uint32_t rx, uint3
         };
         if (A1 && own_op) epilogue(std::bool_constant<A1>{});
         else epilogue(std::false_type{});
-        }  // live
-        if constexpr (FIX2) {
-            // the taps of every wave are done: the tile and the plan entries are dead
-            __syncthreads();
-            scx[0] = sce[2u * qx]; scx[1] = sce[2u * qx + 1u];
-            scy[0] = sre[2u * qy]; scy[1] = sre[2u * qy + 1u];
-            uint32_t(*const ub)[33] = reinterpret_cast<uint32_t(*)[33]>(tile_mem);
-            uint32_t(*const yb)[33] = ub + 32;
-            uint32_t(*const fb_)[33] = ub + 64;
-            uint32_t(*const cb)[32] = reinterpret_cast<uint32_t(*)[32]>(&cr[0][0][0][0]);
-            // a block column's (row's) F is computable here when it is exact or its sample's texels lie in
-            // the block (nonzero weights only)
-            auto axis_ok = [&](uint2 e, int32_t b0) {
-                if (e.y == 0u) return true;
-                return (uint32_t)((int32_t)(e.x & 0xFFFFu) - b0) <= 31u && (uint32_t)((int32_t)(e.x >> 16) - b0) <= 31u;
-            };
-            if (live) {
-#pragma unroll
-                for (int b = 0; b < 2; ++b)
-#pragma unroll
-                    for (int c = 0; c < 2; ++c) {
-                        if (!in[b][c]) continue;
-                        const uint32_t py = 2u * qy + b, px = 2u * qx + c;
-                        ub[py][px] = bw[b][c];
-                        yb[py][px] = o1[b][c];
-                        cb[py][px] = o0[b][c];
-                        if (exact[b][c]) fb_[py][px] = fw[b][c];
-                    }
-            }
-            // every lane, live or not: a block row (column) outside the frame still has in-frame columns (rows)
-            if (qy == 0u) { okc[2u * qx] = axis_ok(scx[0], (int32_t)bx); okc[2u * qx + 1u] = axis_ok(scx[1], (int32_t)bx); }
-            if (qx == 0u) { okr[2u * qy] = axis_ok(scy[0], (int32_t)by); okr[2u * qy + 1u] = axis_ok(scy[1], (int32_t)by); }
-            __syncthreads();
-            // the sample's block-relative texels of one axis (a weight-0 texel repeats the first: t * 0 == +0)
-            auto texels = [&](uint2 e, int32_t b0, int32_t& t0, int32_t& t1, float& w) {
-                w = __uint_as_float(e.y);
-                t0 = (int32_t)(e.x & 0xFFFFu) - b0;
-                t1 = w != 0.0f ? (int32_t)(e.x >> 16) - b0 : t0;
-            };
-            auto D = [&](uint32_t w) {
-                const F4 d = dec<A1>(L, w);
-                return make_float4(d.r, d.g, d.b, d.a);
-            };
-            // F = q(remix(S(Y), S(B))) at this lane's inexact pixels whose F is computable
-            if (live) {
-#pragma unroll
-                for (int b = 0; b < 2; ++b)
-#pragma unroll
-                    for (int c = 0; c < 2; ++c) {
-                        if (!in[b][c] || exact[b][c]) continue;
-                        const uint32_t py = 2u * qy + b, px = 2u * qx + c;
-                        if (okc[px] == 0u || okr[py] == 0u) continue;
-                        int32_t u0, u1, v0, v1;
-                        float fa, fb;
-                        texels(scx[c], (int32_t)bx, u0, u1, fa);
-                        texels(scy[b], (int32_t)by, v0, v1, fb);
-                        const F4 sy = lerp_plan(D(yb[v0][u0]), D(yb[v0][u1]), D(yb[v1][u0]), D(yb[v1][u1]), fa, fb);
-                        const F4 sb = lerp_plan(D(ub[v0][u0]), D(ub[v0][u1]), D(ub[v1][u0]), D(ub[v1][u1]), fa, fb);
-                        fb_[py][px] = enc(L, remix(sy, sb));
-                    }
-            }
-            __syncthreads();
-            // out = remix(S(col), S(F)) at the inexact pixels whose sample's texels lie in the block and have
-            // a computable F (fixup_gather_kernel<EPI_FINAL>'s arithmetic); the rest: the fix-up pass's
-            if (live) {
-#pragma unroll
-                for (int b = 0; b < 2; ++b)
-#pragma unroll
-                    for (int c = 0; c < 2; ++c) {
-                        if (!in[b][c] || exact[b][c]) continue;
-                        int32_t u0, u1, v0, v1;
-                        float fa, fb;
-                        texels(scx[c], (int32_t)bx, u0, u1, fa);
-                        texels(scy[b], (int32_t)by, v0, v1, fb);
-                        if ((uint32_t)u0 > 31u || (uint32_t)u1 > 31u || (uint32_t)v0 > 31u || (uint32_t)v1 > 31u) continue;
-                        if (okc[u0] == 0u || okc[u1] == 0u || okr[v0] == 0u || okr[v1] == 0u) continue;
-                        const F4 sc = lerp_plan(D(cb[v0][u0]), D(cb[v0][u1]), D(cb[v1][u0]), D(cb[v1][u1]), fa, fb);
-                        const F4 sf = lerp_plan(D(fb_[v0][u0]), D(fb_[v0][u1]), D(fb_[v1][u0]), D(fb_[v1][u1]), fa, fb);
-                        out.px[(y0 + b) * ow + x0 + c] = enc(L, remix(sc, sf));
-                    }
-            }
-        }
-        if constexpr (FIX1) {
-            // Y = remix(S(X), S(U1)) at the inexact pixels whose sample's texels (those of nonzero weight) lie
-            // in this block: fixup_gather_kernel<EPI_Y>'s arithmetic, each texel from LDS (a texel of weight 0
-            // enters the lerp as t * 0 == +0 for any finite t >= 0, as the fix-up's unread 0 does)
-            __syncthreads();
-            if (live) {
-#pragma unroll
-                for (int b = 0; b < 2; ++b)
-#pragma unroll
-                    for (int c = 0; c < 2; ++c) {
-                        if (!in[b][c] || exact[b][c]) continue;
-                        const uint2 ex = scx[c], ey = scy[b];
-                        const float fa = __uint_as_float(ex.y), fb = __uint_as_float(ey.y);
-                        const int32_t u0 = (int32_t)(ex.x & 0xFFFFu) - (int32_t)bx, v0 = (int32_t)(ey.x & 0xFFFFu) - (int32_t)by;
-                        const int32_t u1 = fa != 0.0f ? (int32_t)(ex.x >> 16) - (int32_t)bx : u0;
-                        const int32_t v1 = fb != 0.0f ? (int32_t)(ey.x >> 16) - (int32_t)by : v0;
-                        if ((uint32_t)u0 > 31u || (uint32_t)u1 > 31u || (uint32_t)v0 > 31u || (uint32_t)v1 > 31u)
-                            continue;  // crosses the block edge: the fix-up pass's (residual list)
-                        auto X = [&](int32_t u, int32_t v) {
-                            const int32_t ly = v + (int32_t)by - lo_y, lx = u + (int32_t)bx - lo_x;
-                            return texel(ly * FS + lx + (ly >> 1));
-                        };
-                        auto U = [&](int32_t u, int32_t v) {
-                            const F4 d = dec<A1>(L, ublk[v][u]);
-                            return make_float4(d.r, d.g, d.b, d.a);
-                        };
-                        const F4 sx = lerp_plan(X(u0, v0), X(u1, v0), X(u0, v1), X(u1, v1), fa, fb);
-                        const F4 su = lerp_plan(U(u0, v0), U(u1, v0), U(u0, v1), U(u1, v1), fa, fb);
-                        out.px[(y0 + b) * ow + x0 + c] = enc(L, remix(sx, su));
-                    }
-            }
-        }
     };
     if (a1) run(std::true_type{});
     else run(std::false_type{});
-    }
 }
-
 
 // ---- remixes of the chain at any proven-identity size (general fused schedule) ----------------------
 // On frames whose same-size passes are identities on stored texels (the host's same_size_identity, e.g.
@@ -1286,8 +1065,7 @@ __global__ void __launch_bounds__(256) same_copy_kernel(Tables tb, CTex src, con
 // column.
 template <uint32_t EPI>
 __global__ void __launch_bounds__(256) fixup_gather_kernel(Tables tb, CTex A, CTex B, CTex C,
-                                                           const uint2* __restrict__ plan,
-                                                           const uint32_t* __restrict__ list, uint32_t n_cols,
+                                                           const uint2* __restrict__ plan, uint32_t n_cols,
                                                            uint32_t n_rows, Tex out, const uint4* __restrict__ rec,
                                                            const uint32_t* __restrict__ strips, uint32_t strip_w) {
     __shared__ Lds L;
@@ -1296,74 +1074,52 @@ __global__ void __launch_bounds__(256) fixup_gather_kernel(Tables tb, CTex A, CT
     uint32_t x = 0u, y = 0u, qx = 0u;  // qx: a column lane's strip column (strips)
     bool live = true;
     uint2 cx, cy, PX[3], PY[3];
-    if (rec) {
-        uint32_t k = 0u;
-        bool col = true;
-        if (i < nc) {
-            k = (uint32_t)(i / H);
-            y = (uint32_t)(i % H);
-        } else {
-            const uint64_t j = i - nc;
-            live = j < (uint64_t)n_rows * W;
-            col = false;
-            if (live) {
-                k = n_cols + (uint32_t)(j / W);
-                x = (uint32_t)(j % W);
-            }
-        }
-        const uint4 r0 = rec[2u * k], r1 = rec[2u * k + 1u];
-        const uint2 e0 = make_uint2(r0.y, r0.z), e1 = make_uint2(r0.w, r1.x), e2 = make_uint2(r1.y, r1.z);
-        if (col) {
-            x = r0.x;
-            qx = r1.w - 1u;
-            PX[0] = e0; PX[1] = e1; PX[2] = e2;
-            const uint32_t yc = min(y, H - 1u);
-            PY[1] = plan[W + yc];
-            if constexpr (EPI == EPI_FINAL) {
-                PY[0] = plan[W + (yc ? yc - 1u : 0u)];
-                PY[2] = plan[W + min(yc + 1u, H - 1u)];
-            }
-        } else {
-            y = r0.x;
-            PY[0] = e0; PY[1] = e1; PY[2] = e2;
-            const uint32_t xc = min(x, W - 1u);
-            PX[1] = plan[xc];
-            if constexpr (EPI == EPI_FINAL) {
-                PX[0] = plan[xc ? xc - 1u : 0u];
-                PX[2] = plan[min(xc + 1u, W - 1u)];
-            }
-        }
-        live = live && x < W && y < H;  // defensive: a list entry outside the frame
-        cx = PX[1];
-        cy = PY[1];
-        // a dead lane (past the list, or a row lane's defensive case) gathers at pixel (0, 0) with every neighbour
-        // entry its own: the record it read (entry 0 for a lane past the list, a column record) must not leave a
-        // column's entry among the row ones, whose texel indices would then index rows (round 6's memory fault
-        // at 3996 x 495: tools/bloom_fixup_addr.cpp)
-        if (!live) { x = y = 0u; cx = plan[0]; cy = plan[W]; PX[0] = PX[1] = PX[2] = cx; PY[0] = PY[1] = PY[2] = cy; }
+    uint32_t k = 0u;
+    bool col = true;
+    if (i < nc) {
+        k = (uint32_t)(i / H);
+        y = (uint32_t)(i % H);
     } else {
-        if (i < nc) {
-            x = list[i / H];
-            y = (uint32_t)(i % H);
-        } else {
-            const uint64_t j = i - nc;
-            live = j < (uint64_t)n_rows * W;
-            if (live) {
-                y = list[n_cols + j / W];
-                x = (uint32_t)(j % W);
-            }
-        }
-        live = live && x < W && y < H;  // defensive: a list entry outside the frame
-        if (!live) x = y = 0u;
-        cx = plan[x];
-        cy = plan[W + y];
-        if constexpr (EPI == EPI_FINAL) {
-            PX[0] = plan[x ? x - 1u : 0u]; PX[1] = cx; PX[2] = plan[min(x + 1u, W - 1u)];
-            PY[0] = plan[W + (y ? y - 1u : 0u)]; PY[1] = cy; PY[2] = plan[W + min(y + 1u, H - 1u)];
+        const uint64_t j = i - nc;
+        live = j < (uint64_t)n_rows * W;
+        col = false;
+        if (live) {
+            k = n_cols + (uint32_t)(j / W);
+            x = (uint32_t)(j % W);
         }
     }
+    const uint4 r0 = rec[2u * k], r1 = rec[2u * k + 1u];
+    const uint2 e0 = make_uint2(r0.y, r0.z), e1 = make_uint2(r0.w, r1.x), e2 = make_uint2(r1.y, r1.z);
+    if (col) {
+        x = r0.x;
+        qx = r1.w - 1u;
+        PX[0] = e0; PX[1] = e1; PX[2] = e2;
+        const uint32_t yc = min(y, H - 1u);
+        PY[1] = plan[W + yc];
+        if constexpr (EPI == EPI_FINAL) {
+            PY[0] = plan[W + (yc ? yc - 1u : 0u)];
+            PY[2] = plan[W + min(yc + 1u, H - 1u)];
+        }
+    } else {
+        y = r0.x;
+        PY[0] = e0; PY[1] = e1; PY[2] = e2;
+        const uint32_t xc = min(x, W - 1u);
+        PX[1] = plan[xc];
+        if constexpr (EPI == EPI_FINAL) {
+            PX[0] = plan[xc ? xc - 1u : 0u];
+            PX[2] = plan[min(xc + 1u, W - 1u)];
+        }
+    }
+    live = live && x < W && y < H;  // defensive: a list entry outside the frame
+    cx = PX[1];
+    cy = PY[1];
+    // a dead lane (past the list, or a row lane's defensive case) gathers at pixel (0, 0) with every neighbour
+    // entry its own: the record it read (entry 0 for a lane past the list, a column record) must not leave a
+    // column's entry among the row ones, whose texel indices would then index rows (round 6's memory fault
+    // at 3996 x 495: tools/bloom_fixup_addr.cpp)
+    if (!live) { x = y = 0u; cx = plan[0]; cy = plan[W]; PX[0] = PX[1] = PX[2] = cx; PY[0] = PY[1] = PY[2] = cy; }
     if (i >= nc && cx.y != 0u) live = false;  // an inexact column: its pixels are the first part's
-    const bool sl = EPI == EPI_FINAL && strips != nullptr && rec != nullptr && i < nc;  // a column lane on strips
+    const bool sl = EPI == EPI_FINAL && strips != nullptr && i < nc;  // a column lane on strips
     auto img = [&](CTex T, uint32_t im) -> SrcImg {
         if (sl) return {strips + (size_t)im * strip_w * H, 1u, H, strip_w - 1u, (int32_t)x - (int32_t)qx};
         return {T.px, W, 1u, 0xFFFFFFFFu, 0};
@@ -1410,45 +1166,6 @@ __global__ void __launch_bounds__(256) fixup_gather_kernel(Tables tb, CTex A, CT
                                    make_float4(f2.r, f2.g, f2.b, f2.a), make_float4(f3.r, f3.g, f3.b, f3.a), fa, fb);
             out.px[y * W + x] = enc(L, remix(finish_same(L, a), f));
         }
-    }
-}
-
-template <uint32_t EPI>
-__global__ void __launch_bounds__(256) fixup_kernel(Tables tb, CTex A, CTex B, CTex C, const uint2* __restrict__ plan,
-                                                    const uint32_t* __restrict__ list, uint32_t n_cols, uint32_t n_rows,
-                                                    Tex out) {
-    __shared__ Lds L;
-    load_tables(tb, L);
-    const uint32_t W = out.w, H = out.h;
-    const uint64_t i = (uint64_t)blockIdx.x * 256u + threadIdx.x, nc = (uint64_t)n_cols * H;
-    uint32_t x, y;
-    if (i < nc) {
-        x = list[i / H];
-        y = (uint32_t)(i % H);
-    } else {
-        const uint64_t j = i - nc;
-        if (j >= (uint64_t)n_rows * W) return;
-        y = list[n_cols + j / W];
-        x = (uint32_t)(j % W);
-        if (plan[x].y != 0u) return;  // an inexact column: its pixels are the first part's
-    }
-    if (x >= W || y >= H) return;  // defensive: a list entry outside the frame
-    const uint2 cx = plan[x], cy = plan[W + y];
-    if constexpr (EPI == EPI_Y) {
-        out.px[y * W + x] = enc(L, remix(sample_same(L, A, cx, cy), sample_same(L, B, cx, cy)));
-    } else {
-        auto F = [&](uint32_t u, uint32_t v) {
-            const uint2 px = plan[u], py = plan[W + v];
-            return quant(L, remix(sample_same(L, B, px, py), sample_same(L, C, px, py)));
-        };
-        const float fa = __uint_as_float(cx.y), fb = __uint_as_float(cy.y);
-        const uint32_t x0 = cx.x & 0xFFFFu, x1 = cx.x >> 16, y0 = cy.x & 0xFFFFu, y1 = cy.x >> 16;
-        const F4 z{0.0f, 0.0f, 0.0f, 0.0f};
-        const bool ex = fa != 0.0f, ey = fb != 0.0f;
-        const F4 a = F(x0, y0), b = ex ? F(x1, y0) : z, c = ey ? F(x0, y1) : z, d = ex && ey ? F(x1, y1) : z;
-        const F4 f = lerp_plan(make_float4(a.r, a.g, a.b, a.a), make_float4(b.r, b.g, b.b, b.a),
-                               make_float4(c.r, c.g, c.b, c.a), make_float4(d.r, d.g, d.b, d.a), fa, fb);
-        out.px[y * W + x] = enc(L, remix(sample_same(L, A, cx, cy), f));
     }
 }
 
@@ -1603,8 +1320,7 @@ __global__ void BLOOM_BOUNDS bloom_y_kernel(Tables tb, CTex X, uint32_t point, T
 // texels lie in a (2 + hx) x (2 + hy) neighbourhood at the plan's constant offset, read once for the
 // four pixels (14 LDS reads per pixel instead of 21 at 4096x2048), each pixel reduced exactly as
 // up8(PlanSrc) does.  HX / HY: the tap's half flags.
-constexpr int FP_YQ = 40;  // 32 + the taps' reach (38 at 4096x2048)
-// The tile's layout: entry (ly, lx) at ly * FS_YQ + lx + ((ly + p) >> 1), p = lo_y & 1 -- every second row
+// The tile's layout (side FP_YQ, row stride FS_YQ: bh_bloom_plan.hpp): entry (ly, lx) at ly * FS_YQ + lx + ((ly + p) >> 1), p = lo_y & 1 -- every second row
 // pair shifted by one float4.  The quad loops' ds_read_b128 lane groups ({0-3, 12-15, 20-27}, {4-11, 16-19,
 // 28-31}, ...: 16 lanes, one pass over the 64 banks) take two quad rows each, and a lane reads at quad
 // column 2 (l & 15) -- only the even 4-bank slots of its quad row.  Without the shift the next quad row (two
@@ -1612,8 +1328,7 @@ constexpr int FP_YQ = 40;  // 32 + the taps' reach (38 at 4096x2048)
 // SQ_LDS_BANK_CONFLICT / SQ_LDS_IDX_ACTIVE 0.34 at strides 40 and 41).  With it a quad row is 2 FS_YQ + 1
 // float4 further, odd: the next quad row reads the odd slots.  (p makes the quad's first texel row even in
 // the shifted index, so a tap's row offsets are launch constants: yq_rowoff(d) = d FS_YQ + floor(d / 2).)
-constexpr int FS_YQ = 40;
-__host__ __device__ constexpr int32_t yq_rowoff(int32_t d) { return d * FS_YQ + (d >= 0 ? d / 2 : -((1 - d) / 2)); }
+constexpr int32_t yq_rowoff(int32_t d) { return d * FS_YQ + (d >= 0 ? d / 2 : -((1 - d) / 2)); }
 template <int HX, int HY>
 __device__ __forceinline__ void yquad_tap(const float4* T, int32_t d1, int i, F4 (&s)[2][2]) {
     // T: the tap's first texel; the rows below it are d1 (FS_YQ or FS_YQ + 1) and 2 FS_YQ + 1 further
@@ -1782,112 +1497,6 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(7))) b
         true);
 }
 
-// ---- persistent blocks (standard plans) ------------------------------------------------------------
-// The grid is the resident block count (a multiple of 8); block b walks the 16x16 tiles of one eighth of
-// the frame (b % 8: the blocks the dispatcher deals to one XCD, whose L2 then holds the halos its tiles
-// share) with stride gridDim / 8.  While a tile is computed from one LDS buffer, the next tile's
-// footprint streams into the other by LDS DMA (global_load_lds: no VGPRs, and the compiler does not
-// wait on it for reads of the other buffer -- a distinct __shared__ array), and the next tile's own
-// per-pixel loads are in flight in registers; the one barrier per tile waits for both.  This hides the
-// staging latency that one-tile blocks expose at every block start, amortises the table loads over the
-// block's tiles and removes the grid's last partial wave of blocks.
-struct TileWalk {
-    uint32_t t, end, step;
-    __device__ __forceinline__ TileWalk(uint32_t n_tiles) {
-        const uint32_t per = (n_tiles + 7u) >> 3, x = blockIdx.x & 7u;
-        const uint32_t start = min(x * per, n_tiles);
-        end = min(start + per, n_tiles);
-        step = gridDim.x >> 3;
-        t = start + (blockIdx.x >> 3);
-    }
-    __device__ __forceinline__ bool valid(uint32_t u) const { return u < end; }
-};
-
-// One 16x16 tile's footprint of a same-size A = STD pass: (16 + 2R)^2 BGRA8 words, row-major, clamped to
-// the texture, by LDS DMA into `buf` (each wave-instruction fills 64 consecutive words).
-template <int STD>
-struct FinalStd {
-    static constexpr int RCH = 2 * (STD / 8);  // the taps' reach: |offset| <= 2 * A / 8 texels
-    static constexpr int NX = 16 + 2 * RCH, NN = NX * NX, ROUNDS = (NN + 255) / 256;
-};
-template <int STD>
-__device__ __forceinline__ void stage_final_dma(const CTex& U, uint32_t t, uint32_t tiles_x, uint32_t* buf) {
-    using F = FinalStd<STD>;
-    const uint32_t ty = t / tiles_x, tx = t - ty * tiles_x;
-    const int32_t x0 = (int32_t)tx * 16 - F::RCH, y0 = (int32_t)ty * 16 - F::RCH;
-    const int32_t wm = (int32_t)U.w - 1, hm = (int32_t)U.h - 1;
-#pragma unroll
-    for (int r = 0; r < F::ROUNDS; ++r) {
-        const int32_t i = r * 256 + (int32_t)threadIdx.x;
-        if (r * 256 + (int32_t)(threadIdx.x & ~63u) < F::NN) {  // wave-uniform: whole 64-word runs
-            const int32_t ly = min(i, F::NN - 1) / F::NX, lx = min(i, F::NN - 1) - ly * F::NX;
-            const uint32_t* g = U.px + (uint32_t)clampi(y0 + ly, 0, hm) * U.w + clampi(x0 + lx, 0, wm);
-            __builtin_amdgcn_global_load_lds(g, buf + r * 256 + (threadIdx.x & ~63u), 4, 0, 0);
-        }
-    }
-}
-// Fused last stage (bloom_final_kernel) with the standard plan A = STD, persistent.
-template <int STD>
-__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(7)))
-bloom_final_pkernel(Tables tb, CTex col, CTex Y, CTex U0, TapPlan P, Tex out, uint32_t tiles_x, uint32_t n_tiles) {
-    using F = FinalStd<STD>;
-    static_assert(F::NN % 64 == 0, "whole 64-word DMA runs");
-    __shared__ Lds L;
-    __shared__ uint32_t B0[F::NN], B1[F::NN];
-    TileWalk w(n_tiles);
-    const int32_t lx = (int32_t)(threadIdx.x & 15u), ly = (int32_t)(threadIdx.x >> 4);
-    auto pix = [&](uint32_t t, int32_t& x, int32_t& y) {
-        const uint32_t ty = t / tiles_x;
-        x = (int32_t)(t - ty * tiles_x) * 16 + lx;
-        y = (int32_t)ty * 16 + ly;
-    };
-    auto fetch_px = [&](uint32_t t, uint32_t& yv, uint32_t& cv) {
-        int32_t x, y;
-        pix(t, x, y);
-        const bool in = x < (int32_t)out.w && y < (int32_t)out.h;
-        const uint32_t i = in ? (uint32_t)y * out.w + (uint32_t)x : 0;
-        yv = Y.px[i];
-        cv = col.px[i];
-    };
-    uint32_t yv = 0, cv = 0;
-    if (w.valid(w.t)) {
-        fetch_px(w.t, yv, cv);
-        stage_final_dma<STD>(U0, w.t, tiles_x, B0);
-    }
-    load_tables(tb, L);
-    // one tile from `cur` while the next streams into `nxt` (the loop is unrolled by two so that each
-    // buffer stays a distinct array in the code)
-    auto tile = [&](const uint32_t* cur, uint32_t* nxt) -> bool {
-        if (!w.valid(w.t)) return false;  // block-uniform
-        // cur's DMA (every wave's share) and this tile's pixel loads landed, nxt's last readers are done:
-        // each wave drains its own vector-memory counter first (the compiler does not count the LDS
-        // DMA's writes as LDS stores that the barrier must order), then the barrier
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __syncthreads();
-        const uint32_t t = w.t, tn = t + w.step;
-        uint32_t yn = 0, cn = 0;
-        if (w.valid(tn)) {
-            fetch_px(tn, yn, cn);
-            stage_final_dma<STD>(U0, tn, tiles_x, nxt);
-        }
-        int32_t x, y;
-        pix(t, x, y);
-        if (x < (int32_t)out.w && y < (int32_t)out.h) {
-            const int32_t x0 = x - lx - F::RCH, y0 = y - ly - F::RCH;
-            const PlanSrc<F::NX, true, STD> src{U0, cur, x0, y0, &P, &L, x, y};
-            const F4 b3 = quant(L, up8(src, Taps(1u, 1u), 0.0f, 0.0f, 0u));
-            const F4 z = quant(L, remix(dec(L, yv), b3));
-            out.px[(uint32_t)y * out.w + (uint32_t)x] = enc(L, remix(dec(L, cv), z));
-        }
-        yv = yn;
-        cv = cn;
-        w.t = tn;
-        return true;
-    };
-    while (tile(B0, B1) && tile(B1, B0)) {
-    }
-}
-
 // The 2:1 form of an 8-tap pass: an up pass from a texture of n texels to 2n pixels along each axis
 // (at 4096x2048 the full-size up pass from 2048x1024 and the one before it).  Its taps' texel
 // coordinates are t = (x >> 1) + o + f with an integer o and a weight f in [0, 1) that depend only on
@@ -1897,13 +1506,7 @@ bloom_final_pkernel(Tables tb, CTex col, CTex Y, CTex U0, TapPlan P, Tex out, ui
 // texels (x>>1) + o and + 1 with weights f, 1 - f -- the general sampler's own arithmetic, without its
 // texcoord, floor and clamp work.  One lane computes a 2x2 pixel quad: per tap the four pixels' texels
 // lie in a 3x3 (2x2 when both parities share o) neighbourhood of (x>>1, y>>1), read once for all four.
-
-struct Up2Plan {
-    int32_t ox[2][8], oy[2][8];      // [pixel parity][tap]: floor(t) - (x >> 1)
-    float fx[2][8], fy[2][8];        // t - floor(t)
-    int32_t x_lo, x_hi, y_lo, y_hi;  // the interior's output pixels (inclusive; empty when lo > hi)
-    uint32_t valid;
-};
+// The plan: Up2Plan (bh_bloom_plan.hpp).
 
 // bilinear of texels (t00, t10, t01, t11) with weights (fa, fb): sample()'s operations in its order
 __device__ __forceinline__ F4 lerp2(const float4& t00, const float4& t10, const float4& t01, const float4& t11, float fa,
@@ -1991,12 +1594,10 @@ __device__ __forceinline__ void quad_taps_std(const float4* base, F4 (&s)[2][2],
 // A 2:1 up pass (kawase_upsample.wgsl): 32x32 pixels per 256-thread block, one 2x2 quad per lane; the
 // outermost blocks (and footprints over FP) take the general sampler per pixel.  STD: 0 = the runtime
 // plan P, else the standard plan A = STD (P still gives the interior).
-constexpr int FP_UPQ = 28;  // footprint of 16 texels + the taps' reach (24 at 4096x2048)
-// row stride in float4, a multiple of 16: here lane l reads texel column (l & 15) + c (a 2:1 pass reads
+// The tile (side FP_UPQ, bh_bloom_plan.hpp) has a row stride FS_UPQ in float4, a multiple of 16: here lane l reads texel column (l & 15) + c (a 2:1 pass reads
 // one texel per output quad), 16 consecutive slots per quad row, and the lane groups take two quad rows
 // (see FS_YQ): with 28 the second row overlapped the first's slots (bank conflicts 0.42 of LDS-active
 // cycles), with 32 it lands on the same slots of the next 64 banks (0.01)
-constexpr int FS_UPQ = 32;
 template <int STD>
 __global__ void BLOOM_BOUNDS up2_kernel(Tables tb, CTex a, uint32_t rx, uint32_t ry, uint32_t point, Up2Plan P,
                                         Tex out) {
@@ -2083,742 +1684,13 @@ __global__ void BLOOM_BOUNDS up2_kernel(Tables tb, CTex a, uint32_t rx, uint32_t
 
 using namespace bh::bloom;
 
+// ---- launchers ---------------------------------------------------------------------------------------
+// In the dry mode of bh_bloom_check (bh_bloom_dry(): the plans are host copies) a launcher returns its form's
+// host check (bh_bloom_plan.cpp) instead of launching.
 namespace {
 dim3 grid_for(uint32_t w, uint32_t h) { return dim3((w + 15u) / 16u, (h + 15u) / 16u); }
+int dry_status(bool ok) { return ok ? 0 : (int)hipErrorInvalidValue; }
 }  // namespace
-
-// Host side of the point-tap proof: the kernels' texcoord / tap / sample_coord arithmetic in IEEE f32
-// (identical on the host: no contraction in this file, and div_core == IEEE division in its domain).
-namespace {
-float h_sample_coord(float u, uint32_t n) {
-    const float t = u * (float)n - 0.5f;
-    return fminf(fmaxf(t, -1.0f), (float)n);
-}
-bool axis_point(uint32_t on, uint32_t tn, float d) {
-    for (uint32_t x = 0; x < on; ++x) {
-        const float t = h_sample_coord(((float)x + 0.5f) / (float)on + d, tn);
-        if (t != floorf(t)) return false;
-    }
-    return true;
-}
-}  // namespace
-
-// One axis of tap i (offset d in texcoord units) over an on-pixel pass of an tn-texel texture: the
-// integer offset o and half flag f with u*tn - 0.5 == x + o + f/2 exactly for every x, else false.
-bool axis_plan(uint32_t on, uint32_t tn, float d, int32_t* o, bool* half) {
-    const float t0 = ((0.5f / (float)on) + d) * (float)tn - 0.5f;
-    const float f0 = floorf(t0);
-    if (!(t0 - f0 == 0.0f || t0 - f0 == 0.5f) || !(fabsf(f0) < 4096.0f)) return false;
-    *o = (int32_t)f0;
-    *half = t0 != f0;
-    const float fr = t0 - f0;
-    for (uint32_t x = 0; x < on; ++x) {
-        const float t = (((float)x + 0.5f) / (float)on + d) * (float)tn - 0.5f;
-        if (t != (float)((int32_t)x + *o) + fr) return false;
-    }
-    return true;
-}
-struct PlanKey { uint32_t ow, oh, tw, th, rx, ry; };
-// The TapPlan of an 8-tap pass (see TapPlan), cached per shape (a few per bloom chain).
-TapPlan tap_plan(uint32_t ow, uint32_t oh, uint32_t tw, uint32_t th, uint32_t rx, uint32_t ry) {
-    static thread_local PlanKey keys[16];
-    static thread_local TapPlan plans[16];
-    static thread_local uint32_t n = 0, next = 0;
-    for (uint32_t i = 0; i < n; ++i)
-        if (keys[i].ow == ow && keys[i].oh == oh && keys[i].tw == tw && keys[i].th == th && keys[i].rx == rx &&
-            keys[i].ry == ry)
-            return plans[i];
-    TapPlan P{};
-    P.valid = 1u;
-    P.lo_x = P.lo_y = 1 << 20;
-    P.hi_x = P.hi_y = -(1 << 20);
-    const float hx = 0.5f / (float)rx, hy = 0.5f / (float)ry;
-    for (int i = 0; i < 8 && P.valid; ++i) {
-        const float du = (hx * (float)((int)((0x12343210u >> (4 * i)) & 15u) - 2)) * 3.0f;
-        const float dv = (hy * (float)((int)((0x10123432u >> (4 * i)) & 15u) - 2)) * 3.0f;
-        bool fx, fy;
-        if (!axis_plan(ow, tw, du, &P.ox[i], &fx) || !axis_plan(oh, th, dv, &P.oy[i], &fy)) {
-            P.valid = 0u;
-            break;
-        }
-        P.hx |= (uint32_t)fx << i;
-        P.hy |= (uint32_t)fy << i;
-        P.lo_x = std::min(P.lo_x, P.ox[i]); P.hi_x = std::max(P.hi_x, P.ox[i] + (int32_t)fx);
-        P.lo_y = std::min(P.lo_y, P.oy[i]); P.hi_y = std::max(P.hi_y, P.oy[i] + (int32_t)fy);
-    }
-    if (!P.valid) P = TapPlan{};
-    keys[next] = {ow, oh, tw, th, rx, ry};
-    plans[next] = P;
-    next = (next + 1u) % 16u;
-    n = n < 16u ? n + 1u : 16u;
-    return P;
-}
-
-// One axis of tap i (offset d in texcoord units) of a 2:1 pass (on == 2 tn): per pixel parity p the
-// integer o[p] and weight f[p] with floor(t) == (x >> 1) + o[p] and t - floor(t) == f[p] for every x,
-// t = u*tn - 0.5 the sampler's unclamped coordinate; [lo, hi] = the pixels whose two texels floor(t),
-// floor(t) + 1 both lie in [0, tn) (there the sampler's clamps change nothing).  False if not so.
-bool axis_plan2(uint32_t on, uint32_t tn, float d, int32_t o[2], float f[2], int32_t* lo, int32_t* hi) {
-    if (on != 2u * tn || tn < 2u) return false;
-    bool seen[2] = {false, false};
-    int32_t ilo = INT_MAX, ihi = -1, count = 0;
-    for (uint32_t x = 0; x < on; ++x) {
-        const float t = (((float)x + 0.5f) / (float)on + d) * (float)tn - 0.5f;
-        const float fl = floorf(t);
-        if (!(fabsf(fl) < 16777216.0f)) return false;
-        const uint32_t p = x & 1u;
-        const int32_t oo = (int32_t)fl - (int32_t)(x >> 1);
-        const float ff = t - fl;
-        if (!seen[p]) {
-            o[p] = oo;
-            f[p] = ff;
-            seen[p] = true;
-        } else if (oo != o[p] || std::memcmp(&ff, &f[p], sizeof ff) != 0) {
-            return false;
-        }
-        if (fl >= 0.0f && fl + 1.0f <= (float)tn - 1.0f) {
-            ilo = std::min(ilo, (int32_t)x);
-            ihi = std::max(ihi, (int32_t)x);
-            ++count;
-        }
-    }
-    if (count != 0 && count != ihi - ilo + 1) return false;  // t is monotone: an interval
-    *lo = count ? ilo : 0;
-    *hi = count ? ihi : -1;
-    return true;
-}
-// The Up2Plan of an up pass (see Up2Plan), cached per shape; valid == 0 when the pass is not 2:1 or a
-// tap's offset or weight varies within a parity class.
-Up2Plan up2_plan(uint32_t ow, uint32_t oh, uint32_t tw, uint32_t th, uint32_t rx, uint32_t ry) {
-    static thread_local PlanKey keys[16];
-    static thread_local Up2Plan plans[16];
-    static thread_local uint32_t n = 0, next = 0;
-    for (uint32_t i = 0; i < n; ++i)
-        if (keys[i].ow == ow && keys[i].oh == oh && keys[i].tw == tw && keys[i].th == th && keys[i].rx == rx &&
-            keys[i].ry == ry)
-            return plans[i];
-    Up2Plan P{};
-    P.valid = 1u;
-    P.x_lo = P.y_lo = 0;
-    P.x_hi = (int32_t)ow - 1;
-    P.y_hi = (int32_t)oh - 1;
-    const float hx = 0.5f / (float)rx, hy = 0.5f / (float)ry;
-    for (int i = 0; i < 8; ++i) {
-        const float du = (hx * (float)((int)((0x12343210u >> (4 * i)) & 15u) - 2)) * 3.0f;
-        const float dv = (hy * (float)((int)((0x10123432u >> (4 * i)) & 15u) - 2)) * 3.0f;
-        int32_t ox[2], oy[2], xl, xh, yl, yh;
-        float fx[2], fy[2];
-        if (!axis_plan2(ow, tw, du, ox, fx, &xl, &xh) || !axis_plan2(oh, th, dv, oy, fy, &yl, &yh)) {
-            P.valid = 0u;
-            break;
-        }
-        for (int p = 0; p < 2; ++p) {
-            P.ox[p][i] = ox[p]; P.fx[p][i] = fx[p];
-            P.oy[p][i] = oy[p]; P.fy[p][i] = fy[p];
-        }
-        if (ox[1] - ox[0] < 0 || ox[1] - ox[0] > 1 || oy[1] - oy[0] < 0 || oy[1] - oy[0] > 1) {  // the quad's 3x3
-            P.valid = 0u;
-            break;
-        }
-        P.x_lo = std::max(P.x_lo, xl); P.x_hi = std::min(P.x_hi, xh);
-        P.y_lo = std::max(P.y_lo, yl); P.y_hi = std::min(P.y_hi, yh);
-    }
-    if (!P.valid) P = Up2Plan{};
-    keys[next] = {ow, oh, tw, th, rx, ry};
-    plans[next] = P;
-    next = (next + 1u) % 16u;
-    n = n < 16u ? n + 1u : 16u;
-    return P;
-}
-
-// Grid of a persistent bloom kernel: `per_cu` resident blocks on every CU of the current device, a
-// multiple of 8 (TileWalk splits the tiles into 8 runs).
-uint32_t persistent_grid(uint32_t per_cu) {
-    int dev = 0, cus = 0;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess ||
-        cus <= 0)
-        cus = 256;
-    return std::max(8u, ((uint32_t)cus * per_cu) & ~7u);
-}
-
-// The standard plan (see quad_tap_std) a runtime plan equals, or 0: A = 12 or 3 for a 2:1 up pass, A =
-// 12 or 48 for a same-size TapPlan pass.  BH_BLOOM_NO_STD (A/B) disables them.
-static const bool g_no_std = std::getenv("BH_BLOOM_NO_STD") != nullptr;
-int std_up2_plan(const Up2Plan& P) {
-    if (!P.valid || g_no_std) return 0;
-    for (int A : {12, 3}) {
-        bool eq = true;
-        for (int i = 0; i < 8 && eq; ++i)
-            for (int p = 0; p < 2 && eq; ++p) {
-                const int vx = A * tap_m(0, i) + (p ? 2 : -2), vy = A * tap_m(1, i) + (p ? 2 : -2);
-                eq = P.ox[p][i] == fdiv8(vx) && P.oy[p][i] == fdiv8(vy) && P.fx[p][i] == (float)fmod8(vx) / 8.0f &&
-                     P.fy[p][i] == (float)fmod8(vy) / 8.0f;
-            }
-        if (eq) return A;
-    }
-    return 0;
-}
-int std_tap_plan(const TapPlan& P) {
-    if (!P.valid || g_no_std) return 0;
-    for (int A : {12, 48}) {
-        bool eq = true;
-        for (int i = 0; i < 8 && eq; ++i) {
-            const int vx = A * tap_m(0, i), vy = A * tap_m(1, i);
-            eq = (fmod8(vx) == 0 || fmod8(vx) == 4) && (fmod8(vy) == 0 || fmod8(vy) == 4) && P.ox[i] == fdiv8(vx) &&
-                 P.oy[i] == fdiv8(vy) && ((P.hx >> i) & 1u) == (fmod8(vx) == 4 ? 1u : 0u) &&
-                 ((P.hy >> i) & 1u) == (fmod8(vy) == 4 ? 1u : 0u);
-        }
-        if (eq) return A;
-    }
-    return 0;
-}
-
-// ---- host-side bound checks of the kernels' index arithmetic ------------------------------------
-// Round 4's memory-access fault ("Bound checks") was a fix-up launch with a count read
-// from a freed plan record.  Every form a launcher can take stages a block's input footprint in an LDS
-// tile and reads it at offsets that a plan (or the kernel's own sampler arithmetic) gives; these checks
-// replay that arithmetic on the host, in the kernels' own f32 operations, per block and per tap along
-// each axis (every footprint here is separable), and require every staged extent to fit its tile, every
-// tile read to fall inside the staged extent, and every plan index and list entry to fall inside its
-// texture.  A separable or same-size plan that fails is never used (the pass takes the general form:
-// bh_bloom_sep_verify / bh_bloom_same_verify, called where the host builds the plans), and in the dry
-// mode of bh_bloom_check every launch of a chain runs its form's check instead of launching (the CPU
-// test over frame sizes and levels, tests/test_bloom_bounds.py).
-namespace {
-struct DryRun {
-    uint64_t launches = 0, checks = 0;
-    std::string fail;
-    std::string plan;  // one line per launch: its form, output size, input size, resolution uniform
-};
-thread_local DryRun* g_dry = nullptr;
-// Test hook (tests/test_bloom_bounds.py): the checks treat every tile as this many entries smaller, so a
-// footprint that fills its tile exactly must be reported -- the checks' own negative test.  0 in use.
-const int g_check_slack = [] {
-    const char* e = std::getenv("BH_BLOOM_CHECK_SLACK");
-    return e ? std::atoi(e) : 0;
-}();
-thread_local std::string* g_why = nullptr;  // where a failing check writes its message (first one kept)
-
-bool chk(bool ok, const char* fmt, ...) __attribute__((format(printf, 2, 3)));
-bool chk(bool ok, const char* fmt, ...) {
-    if (g_dry) ++g_dry->checks;
-    if (ok) return true;
-    std::string* w = g_dry ? &g_dry->fail : g_why;
-    if (w && w->empty()) {
-        char buf[256];
-        va_list ap;
-        va_start(ap, fmt);
-        std::vsnprintf(buf, sizeof buf, fmt, ap);
-        va_end(ap);
-        *w = buf;
-    }
-    return false;
-}
-// the dry run's launch list (bh_bloom_check): "form ow oh tw th rx ry"
-void note_launch(const char* form, uint32_t ow, uint32_t oh, uint32_t tw, uint32_t th, uint32_t rx, uint32_t ry) {
-    if (!g_dry) return;
-    ++g_dry->launches;
-    char buf[128];
-    std::snprintf(buf, sizeof buf, "%s %u %u %u %u %u %u\n", form, ow, oh, tw, th, rx, ry);
-    g_dry->plan += buf;
-}
-float h_texcoord(uint32_t i, uint32_t n) { return ((float)i + 0.5f) / (float)n; }
-// Taps::du / dv on the host: (hx * m) * 3 with hx = 0.5 / res
-float h_tap(uint32_t res, int axis, int i) { return ((0.5f / (float)res) * (float)tap_m(axis, i)) * 3.0f; }
-float h_tap_min(uint32_t res, int axis) { return h_tap(res, axis, axis ? 6 : 0); }
-float h_tap_max(uint32_t res, int axis) { return h_tap(res, axis, axis ? 2 : 4); }
-int32_t h_floor(float t) { return (int32_t)floorf(t); }
-
-// One axis of up_sep_kernel (B = 16) / up_sepq_kernel (B = 32): the footprint the kernel derives from the
-// sampler arithmetic of its first and last column, c = hi - lo + 2 entries (floor .. floor + 1), which the
-// kernel cuts to FP -- the cut must never happen -- and for every tap and column of the block the plan's
-// floor f with both of its texels f - lo, f + 1 - lo inside those c entries.  e: the axis's [8][on] entries.
-// off: the block grid's origin offset (blocks start at B k - off; the quad kernel's org), own: the block's own
-// columns must lie in its footprint too (the FIX epilogue reads them from the tile).
-bool sep_axis_ok(const SepEntry* e, uint32_t on, uint32_t tn, uint32_t res, int axis, uint32_t B, int FP, uint32_t off = 0,
-                 bool own = false) {
-    const float dmin = h_tap_min(res, axis), dmax = h_tap_max(res, axis);
-    if (!chk(off < B && off % 2u == 0u, "block grid origin %u for %u-pixel blocks", off, B)) return false;
-    for (int64_t bs = -(int64_t)off; bs < (int64_t)on; bs += B) {
-        const uint32_t b = (uint32_t)std::max<int64_t>(bs, 0);
-        const uint32_t l = (uint32_t)std::min<int64_t>(bs + B - 1, (int64_t)on - 1);
-        const int32_t lo = h_floor(h_sample_coord(h_texcoord(b, on) + dmin, tn));
-        const int32_t hi = h_floor(h_sample_coord(h_texcoord(l, on) + dmax, tn));
-        const int32_t c = hi - lo + 2;
-        if (!chk(c >= 2 && c <= FP - g_check_slack, "separable %s footprint of block %u: %d entries, tile side %d", axis ? "row" : "column",
-                 b, c, FP))
-            return false;
-        if (own && !chk((int32_t)b - lo >= 0 && (int32_t)l - lo <= c - 1,
-                        "in-block fix: %s block %u..%u outside its footprint %d + %d", axis ? "row" : "column", b, l, lo, c))
-            return false;
-        for (int i = 0; i < 8; ++i)
-            for (uint32_t x = b; x <= l; ++x) {
-                const SepEntry& s = e[(size_t)i * on + x];
-                if (!chk(s.f >= -1 && s.f <= (int32_t)tn, "separable plan floor %d outside [-1, %u] (tap %d, %s %u)", s.f,
-                         tn, i, axis ? "row" : "column", x) ||
-                    !chk(s.f - lo >= 0 && s.f + 1 - lo <= c - 1,
-                         "separable tap %d of %s %u reads entries %d..%d of a %d-entry footprint", i, axis ? "row" : "column",
-                         x, s.f - lo, s.f + 1 - lo, c) ||
-                    !chk(s.fa >= 0.0f && s.fa <= 1.0f && s.ia == 1.0f - s.fa, "separable plan weight %g at %s %u", (double)s.fa,
-                         axis ? "row" : "column", x))
-                    return false;
-            }
-    }
-    return true;
-}
-// A tile of FP rows at stride FS, with a row-pair shift of (ly + p) >> 1 entries when shift = p + 1 (the quad
-// tiles: p = 0; bloom_yq_kernel: p up to 1): its largest entry for rows and columns below FP must stay below
-// the declared size.
-bool tile_ok(int FP, int FS, int shift, int size) {
-    const int last = (FP - 1) * FS + (shift ? (FP - 1 + shift - 1) >> 1 : 0) + (FP - 1);
-    return chk(FS >= FP && last < size, "tile FP %d stride %d: last entry %d of %d", FP, FS, last, size);
-}
-
-// One axis of with_source's (and up2_kernel's outer blocks') fallback: the kernel's tap_span over a block of
-// B pixels, and, when it fits FP, every tap's two clamped texels inside it.
-bool span_axis_ok(uint32_t on, uint32_t tn, uint32_t res, int axis, uint32_t B, int FP) {
-    const float dmin = h_tap_min(res, axis), dmax = h_tap_max(res, axis);
-    const int32_t hm = (int32_t)tn - 1;
-    auto clampi_h = [&](int32_t v) { return std::min(std::max(v, 0), hm); };
-    for (uint32_t b = 0; b < on; b += B) {
-        const uint32_t l = std::min(b + B - 1u, on - 1u);
-        const int32_t lo = clampi_h(h_floor(h_sample_coord(h_texcoord(b, on) + dmin, tn)));
-        const int32_t hi = clampi_h(h_floor(h_sample_coord(h_texcoord(l, on) + dmax, tn)) + 1);
-        const int32_t n = hi - lo + 1;
-        if (n > FP) continue;  // block-uniform: this block reads global memory through clamped indices
-        if (!chk(n <= FP - g_check_slack, "staged span of %s block %u: %d texels, tile side %d", axis ? "row" : "column",
-                 b, n, FP))
-            return false;
-        for (int i = 0; i < 8; ++i)
-            for (uint32_t x = b; x <= l; ++x) {
-                const int32_t f = h_floor(h_sample_coord(h_texcoord(x, on) + h_tap(res, axis, i), tn));
-                const int32_t x0 = clampi_h(f), x1 = clampi_h(f + 1);
-                if (!chk(x0 >= lo && x1 <= hi, "staged tap %d of %s %u reads texels %d..%d of span %d..%d", i,
-                         axis ? "row" : "column", x, x0, x1, lo, hi))
-                    return false;
-            }
-    }
-    return true;
-}
-
-// One axis of a TapPlan form over blocks of B pixels and a tile of side FP: the kernel takes the form when
-// hi - lo + B <= FP (launch-uniform), and then a pixel p of a block reads entries p - b + (o_i - lo) and
-// + half_i; otherwise the span fallback.
-bool tapplan_axis_ok(const TapPlan& P, uint32_t on, uint32_t tn, uint32_t res, int axis, uint32_t B, int FP) {
-    const int32_t lo = axis ? P.lo_y : P.lo_x, hi = axis ? P.hi_y : P.hi_x;
-    if (!P.valid || hi - lo + (int32_t)B > FP) return span_axis_ok(on, tn, res, axis, B, FP);
-    if (!chk(hi - lo + (int32_t)B <= FP - g_check_slack, "tap plan footprint %d of a %d tile", hi - lo + (int32_t)B, FP))
-        return false;
-    for (int i = 0; i < 8; ++i) {
-        const int32_t o = axis ? P.oy[i] : P.ox[i];
-        const int32_t h = (int32_t)(((axis ? P.hy : P.hx) >> i) & 1u);
-        if (!chk(o - lo >= 0 && (int32_t)B - 1 + o + h - lo <= hi - lo + (int32_t)B - 1,
-                 "tap plan tap %d offset %d (+%d) outside the footprint %d..%d", i, o, h, lo, hi))
-            return false;
-    }
-    return true;
-}
-
-// One axis of up2_kernel: blocks of 32 pixels staged when the span fits FP_UPQ; inside P's interior the quad
-// reads texels (x >> 1) + o[0] .. (x >> 1) + o[1] + 1 of every tap, which must lie in the span.
-bool up2_axis_ok(const Up2Plan& P, uint32_t on, uint32_t tn, uint32_t res, int axis, int FP) {
-    if (!span_axis_ok(on, tn, res, axis, 32u, FP)) return false;
-    const float dmin = h_tap_min(res, axis), dmax = h_tap_max(res, axis);
-    const int32_t hm = (int32_t)tn - 1;
-    const int32_t ilo = axis ? P.y_lo : P.x_lo, ihi = axis ? P.y_hi : P.x_hi;
-    for (uint32_t b = 0; b < on; b += 32u) {
-        const uint32_t l = std::min(b + 31u, on - 1u);
-        const int32_t lo = std::min(std::max(h_floor(h_sample_coord(h_texcoord(b, on) + dmin, tn)), 0), hm);
-        const int32_t hi = std::min(std::max(h_floor(h_sample_coord(h_texcoord(l, on) + dmax, tn)) + 1, 0), hm);
-        if (hi - lo + 1 > FP || (int32_t)b < ilo || (int32_t)b + 31 > ihi) continue;  // not an inner block
-        for (int i = 0; i < 8; ++i) {
-            const int32_t o0 = axis ? P.oy[0][i] : P.ox[0][i], o1 = axis ? P.oy[1][i] : P.ox[1][i];
-            for (uint32_t x = b; x <= l; x += 2u) {
-                const int32_t first = (int32_t)(x >> 1) + o0, last = (int32_t)(x >> 1) + o1 + 1;
-                if (!chk(first >= lo && last <= hi && first >= 0 && last <= hm,
-                         "2:1 quad tap %d of %s %u reads texels %d..%d of span %d..%d", i, axis ? "row" : "column", x,
-                         first, last, lo, hi))
-                    return false;
-            }
-        }
-    }
-    return true;
-}
-
-// The same-size plan (bh_bloom_same_plan) and its list of inexact columns, then rows: every texel index
-// inside the frame, weights in [0, 1], and the list exactly the columns / rows of nonzero weight, ascending
-// (the fused epilogues skip those pixels and fixup_kernel recomputes them: a missing entry leaves a pixel
-// unwritten, an extra one writes it twice with the same value).
-bool same_ok(uint32_t w, uint32_t h, const uint32_t* plan, const uint32_t* list, uint32_t nc, uint32_t nr,
-             bool with_list = true) {
-    if (!chk(nc <= w && nr <= h, "same-size plan: %u inexact columns of %u, %u rows of %u", nc, w, nr, h)) return false;
-    for (int axis = 0; axis < 2; ++axis) {
-        const uint32_t n = axis ? h : w, base = axis ? w : 0u, cnt = axis ? nr : nc;
-        const uint32_t* L = with_list ? list + (axis ? nc : 0u) : nullptr;
-        uint32_t k = 0;
-        for (uint32_t x = 0; x < n; ++x) {
-            const uint32_t e = plan[2u * (base + x)];
-            float wgt;
-            std::memcpy(&wgt, &plan[2u * (base + x) + 1u], 4);
-            const uint32_t x0 = e & 0xFFFFu, x1 = e >> 16;
-            if (!chk(x0 < n && x1 < n && wgt >= 0.0f && wgt <= 1.0f, "same-size plan %s %u: texels %u, %u, weight %g of %u",
-                     axis ? "row" : "column", x, x0, x1, (double)wgt, n) ||
-                !chk(wgt != 0.0f || x0 == x, "same-size plan: exact %s %u samples texel %u", axis ? "row" : "column", x, x0))
-                return false;
-            if (wgt != 0.0f && with_list) {
-                if (!chk(k < cnt && L[k] == x, "same-size list: %s %u missing", axis ? "row" : "column", x)) return false;
-                ++k;
-            }
-        }
-        if (with_list && !chk(k == cnt, "same-size list: %u %s entries for %u inexact", cnt, axis ? "row" : "column", k)) return false;
-    }
-    return true;
-}
-// Whether inexact column (row) x of an n-pixel axis samples a texel outside its 32-pixel block of a grid at
-// origin off: such a column's pixels are the fix-up pass's, the others up_sepq_kernel's in-block fix (FIX).
-// reach2 (the final epilogue's fix): also when a sampled texel is itself inexact and samples outside the block.
-bool same_crosses(const uint32_t* plan, uint32_t base, uint32_t x, uint32_t off, bool reach2 = false) {
-    const uint32_t e = plan[2u * (base + x)], wbits = plan[2u * (base + x) + 1u];
-    if (wbits == 0u) return false;  // exact: its own texel (same_ok)
-    const uint32_t blk = (x + off) / 32u;
-    const uint32_t t[2] = {e & 0xFFFFu, e >> 16};  // both of nonzero weight (0 < w < 1)
-    for (uint32_t u : t) {
-        if ((u + off) / 32u != blk) return true;
-        if (reach2 && plan[2u * (base + u) + 1u] != 0u) {
-            const uint32_t eu = plan[2u * (base + u)];
-            if (((eu & 0xFFFFu) + off) / 32u != blk || ((eu >> 16) + off) / 32u != blk) return true;
-        }
-    }
-    return false;
-}
-// The residual list at origin org: the crossing columns, then rows, ascending -- exactly what it must hold
-bool residual_ok(uint32_t w, uint32_t h, const uint32_t* plan, const uint32_t* list, uint32_t nc, uint32_t nr, uint32_t org,
-                 bool reach2) {
-    if (!chk(nc <= w && nr <= h && (org & 0xFFFFu) < 32u && (org >> 16) < 32u && org % 2u == 0u && (org >> 16) % 2u == 0u,
-             "residual list: %u columns of %u, %u rows of %u, origin %u,%u", nc, w, nr, h, org & 0xFFFFu, org >> 16))
-        return false;
-    for (int axis = 0; axis < 2; ++axis) {
-        const uint32_t n = axis ? h : w, base = axis ? w : 0u, cnt = axis ? nr : nc, off = axis ? org >> 16 : org & 0xFFFFu;
-        const uint32_t* L = list + (axis ? nc : 0u);
-        uint32_t k = 0;
-        for (uint32_t x = 0; x < n; ++x)
-            if (same_crosses(plan, base, x, off, reach2)) {
-                if (!chk(k < cnt && L[k] == x, "residual list: crossing %s %u missing", axis ? "row" : "column", x)) return false;
-                ++k;
-            }
-        if (!chk(k == cnt, "residual list: %u %s entries for %u crossing", cnt, axis ? "row" : "column", k)) return false;
-    }
-    return true;
-}
-// The fix-up records of a list (bh_bloom_fixup_records): entry k's column (row) and the plan entries of it and
-// of its clamped neighbours, exactly as the kernel would read them from the plan.
-bool records_ok(uint32_t w, uint32_t h, const uint32_t* plan, const uint32_t* list, uint32_t nc, uint32_t nr,
-                const uint32_t* rec) {
-    for (uint32_t k = 0; k < nc + nr; ++k) {
-        const uint32_t n = k < nc ? w : h, base = k < nc ? 0u : w, u = list[k];
-        const uint32_t* r = rec + 8u * k;
-        if (!chk(r[0] == u && u < n, "fix-up record %u names %u, its list %u", k, r[0], u)) return false;
-        const uint32_t nb[3] = {u ? u - 1u : 0u, u, std::min(u + 1u, n - 1u)};
-        for (int t = 0; t < 3; ++t)
-            if (!chk(r[1 + 2 * t] == plan[2u * (base + nb[t])] && r[2 + 2 * t] == plan[2u * (base + nb[t]) + 1u],
-                     "fix-up record %u: plan entry %u differs", k, nb[t]))
-                return false;
-    }
-    return true;
-}
-// The inexact columns of a same-size plan (its list's column count)
-uint32_t n_inexact(uint32_t w, const uint32_t* plan) {
-    uint32_t n = 0;
-    for (uint32_t x = 0; x < w; ++x) n += plan[2u * x + 1u] != 0u;
-    return n;
-}
-// The column records' word 7: 1 + the column's strip column (fixup_gather_kernel's qx)
-bool strip_records_ok(const uint32_t* list, uint32_t nc, const uint32_t* stc, const uint32_t* rec) {
-    for (uint32_t k = 0; k < nc; ++k)
-        if (!chk(rec[8u * k + 7u] == stc[list[k]], "fix-up record %u: strip column %u, table %u", k, rec[8u * k + 7u], stc[list[k]]))
-            return false;
-    return true;
-}
-// The fix-up's column strips (bh_bloom_strip_table, up_sepq_kernel's STRIPS epilogue, fixup_gather_kernel):
-// stc[c] is 0 or 1 + column c's strip column, distinct and below tw, so each strip word has one writer; and
-// every texel a column lane of inexact column x reads (its own sample and F's at the sample's texels) lies in
-// x's strip at the same offset: stc[c] - stc[x] == c - x.
-bool strip_ok(uint32_t w, uint32_t h, const uint32_t* plan, const uint32_t* list, uint32_t nc, const uint32_t* stc,
-              uint32_t tw) {
-    if (!chk(tw > 0u && tw <= w && nc <= w, "strips: %u strip columns, %u inexact columns of %u", tw, nc, w)) return false;
-    std::vector<uint8_t> seen(tw, 0u);
-    for (uint32_t c = 0; c < w; ++c) {
-        if (stc[c] == 0u) continue;
-        const uint32_t q = stc[c] - 1u;
-        if (!chk(q < tw && !seen[q], "strip table: column %u -> strip column %u of %u", c, q, tw)) return false;
-        seen[q] = 1u;
-    }
-    for (uint32_t k = 0; k < nc; ++k) {
-        const uint32_t x = list[k];
-        if (!chk(x < w && stc[x] != 0u, "strips: inexact column %u outside every strip", x)) return false;
-        auto same_strip = [&](uint32_t c) { return c < w && stc[c] != 0u && (int64_t)stc[c] - stc[x] == (int64_t)c - x; };
-        const uint32_t e = plan[2u * x], ex = plan[2u * x + 1u];
-        const uint32_t px[2] = {e & 0xFFFFu, e >> 16};
-        for (int t = 0; t < (ex != 0u ? 2 : 1); ++t) {
-            const uint32_t ep = plan[2u * px[t]], wp = plan[2u * px[t] + 1u];
-            if (!chk(same_strip(px[t]) && same_strip(ep & 0xFFFFu) && (wp == 0u || same_strip(ep >> 16)),
-                     "strips: column %u reads texel %u (samples %u, %u) outside its strip", x, px[t], ep & 0xFFFFu, ep >> 16))
-                return false;
-        }
-    }
-    (void)h;
-    return true;
-}
-}  // namespace
-
-// The strip table of a same-size plan's nc inexact columns (list, ascending): the columns within 2 of an
-// inexact column, merged into contiguous runs (inexact columns cluster), numbered left to right: stc[c] = 1 +
-// c's strip column, 0 outside.  Returns the number of strip columns (0: no inexact column).
-extern "C" __attribute__((visibility("hidden"))) uint32_t bh_bloom_strip_table(uint32_t w, const uint32_t* list, uint32_t nc,
-                                                                             uint32_t* stc) {
-    std::fill(stc, stc + w, 0u);
-    uint32_t tw = 0;
-    for (uint32_t k = 0; k < nc; ++k) {
-        const int64_t lo = std::max<int64_t>((int64_t)list[k] - 2, 0), hi = std::min<int64_t>((int64_t)list[k] + 2, (int64_t)w - 1);
-        for (int64_t c = lo; c <= hi; ++c)
-            if (stc[c] == 0u) stc[c] = ++tw;
-    }
-    return tw;
-}
-
-// The fix-up records of a list of n_cols columns then n_rows rows into out (8 words per entry, see
-// fixup_gather_kernel).
-extern "C" __attribute__((visibility("hidden"))) void bh_bloom_fixup_records(uint32_t w, uint32_t h, const uint32_t* plan,
-                                                                           const uint32_t* list, uint32_t nc, uint32_t nr,
-                                                                           uint32_t* out) {
-    for (uint32_t k = 0; k < nc + nr; ++k) {
-        const uint32_t n = k < nc ? w : h, base = k < nc ? 0u : w, u = std::min(list[k], n - 1u);
-        const uint32_t nb[3] = {u ? u - 1u : 0u, u, std::min(u + 1u, n - 1u)};
-        uint32_t* r = out + 8u * k;
-        r[0] = list[k];
-        for (int t = 0; t < 3; ++t) {
-            r[1 + 2 * t] = plan[2u * (base + nb[t])];
-            r[2 + 2 * t] = plan[2u * (base + nb[t]) + 1u];
-        }
-        r[7] = 0u;
-    }
-}
-
-// The quad grid's origin for the in-block fix of a same-size plan (bh_bloom_same_plan): per axis the even
-// offset in [0, 32) with the fewest inexact columns (rows) whose sample crosses a block edge (ties: the
-// smallest), as org = ox | oy << 16; the crossing ones into cols / rows when given.  An offset may add a
-// column (row) of blocks: at 1920 x 1080 offset 8 (61 block columns, no residual) measured 0.1234 ms per
-// chain against 0.1265 for offset 0 (60 columns and a fix-up launch over the one crossing column)
-// (profiles/r05/bloom_org/).  BH_BLOOM_ORG_KEEP (A/B): only offsets that keep the block count.
-extern "C" __attribute__((visibility("hidden"))) uint32_t bh_bloom_same_org(uint32_t w, uint32_t h, const uint32_t* plan,
-                                                                          std::vector<uint32_t>* cols,
-                                                                          std::vector<uint32_t>* rows,
-                                                                          std::vector<uint32_t>* cols2,
-                                                                          std::vector<uint32_t>* rows2) {
-    static const bool grow = std::getenv("BH_BLOOM_ORG_KEEP") == nullptr;
-    uint32_t org = 0;
-    for (int axis = 0; axis < 2; ++axis) {
-        const uint32_t n = axis ? h : w, base = axis ? w : 0u;
-        // fewest crossings of the final epilogue's fix (reach 2), then of the Y epilogue's, then the offset
-        uint64_t best_n = UINT64_MAX;
-        uint32_t best = 0;
-        const uint32_t blocks = (n + 31u) / 32u;
-        for (uint32_t off = 0; off < 32u && best_n != 0u; off += 2u) {
-            if ((n + off + 31u) / 32u != blocks && !grow) break;  // offsets only grow the count
-            uint64_t c2 = 0, c1 = 0;
-            for (uint32_t x = 0; x < n; ++x) {
-                c2 += same_crosses(plan, base, x, off, true) ? 1u : 0u;
-                c1 += same_crosses(plan, base, x, off) ? 1u : 0u;
-            }
-            if ((c2 << 32 | c1) < best_n) { best_n = c2 << 32 | c1; best = off; }
-        }
-        org |= best << (axis ? 16 : 0);
-        for (int r = 0; r < 2; ++r) {
-            std::vector<uint32_t>* out = r ? (axis ? rows2 : cols2) : (axis ? rows : cols);
-            if (!out) continue;
-            out->clear();
-            for (uint32_t x = 0; x < n; ++x)
-                if (same_crosses(plan, base, x, best, r == 1)) out->push_back(x);
-        }
-    }
-    return org;
-}
-
-// whether bh_launch_bloom_sep runs a plan of these extents with the quad kernel (the in-block fix's form)
-extern "C" __attribute__((visibility("hidden"))) bool bh_bloom_sep_fix_ok(int ext, uint32_t ow, uint32_t oh, uint32_t epi);
-
-// The separable up pass's launch form for a plan's extents (low 16 bits: 16x16 blocks, high: 32x32): the
-// quad kernel when its footprint fits a 28 / 40 / 60 tile, else the one-pixel kernel at 24 / 44, else none
-// (FP 0: the general pass).  One definition for the launcher and its check.
-struct SepForm {
-    int FP = 0, FS = 0;
-    bool quad = false, raw = false;
-};
-static const bool g_no_sepq = std::getenv("BH_BLOOM_NO_SEPQ") != nullptr;  // A/B: the one-pixel kernel
-static uint32_t env_u32(const char* name) {
-    const char* e = std::getenv(name);
-    return e ? (uint32_t)std::strtoul(e, nullptr, 10) : 0u;
-}
-static SepForm sep_form(int ext, uint32_t ow, uint32_t oh) {
-    // A/B: BH_BLOOM_SEPQ_MIN_BLOCKS=n runs a pass of fewer than n quad blocks (32x32 pixels) with the
-    // one-pixel kernel (four times the blocks) when its footprint fits; BH_BLOOM_SEPQ_RAW bit 0 / bit 1
-    // stage the 28 / 40 tiles as raw words too (decoded per read)
-    static const uint32_t min_blocks = env_u32("BH_BLOOM_SEPQ_MIN_BLOCKS"), raw_mask = env_u32("BH_BLOOM_SEPQ_RAW");
-    const int e16 = ext & 0xFFFF, e32 = (ext >> 16) & 0xFFFF;
-    const int one = e16 <= 0 ? 0 : e16 <= 24 ? 24 : e16 <= 44 ? 44 : 0;
-    int q = g_no_sepq || e32 <= 0 ? 0 : e32 <= 28 ? 28 : e32 <= 40 ? 40 : e32 <= 60 ? 60 : 0;
-    const uint64_t qblocks = (uint64_t)((ow + 31u) / 32u) * ((oh + 31u) / 32u);
-    if (qblocks < min_blocks && one != 0) q = 0;
-    SepForm f;
-    if (q != 0) {
-        f.quad = true;
-        f.FP = q;
-        f.raw = q == 60 || (q == 28 && (raw_mask & 1u)) || (q == 40 && (raw_mask & 2u));
-        f.FS = f.raw ? (q == 60 ? SEPQ_FS60 : 48) : (q == 28 ? 32 : 40);
-    } else if (one != 0) {
-        f.FP = one;
-        f.raw = one == 44;
-        f.FS = f.raw ? sep_stride<44, true>() : sep_stride<24, false>();
-    }
-    return f;
-}
-
-// A/B: BH_BLOOM_CAP_<PLAIN|Y|FINAL>=n caps the quad pass of that epilogue at n blocks per CU (dynamic LDS
-// padding): a launch of 1.33 rounds of resident waves may finish sooner as 2 full rounds of less contended ones
-static size_t sepq_cap_pad(const void* fn, uint32_t epi) {
-    static const int cap[3] = {(int)env_u32("BH_BLOOM_CAP_PLAIN"), (int)env_u32("BH_BLOOM_CAP_Y"),
-                               (int)env_u32("BH_BLOOM_CAP_FINAL")};
-    const int n = epi < 3u ? cap[epi] : 0;
-    if (n <= 0) return 0;
-    hipFuncAttributes at{};
-    if (hipFuncGetAttributes(&at, fn) != hipSuccess) return 0;
-    const long want = 163840L / (n + 1) + 1 - (long)at.sharedSizeBytes;  // n + 1 blocks no longer fit
-    return want > 0 ? (size_t)want : 0;
-}
-
-// whether bh_launch_bloom_sep runs a plan of these extents with epilogue epi in the in-block fix form: the
-// quad kernel, and for the final epilogue a tile large enough for its words (sepq_fix2_fits)
-static bool sep_fix_form(const SepForm& f, uint32_t epi) {
-    if (!f.quad) return false;
-    if (epi == EPI_Y) return true;
-    const size_t tile = (f.raw ? 4u : 16u) * (size_t)(f.FP * f.FS + f.FP / 2);
-    return epi == EPI_FINAL && tile >= 3u * FIX_WORDS * 4u;
-}
-extern "C" __attribute__((visibility("hidden"))) bool bh_bloom_sep_fix_ok(int ext, uint32_t ow, uint32_t oh, uint32_t epi) {
-    return sep_fix_form(sep_form(ext, ow, oh), epi);
-}
-
-// bh_bloom_sep_plan's plan (host copy `plan`, extents `ext`) checked for the form bh_launch_bloom_sep takes:
-// false (and the reason in *why) when any block's footprint exceeds its tile or any read leaves it.
-extern "C" __attribute__((visibility("hidden"))) bool bh_bloom_sep_verify(uint32_t ow, uint32_t oh, uint32_t tw,
-                                                                        uint32_t th, uint32_t rx, uint32_t ry,
-                                                                        const uint32_t* plan, int ext, uint32_t org, bool fix,
-                                                                        std::string* why) {
-    std::string* prev = g_why;
-    g_why = why;
-    const SepForm f = sep_form(ext, ow, oh);
-    const SepEntry* e = reinterpret_cast<const SepEntry*>(plan);
-    const uint32_t B = f.quad ? 32u : 16u;
-    const int size = f.quad ? f.FP * f.FS + f.FP / 2 : f.FP * f.FS;
-    // the one-pixel kernel has no grid origin and no in-block fix
-    const uint32_t ox = f.quad ? org & 0xFFFFu : 0u, oy = f.quad ? org >> 16 : 0u;
-    const bool own = fix && f.quad;
-    // FP == 0: no staged form fits these extents, and the launcher refuses the plan (the general pass runs)
-    const bool ok = f.FP == 0 || (tile_ok(f.FP, f.FS, f.quad ? 1 : 0, size) && sep_axis_ok(e, ow, tw, rx, 0, B, f.FP, ox, own) &&
-                                  sep_axis_ok(e + 8u * (size_t)ow, oh, th, ry, 1, B, f.FP, oy, own));
-    g_why = prev;
-    return ok;
-}
-extern "C" __attribute__((visibility("hidden"))) bool bh_bloom_same_verify(uint32_t w, uint32_t h, const uint32_t* plan,
-                                                                         uint32_t nc, uint32_t nr, std::string* why) {
-    std::string* prev = g_why;
-    g_why = why;
-    const bool ok = same_ok(w, h, plan, plan + 2u * ((size_t)w + h), nc, nr);
-    g_why = prev;
-    return ok;
-}
-// The fix-up records of a list (records_ok) and, when stc != nullptr, the column strips of the plan's full list
-// with the column records' word 7 (strip_ok, strip_records_ok): what bh_bloom_check's dry run checks at each
-// launch, run by sep_plan on every real plan before it is uploaded.
-extern "C" __attribute__((visibility("hidden"))) bool bh_bloom_records_verify(uint32_t w, uint32_t h, const uint32_t* plan,
-                                                                            const uint32_t* list, uint32_t nc, uint32_t nr,
-                                                                            const uint32_t* rec, const uint32_t* stc,
-                                                                            uint32_t strip_w, std::string* why) {
-    std::string* prev = g_why;
-    g_why = why;
-    const bool ok = records_ok(w, h, plan, list, nc, nr, rec) &&
-                    (!stc || (strip_ok(w, h, plan, list, nc, stc, strip_w) && strip_records_ok(list, nc, stc, rec)));
-    g_why = prev;
-    return ok;
-}
-// Dry mode (bh_bloom_check): while it is on, the launchers below check their launch's form on the host and
-// return without launching; the plan pointers they receive are host copies.
-extern "C" __attribute__((visibility("hidden"))) void bh_bloom_dry_begin(void) {
-    delete g_dry;
-    g_dry = new DryRun();
-}
-extern "C" __attribute__((visibility("hidden"))) bool bh_bloom_dry_end(uint64_t* launches, uint64_t* checks,
-                                                                     std::string* fail, std::string* plan) {
-    if (!g_dry) return false;
-    if (launches) *launches = g_dry->launches;
-    if (checks) *checks = g_dry->checks;
-    if (fail) *fail = g_dry->fail;
-    if (plan) *plan = g_dry->plan;
-    const bool ok = g_dry->fail.empty();
-    delete g_dry;
-    g_dry = nullptr;
-    return ok;
-}
-extern "C" __attribute__((visibility("hidden"))) bool bh_bloom_dry(void) { return g_dry != nullptr; }
-
-// The separable plan of an 8-tap pass (see SepEntry / up_sep_kernel): 8 * (ow + oh) entries of 4 words
-// into `outp` (per tap and column, then per tap and row), from the kernel's own f32 arithmetic: texcoord
-// (x + 0.5) / n (the division core is IEEE division in its domain), the tap offset, sample_coord and
-// floor.  Returns the largest 16x16 block footprint along either axis (the staged tile's side of
-// up_sep_kernel) in the low 16 bits and the largest 32x32 block footprint (up_sepq_kernel, its grid at
-// origin org) in the high ones, or -1 (texture sides above 65535).
-extern "C" __attribute__((visibility("hidden"))) int bh_bloom_sep_plan(uint32_t ow, uint32_t oh, uint32_t tw,
-                                                                     uint32_t th, uint32_t rx, uint32_t ry,
-                                                                     uint32_t* outp, uint32_t org) {
-    if (tw > 65535u || th > 65535u || tw == 0u || th == 0u || ow == 0u || oh == 0u) return -1;
-    const float hx = 0.5f / (float)rx, hy = 0.5f / (float)ry;
-    auto axis = [](uint32_t on, uint32_t tn, float d, uint32_t x, uint32_t* o) {
-        const float t = h_sample_coord(((float)x + 0.5f) / (float)on + d, tn);
-        const float f = floorf(t), fa = t - f, ia = 1.0f - fa;
-        const int32_t fi = (int32_t)f;
-        std::memcpy(&o[0], &fi, 4);
-        std::memcpy(&o[1], &fa, 4);
-        std::memcpy(&o[2], &ia, 4);
-        o[3] = 0u;
-    };
-    auto fl = [&](size_t e) { int32_t v; std::memcpy(&v, outp + 4u * e, 4); return v; };
-    for (int i = 0; i < 8; ++i) {
-        const float du = (hx * (float)((int)((0x12343210u >> (4 * i)) & 15u) - 2)) * 3.0f;
-        const float dv = (hy * (float)((int)((0x10123432u >> (4 * i)) & 15u) - 2)) * 3.0f;
-        for (uint32_t x = 0; x < ow; ++x) axis(ow, tw, du, x, outp + 4u * ((size_t)i * ow + x));
-        for (uint32_t y = 0; y < oh; ++y) axis(oh, th, dv, y, outp + 4u * (8u * (size_t)ow + (size_t)i * oh + y));
-    }
-    int ext[2] = {0, 0};  // 16- and 32-pixel blocks
-    for (int q = 0; q < 2; ++q) {
-        const uint32_t B = q ? 32u : 16u;
-        for (int ax = 0; ax < 2; ++ax) {
-            const uint32_t n = ax ? oh : ow;
-            const size_t base = ax ? 8u * (size_t)ow : 0u;
-            const int64_t off = q ? (ax ? org >> 16 : org & 0xFFFFu) : 0;
-            for (int64_t bs = -off; bs < (int64_t)n; bs += B) {
-                const uint32_t b = (uint32_t)std::max<int64_t>(bs, 0);
-                const uint32_t l = (uint32_t)std::min<int64_t>(bs + B - 1, (int64_t)n - 1);
-                int32_t lo = INT_MAX, hi = INT_MIN;
-                for (int i = 0; i < 8; ++i) {
-                    lo = std::min(lo, fl(base + (size_t)i * n + b));
-                    hi = std::max(hi, fl(base + (size_t)i * n + l));
-                }
-                ext[q] = std::max(ext[q], hi - lo + 2);
-            }
-        }
-    }
-    return std::min(ext[0], 0x7FFF) | std::min(ext[1], 0x7FFF) << 16;  // up_sep_kernel's | up_sepq_kernel's
-}
 
 extern "C" __attribute__((visibility("hidden"))) int bh_launch_bloom_sep(const float* lut, const float* enc,
                                                                         const uint8_t* buckets, const uint32_t* codes,
@@ -2827,70 +1699,46 @@ extern "C" __attribute__((visibility("hidden"))) int bh_launch_bloom_sep(const f
                                                                         const uint32_t* sep, int ext, uint32_t epi,
                                                                         const uint32_t* own0, const uint32_t* own1,
                                                                         const uint32_t* same, uint32_t* out, uint32_t* aux,
-                                                                        uint32_t ow, uint32_t oh, uint32_t org, bool fix,
+                                                                        uint32_t ow, uint32_t oh,
                                                                         const uint32_t* stc, uint32_t* strips,
                                                                         uint32_t strip_w, bool* strips_written,
                                                                         hipStream_t s) {
     if (strips_written) *strips_written = false;
-    const SepForm f = sep_form(ext, ow, oh);
+    const SepForm f = sep_form(ext);
     if (f.FP == 0 || !sep) return (int)hipErrorInvalidValue;
-    // the grid origin and the in-block fix are the quad kernel's (the fix with the Y or final epilogue)
-    if (!f.quad) org = 0u;
-    fix = fix && sep_fix_form(f, epi);
-    // the fix-up's column strips: the quad kernel's final epilogue without its in-block fix
-    const bool st = stc && f.quad && epi == EPI_FINAL && !fix && same;
-    if (g_dry) {  // the plan is a host copy: check the form's every read instead of launching
-        char form[32];
-        std::snprintf(form, sizeof form, "%s%d%s/%u%s", f.quad ? "sepq" : "sep", f.FP, f.raw ? "r" : "", epi, fix ? "f" : "");
-        note_launch(form, ow, oh, aw, ah, rx, ry);
-        if (st && !strip_ok(ow, oh, same, same + 2u * ((size_t)ow + oh), n_inexact(ow, same), stc, strip_w))
-            return (int)hipErrorInvalidValue;
-        if (strips_written) *strips_written = st;
-        return bh_bloom_sep_verify(ow, oh, aw, ah, rx, ry, sep, ext, org, fix, nullptr) &&
-                       (epi == EPI_PLAIN || chk(same != nullptr, "separable epilogue without a same-size plan"))
-                   ? 0
-                   : (int)hipErrorInvalidValue;
+    // the fix-up's column strips: the quad kernel's final epilogue
+    const bool st = stc && f.quad && epi == EPI_FINAL && same;
+    const uint32_t* const STC = st ? stc : nullptr;
+    if (bh_bloom_dry()) {
+        const bool ok = check_sep_launch(ow, oh, aw, ah, rx, ry, sep, ext, epi, same, STC, strip_w);
+        if (strips_written) *strips_written = st && ok;
+        return dry_status(ok);
     }
     if (st && !strips) return (int)hipErrorInvalidValue;
-    const uint32_t* const STC = st ? stc : nullptr;
     const Tables tb{lut, enc, buckets, codes};
     const CTex A{a, aw, ah}, O0{own0 ? own0 : a, ow, oh}, O1{own1 ? own1 : a, ow, oh};
     const SepEntry* P = reinterpret_cast<const SepEntry*>(sep);
     const uint2* S = reinterpret_cast<const uint2*>(same);
     const Tex O{out, ow, oh}, X{aux ? aux : out, ow, oh};
-    const dim3 g = grid_for(ow, oh), gq((ow + (org & 0xFFFFu) + 31u) / 32u, (oh + (org >> 16) + 31u) / 32u);
-#define BH_SEP(FP, E, RAW) \
+    const dim3 g = grid_for(ow, oh), gq((ow + 31u) / 32u, (oh + 31u) / 32u);
+#define BH_SEP(FP, RAW, E) \
     hipLaunchKernelGGL((up_sep_kernel<FP, E, RAW>), g, dim3(256), 0, s, tb, A, rx, ry, P, O, O0, O1, S, X)
-#define BH_SEPQ(FP, E, RAW, FS, FX)                                                                                  \
-    do {                                                                                                             \
-        hipLaunchKernelGGL((up_sepq_kernel<FP, E, RAW, FS, FX>), gq, dim3(256),                                      \
-                           sepq_cap_pad(reinterpret_cast<const void*>(&up_sepq_kernel<FP, E, RAW, FS, FX>), E), s, tb, A, \
-                           rx, ry, P, O, O0, O1, S, X, org, STC, strips, strip_w);                                   \
+#define BH_SEPQ(FP, RAW, FS, E)                                                                                 \
+    hipLaunchKernelGGL((up_sepq_kernel<FP, E, RAW, FS>), gq, dim3(256), 0, s, tb, A, rx, ry, P, O, O0, O1, S, X, \
+                       STC, strips, strip_w)
+#define BH_EPI(LAUNCH, ...)                                       \
+    do {                                                          \
+        if (epi == EPI_Y) LAUNCH(__VA_ARGS__, EPI_Y);             \
+        else if (epi == EPI_FINAL) LAUNCH(__VA_ARGS__, EPI_FINAL); \
+        else LAUNCH(__VA_ARGS__, EPI_PLAIN);                      \
     } while (0)
-#define BH_EPI(LAUNCH, ...)                                                    \
-    do {                                                                       \
-        if (epi == EPI_Y) LAUNCH(__VA_ARGS__, EPI_Y, _);                       \
-        else if (epi == EPI_FINAL && fix) LAUNCH(__VA_ARGS__, EPI_FINAL, true); \
-        else if (epi == EPI_FINAL) LAUNCH(__VA_ARGS__, EPI_FINAL, _);          \
-        else LAUNCH(__VA_ARGS__, EPI_PLAIN, _);                                \
-    } while (0)
-#define BH_Q(FPv, RAWv, FSv, E, FX) BH_SEPQ(FPv, E, RAWv, FSv, BH_FIX_##FX)
-#define BH_FIX_true true
-#define BH_FIX__ false
-#define BH_1(FPv, RAWv, E, _) BH_SEP(FPv, E, RAWv)
     // the instantiations sep_form can name (its FS follows from FP and raw)
-    if (f.quad && f.FP == 28 && f.raw) BH_EPI(BH_Q, 28, true, 48);
-    else if (f.quad && f.FP == 40 && f.raw) BH_EPI(BH_Q, 40, true, 48);
-    else if (f.quad && f.FP == 28) BH_EPI(BH_Q, 28, false, 32);
-    else if (f.quad && f.FP == 40) BH_EPI(BH_Q, 40, false, 40);
-    else if (f.quad && f.FP == 60) BH_EPI(BH_Q, 60, true, SEPQ_FS60);
-    else if (f.FP == 24) BH_EPI(BH_1, 24, false);
-    else if (f.FP == 44) BH_EPI(BH_1, 44, true);
+    if (f.quad && f.FP == 28) BH_EPI(BH_SEPQ, 28, false, 32);
+    else if (f.quad && f.FP == 40) BH_EPI(BH_SEPQ, 40, false, 40);
+    else if (f.quad && f.FP == 60) BH_EPI(BH_SEPQ, 60, true, SEPQ_FS60);
+    else if (f.FP == 24) BH_EPI(BH_SEP, 24, false);
+    else if (f.FP == 44) BH_EPI(BH_SEP, 44, true);
     else return (int)hipErrorInvalidValue;
-#undef BH_1
-#undef BH_FIX_true
-#undef BH_FIX__
-#undef BH_Q
 #undef BH_EPI
 #undef BH_SEPQ
 #undef BH_SEP
@@ -2899,93 +1747,50 @@ extern "C" __attribute__((visibility("hidden"))) int bh_launch_bloom_sep(const f
     return (int)e;
 }
 
-// The fix-up pass of a fused epilogue (fixup_kernel): `list` = n_cols columns then n_rows rows
+// The fix-up pass of a fused epilogue (fixup_gather_kernel): `list` = the same-size plan's n_cols inexact columns
+// then n_rows rows, `recs` their records
 extern "C" __attribute__((visibility("hidden"))) int bh_launch_bloom_fixup(const float* lut, const float* enc,
                                                                           const uint8_t* buckets, const uint32_t* codes,
                                                                           uint32_t epi, const uint32_t* a, const uint32_t* b,
                                                                           const uint32_t* c, const uint32_t* same,
                                                                           const uint32_t* list, uint32_t n_cols,
                                                                           uint32_t n_rows, uint32_t* out, uint32_t w,
-                                                                          uint32_t h, int32_t residual_org, const uint32_t* recs,
+                                                                          uint32_t h, const uint32_t* recs,
                                                                           const uint32_t* stc, const uint32_t* strips,
                                                                           uint32_t strip_w, hipStream_t s) {
-    if (n_cols > w || n_rows > h || !list || !same) return (int)hipErrorInvalidValue;  // the list of this frame's plan
-    // the column strips (the full list of the final epilogue, with its records; stc: the table they were written by)
-    static const bool no_rec = std::getenv("BH_BLOOM_FIXUP_NOREC") != nullptr;  // A/B: list, then plan
-    const bool st = stc && recs && !no_rec && epi == EPI_FINAL && residual_org < 0;
-    const uint64_t n = (uint64_t)n_cols * h + (uint64_t)n_rows * w;
-    if (g_dry) {
-        // residual_org < 0: the list of every inexact column and row, right after the plan; else the residual
-        // list of the in-block fix at that grid origin (crossing columns and rows only)
-        note_launch(residual_org < 0 ? (epi == EPI_Y ? "fixup/1" : "fixup/2") : (epi == EPI_Y ? "fixup/1r" : "fixup/2r"), w, h,
-                    n_cols, n_rows, 0u, 0u);
-        const bool ok = residual_org < 0
-                            ? same_ok(w, h, same, list, n_cols, n_rows) &&
-                                  chk(list == same + 2u * ((size_t)w + h), "fix-up list is not its plan's")
-                            : same_ok(w, h, same, nullptr, 0u, 0u, false) &&
-                                  residual_ok(w, h, same, list, n_cols, n_rows, (uint32_t)residual_org, epi == EPI_FINAL);
-        return ok && (!recs || records_ok(w, h, same, list, n_cols, n_rows, recs)) &&
-                       (!st || (strip_ok(w, h, same, list, n_cols, stc, strip_w) && strip_records_ok(list, n_cols, stc, recs)))
-                   ? 0
-                   : (int)hipErrorInvalidValue;
-    }
+    // the list and records of this frame's plan
+    if (n_cols > w || n_rows > h || !list || !same || !recs) return (int)hipErrorInvalidValue;
+    // the column strips (the final epilogue's; stc: the table they were written by)
+    const bool st = stc && epi == EPI_FINAL;
+    if (bh_bloom_dry())
+        return dry_status(check_fixup_launch(epi, w, h, same, list, n_cols, n_rows, recs, st ? stc : nullptr, strip_w));
     if (st && !strips) return (int)hipErrorInvalidValue;
-    const uint32_t* const SP = st ? strips : nullptr;
+    const uint64_t n = (uint64_t)n_cols * h + (uint64_t)n_rows * w;
     if (n == 0) return 0;
     const Tables tb{lut, enc, buckets, codes};
-    const dim3 g0((uint32_t)((n + 255u) / 256u));
+    const dim3 g((uint32_t)((n + 255u) / 256u));
     const uint2* S = reinterpret_cast<const uint2*>(same);
-    static const bool per_sample = std::getenv("BH_BLOOM_FIXUP_SAMPLE") != nullptr;  // A/B: the per-sample form
-    const uint4* R = no_rec ? nullptr : reinterpret_cast<const uint4*>(recs);
-    const dim3 g = g0;
-    if (!per_sample && epi == EPI_Y)
+    const uint4* R = reinterpret_cast<const uint4*>(recs);
+    if (epi == EPI_Y)
         hipLaunchKernelGGL(fixup_gather_kernel<EPI_Y>, g, dim3(256), 0, s, tb, CTex{a, w, h}, CTex{b, w, h},
-                           CTex{b, w, h}, S, list, n_cols, n_rows, Tex{out, w, h}, R, nullptr, 0u);
-    else if (!per_sample)
-        hipLaunchKernelGGL(fixup_gather_kernel<EPI_FINAL>, g, dim3(256), 0, s, tb, CTex{a, w, h}, CTex{b, w, h},
-                           CTex{c, w, h}, S, list, n_cols, n_rows, Tex{out, w, h}, R, SP, strip_w);
-    else if (epi == EPI_Y)
-        hipLaunchKernelGGL(fixup_kernel<EPI_Y>, g, dim3(256), 0, s, tb, CTex{a, w, h}, CTex{b, w, h}, CTex{b, w, h}, S, list,
-                           n_cols, n_rows, Tex{out, w, h});
+                           CTex{b, w, h}, S, n_cols, n_rows, Tex{out, w, h}, R, nullptr, 0u);
     else
-        hipLaunchKernelGGL(fixup_kernel<EPI_FINAL>, g, dim3(256), 0, s, tb, CTex{a, w, h}, CTex{b, w, h}, CTex{c, w, h}, S,
-                           list, n_cols, n_rows, Tex{out, w, h});
+        hipLaunchKernelGGL(fixup_gather_kernel<EPI_FINAL>, g, dim3(256), 0, s, tb, CTex{a, w, h}, CTex{b, w, h},
+                           CTex{c, w, h}, S, n_cols, n_rows, Tex{out, w, h}, R, st ? strips : nullptr, strip_w);
     return (int)hipGetLastError();
 }
 
-// Two downsamples a -> (mw x mh) -> out in one pass (down2_kernel); false: not taken (BH_BLOOM_NO_DOWN2,
-// A/B), the caller runs the two passes
+// Two downsamples a -> (mw x mh) -> out in one pass (down2_kernel)
 extern "C" __attribute__((visibility("hidden"))) int bh_launch_bloom_down2(const float* lut, const float* enc,
                                                                           const uint8_t* buckets, const uint32_t* codes,
                                                                           const uint32_t* a, uint32_t aw, uint32_t ah,
                                                                           uint32_t mw, uint32_t mh, uint32_t* out,
                                                                           uint32_t ow, uint32_t oh, hipStream_t s) {
     if (mw == 0u || mh == 0u) return (int)hipErrorInvalidValue;
-    if (g_dry) {  // every index of down2_kernel is clamped to its texture (down_at): only the sizes to check
-        note_launch("down2", ow, oh, aw, ah, mw, mh);
-        return chk(aw > 0u && ah > 0u && ow > 0u && oh > 0u, "down2 of an empty texture") ? 0 : (int)hipErrorInvalidValue;
-    }
+    if (bh_bloom_dry()) return dry_status(check_down2_launch(ow, oh, aw, ah, mw, mh));
     hipLaunchKernelGGL(down2_kernel, grid_for(ow, oh), dim3(256), 0, s, Tables{lut, enc, buckets, codes}, CTex{a, aw, ah},
                        mw, mh, Tex{out, ow, oh});
     return (int)hipGetLastError();
-}
-
-// The same-size plan of a w x h frame (remix_plan_kernel): per column, then per row, the two clamped
-// texels and the weight of a sample at the pixel's own texcoord ((x + 0.5) / n, sample_coord, floor).
-// Texel indices are 16-bit fields: w, h <= 65536.
-extern "C" __attribute__((visibility("hidden"))) bool bh_bloom_same_plan(uint32_t w, uint32_t h, uint32_t* outp) {
-    if (w > 65536u || h > 65536u || w == 0u || h == 0u) return false;
-    auto axis = [](uint32_t n, uint32_t x, uint32_t* o) {
-        const float t = h_sample_coord(((float)x + 0.5f) / (float)n, n);
-        const float f = floorf(t), wgt = t - f;
-        const int32_t hi = (int32_t)n - 1;
-        const int32_t a0 = std::min(std::max((int32_t)f, 0), hi), a1 = std::min(std::max((int32_t)f + 1, 0), hi);
-        o[0] = (uint32_t)a0 | (uint32_t)a1 << 16;
-        std::memcpy(&o[1], &wgt, 4);
-    };
-    for (uint32_t x = 0; x < w; ++x) axis(w, x, outp + 2u * x);
-    for (uint32_t y = 0; y < h; ++y) axis(h, y, outp + 2u * ((size_t)w + y));
-    return true;
 }
 
 extern "C" __attribute__((visibility("hidden"))) int bh_launch_bloom_remix_plan(const float* lut, const float* enc,
@@ -2994,11 +1799,7 @@ extern "C" __attribute__((visibility("hidden"))) int bh_launch_bloom_remix_plan(
                                                                                const uint32_t* b, const uint32_t* plan,
                                                                                uint32_t* out, uint32_t w, uint32_t h,
                                                                                hipStream_t s) {
-    if (g_dry) {  // the plan's texel indices (host copy)
-        note_launch("remix_plan", w, h, w, h, w, h);
-        return chk(plan != nullptr, "remix without a plan") && same_ok(w, h, plan, nullptr, 0u, 0u, false) ? 0
-                                                                                                                : (int)hipErrorInvalidValue;
-    }
+    if (bh_bloom_dry()) return dry_status(check_same_launch("remix_plan", w, h, plan));
     hipLaunchKernelGGL(remix_plan_kernel, grid_for(w, h), dim3(256), 0, s, Tables{lut, enc, buckets, codes},
                        CTex{a, w, h}, CTex{b, w, h}, reinterpret_cast<const uint2*>(plan), Tex{out, w, h});
     return (int)hipGetLastError();
@@ -3009,12 +1810,7 @@ extern "C" __attribute__((visibility("hidden"))) int bh_launch_bloom_same_copy(c
                                                                               const uint32_t* codes, const uint32_t* src,
                                                                               const uint32_t* plan, uint32_t* out,
                                                                               uint32_t w, uint32_t h, hipStream_t s) {
-    if (g_dry) {  // the plan's texel indices (host copy)
-        note_launch("same_copy", w, h, w, h, w, h);
-        return chk(plan != nullptr, "same-size copy without a plan") && same_ok(w, h, plan, nullptr, 0u, 0u, false)
-                   ? 0
-                   : (int)hipErrorInvalidValue;
-    }
+    if (bh_bloom_dry()) return dry_status(check_same_launch("same_copy", w, h, plan));
     const dim3 g((w + 63u) / 64u, (h + 4u * SAME_COPY_ROWS - 1u) / (4u * SAME_COPY_ROWS));
     hipLaunchKernelGGL(same_copy_kernel, g, dim3(256), 0, s, Tables{lut, enc, buckets, codes}, CTex{src, w, h},
                        reinterpret_cast<const uint2*>(plan), Tex{out, w, h});
@@ -3027,41 +1823,15 @@ extern "C" __attribute__((visibility("hidden"))) int bh_launch_bloom_remix2_plan
                                                                                 const uint32_t* Bt, const uint32_t* plan,
                                                                                 uint32_t* out, uint32_t w, uint32_t h,
                                                                                 hipStream_t s) {
-    if (g_dry) {  // the plan's texel indices (host copy)
-        note_launch("remix2_plan", w, h, w, h, w, h);
-        return chk(plan != nullptr, "remix without a plan") && same_ok(w, h, plan, nullptr, 0u, 0u, false) ? 0
-                                                                                                       : (int)hipErrorInvalidValue;
-    }
+    if (bh_bloom_dry()) return dry_status(check_same_launch("remix2_plan", w, h, plan));
     hipLaunchKernelGGL(remix2_plan_kernel, grid_for(w, h), dim3(256), 0, s, Tables{lut, enc, buckets, codes},
                        CTex{col, w, h}, CTex{Y, w, h}, CTex{Bt, w, h}, reinterpret_cast<const uint2*>(plan),
                        Tex{out, w, h});
     return (int)hipGetLastError();
 }
 
-// bit i: tap i of kawase_upsample.wgsl samples texel centres exactly for every pixel of an
-// ow x oh pass over a tw x th texture with resolution uniform (rx, ry)
-extern "C" __attribute__((visibility("hidden"))) uint32_t bh_bloom_point_mask(uint32_t ow, uint32_t oh, uint32_t tw,
-                                                                             uint32_t th, uint32_t rx, uint32_t ry) {
-    const float hx = 0.5f / (float)rx, hy = 0.5f / (float)ry;
-    uint32_t m = 0;
-    for (int i = 0; i < 8; ++i) {
-        const float du = (hx * (float)((int)((0x12343210u >> (4 * i)) & 15u) - 2)) * 3.0f;
-        const float dv = (hy * (float)((int)((0x10123432u >> (4 * i)) & 15u) - 2)) * 3.0f;
-        if (axis_point(ow, tw, du) && axis_point(oh, th, dv)) m |= 1u << i;
-    }
-    return m;
-}
-
-// Whether bh_launch_bloom_pass runs an up pass of this shape with up_sep_kernel (neither the TapPlan nor
-// the Up2Plan form applies): only then does the host build the shape's separable plan (bh_bloom_sep_plan).
-static const bool g_no_up2 = std::getenv("BH_BLOOM_NO_UP2") != nullptr;  // A/B: the general up pass
-static const bool g_no_sep = std::getenv("BH_BLOOM_NO_SEP") != nullptr;  // A/B: the per-pixel sampler
-extern "C" __attribute__((visibility("hidden"))) bool bh_bloom_up_uses_sep(uint32_t ow, uint32_t oh, uint32_t aw,
-                                                                         uint32_t ah, uint32_t rx, uint32_t ry) {
-    if (g_no_sep || tap_plan(ow, oh, aw, ah, rx, ry).valid) return false;
-    return g_no_up2 || !up2_plan(ow, oh, aw, ah, rx, ry).valid;
-}
-
+// One render pass of the reference.  An up pass takes the first form that applies: the TapPlan form of pass_kernel,
+// the 2:1 quad form (up2_kernel), the separable plan the caller built (bh_bloom_up_uses_sep), the general sampler.
 extern "C" __attribute__((visibility("hidden"))) int bh_launch_bloom_pass(uint32_t shader, const float* lut,
                                                                          const float* enc, const uint8_t* buckets,
                                                                          const uint32_t* codes, const uint32_t* a,
@@ -3072,16 +1842,12 @@ extern "C" __attribute__((visibility("hidden"))) int bh_launch_bloom_pass(uint32
     const Tables tb{lut, enc, buckets, codes};
     const CTex A{a, aw, ah}, B{b ? b : a, aw, ah};
     const Tex O{out, ow, oh};
+    const bool dry = bh_bloom_dry();
     const TapPlan P = shader == SH_UP ? tap_plan(ow, oh, aw, ah, rx, ry) : TapPlan{};
-    const uint32_t pm = shader == SH_UP && !P.valid && !g_dry ? bh_bloom_point_mask(ow, oh, aw, ah, rx, ry) : 0u;
-    if (shader == SH_UP && !P.valid && !g_no_up2) {
+    const uint32_t pm = shader == SH_UP && !P.valid && !dry ? bh_bloom_point_mask(ow, oh, aw, ah, rx, ry) : 0u;
+    if (shader == SH_UP && !P.valid && up2_enabled()) {
         const Up2Plan Q = up2_plan(ow, oh, aw, ah, rx, ry);
-        if (Q.valid && g_dry) {
-            note_launch(std_up2_plan(Q) == 12 ? "up2_12" : std_up2_plan(Q) == 3 ? "up2_3" : "up2_0", ow, oh, aw, ah, rx, ry);
-            const bool ok = tile_ok(FP_UPQ, FS_UPQ, 0, FP_UPQ * FS_UPQ) && up2_axis_ok(Q, ow, aw, rx, 0, FP_UPQ) &&
-                            up2_axis_ok(Q, oh, ah, ry, 1, FP_UPQ);
-            return ok ? 0 : (int)hipErrorInvalidValue;
-        }
+        if (Q.valid && dry) return dry_status(check_up2_launch(Q, ow, oh, aw, ah, rx, ry));
         if (Q.valid) {
             const dim3 g((ow + 31u) / 32u, (oh + 31u) / 32u);
             switch (std_up2_plan(Q)) {
@@ -3092,19 +1858,11 @@ extern "C" __attribute__((visibility("hidden"))) int bh_launch_bloom_pass(uint32
             return (int)hipGetLastError();
         }
     }
-    if (shader == SH_UP && !P.valid && sep && sep_form(sep_ext, ow, oh).FP != 0 && !g_no_sep) {
+    if (shader == SH_UP && !P.valid && sep && sep_form(sep_ext).FP != 0 && sep_enabled()) {
         return bh_launch_bloom_sep(lut, enc, buckets, codes, a, aw, ah, rx, ry, sep, sep_ext, EPI_PLAIN, nullptr, nullptr,
-                                   nullptr, out, nullptr, ow, oh, 0u, false, nullptr, nullptr, 0u, nullptr, s);
+                                   nullptr, out, nullptr, ow, oh, nullptr, nullptr, 0u, nullptr, s);
     }
-    if (g_dry) {  // pass_kernel: an up pass stages through with_source<FP_UP>; the others read clamped indices
-        note_launch(shader == SH_UP ? (P.valid ? "pass_up_tap" : "pass_up") : shader == SH_COPY ? "pass_copy"
-                    : shader == SH_DOWN ? "pass_down" : "pass_remix", ow, oh, aw, ah, rx, ry);
-        const bool ok = chk(aw > 0u && ah > 0u && ow > 0u && oh > 0u, "pass over an empty texture") &&
-                        (shader != SH_UP || (tile_ok(FP_UP, FP_UP, 0, FP_UP * FP_UP) &&
-                                             tapplan_axis_ok(P, ow, aw, rx, 0, 16u, FP_UP) &&
-                                             tapplan_axis_ok(P, oh, ah, ry, 1, 16u, FP_UP)));
-        return ok ? 0 : (int)hipErrorInvalidValue;
-    }
+    if (dry) return dry_status(check_pass_launch(shader, P, ow, oh, aw, ah, rx, ry));
     switch (shader) {
         case SH_COPY: hipLaunchKernelGGL(pass_kernel<SH_COPY>, grid_for(ow, oh), dim3(256), 0, s, tb, A, B, rx, ry, pm, P, O); break;
         case SH_DOWN: hipLaunchKernelGGL(pass_kernel<SH_DOWN>, grid_for(ow, oh), dim3(256), 0, s, tb, A, B, rx, ry, pm, P, O); break;
@@ -3112,22 +1870,6 @@ extern "C" __attribute__((visibility("hidden"))) int bh_launch_bloom_pass(uint32
         default: hipLaunchKernelGGL(pass_kernel<SH_REMIX>, grid_for(ow, oh), dim3(256), 0, s, tb, A, B, rx, ry, pm, P, O); break;
     }
     return (int)hipGetLastError();
-}
-
-extern "C" __attribute__((visibility("hidden"))) bool bh_bloom_down2_fusable(uint32_t w, uint32_t h) {
-    // the sides multiples of 32 (the Y quad kernel's block: every lane inside the frame), and down2_kernel's
-    // sample arithmetic (down_at) on every pixel of both levels: texel 2 x' and 2 x' + 1, weight 0.5 -- which
-    // holds at powers of two, not at display sizes such as 1920 x 1080 (37 and 32 inexact samples per axis)
-    auto axis = [](uint32_t n) {
-        if (n % 32u != 0u) return false;
-        for (uint32_t on = n / 2u, tn = n; on >= n / 4u; tn = on, on /= 2u)
-            for (uint32_t x = 0; x < on; ++x) {
-                const float t = h_sample_coord(h_texcoord(x, on), tn), f = floorf(t);
-                if (f != (float)(2u * x) || t - f != 0.5f || 2u * x + 1u > tn - 1u) return false;
-            }
-        return true;
-    };
-    return axis(w) && axis(h);
 }
 
 extern "C" __attribute__((visibility("hidden"))) int bh_launch_bloom_y(const float* lut, const float* enc,
@@ -3141,15 +1883,7 @@ extern "C" __attribute__((visibility("hidden"))) int bh_launch_bloom_y(const flo
     const bool quad = P.valid && !no_quad && P.hi_x - P.lo_x + 32 <= FP_YQ && P.hi_y - P.lo_y + 32 <= FP_YQ;
     const bool d2 = quad && d2out && !no_yd2 && bh_bloom_down2_fusable(w, h);
     if (d2_done) *d2_done = d2;
-    if (g_dry) {  // the quad form's tile (row-pair shift) or with_source<FP_Y>
-        note_launch(quad ? (std_tap_plan(P) == 12 ? "yq12" : "yq0") : "y1", w, h, w, h, w, h);
-        if (d2) note_launch("down2f", w / 4u, h / 4u, w, h, w / 2u, h / 2u);  // fused into the Y launch
-        const bool ok = quad ? tile_ok(FP_YQ, FS_YQ, 2, FP_YQ * FS_YQ + FP_YQ / 2 + 1) &&
-                                   tapplan_axis_ok(P, w, w, w, 0, 32u, FP_YQ) && tapplan_axis_ok(P, h, h, h, 1, 32u, FP_YQ)
-                             : tile_ok(FP_Y, FP_Y, 0, FP_Y * FP_Y) && tapplan_axis_ok(P, w, w, w, 0, 16u, FP_Y) &&
-                                   tapplan_axis_ok(P, h, h, h, 1, 16u, FP_Y);
-        return ok ? 0 : (int)hipErrorInvalidValue;
-    }
+    if (bh_bloom_dry()) return dry_status(check_y_launch(P, quad, d2, w, h));
     if (quad) {
         const dim3 g((w + 31u) / 32u, (h + 31u) / 32u);
         const Tables tb{lut, enc, buckets, codes};
@@ -3177,25 +1911,13 @@ extern "C" __attribute__((visibility("hidden"))) int bh_launch_bloom_final(const
                                                                           uint32_t* out, uint32_t w, uint32_t h,
                                                                           hipStream_t s) {
     const TapPlan P = tap_plan(w, h, w, h, rx, ry);
-    if (g_dry) {  // with_source<FP_FINAL>: the TapPlan form (raw words) or the span fallback
-        note_launch(P.valid ? (std_tap_plan(P) == 48 ? "final48" : "final0") : "final", w, h, w, h, rx, ry);
-        const bool ok = tile_ok(FP_FINAL, FP_FINAL, 0, FP_FINAL * FP_FINAL) &&
-                        tapplan_axis_ok(P, w, w, rx, 0, 16u, FP_FINAL) && tapplan_axis_ok(P, h, h, ry, 1, 16u, FP_FINAL);
-        return ok ? 0 : (int)hipErrorInvalidValue;
-    }
+    if (bh_bloom_dry()) return dry_status(check_final_launch(P, w, h, rx, ry));
     const uint32_t pm = P.valid ? 0u : bh_bloom_point_mask(w, h, w, h, rx, ry);
     // the kernel's with_source takes the TapPlan form exactly when this holds (raw words staged)
     const bool plan = P.valid && P.hi_x - P.lo_x + 16 <= FP_FINAL && P.hi_y - P.lo_y + 16 <= FP_FINAL;
     const size_t lds = (size_t)FP_FINAL * FP_FINAL * (plan ? sizeof(uint32_t) : sizeof(float4));
     const bool std48 = plan && std_tap_plan(P) == 48;
-    // persistent blocks: measured no faster; BH_BLOOM_PERSIST=1 takes them (A/B)
-    static const bool persist = std::getenv("BH_BLOOM_PERSIST") != nullptr;
-    const uint32_t tiles_x = (w + 15u) / 16u, n_tiles = tiles_x * ((h + 15u) / 16u);
-    const uint32_t G = persistent_grid(7u);
-    if (std48 && persist && n_tiles >= 2u * G)
-        hipLaunchKernelGGL(bloom_final_pkernel<48>, dim3(G), dim3(256), 0, s, Tables{lut, enc, buckets, codes},
-                           CTex{col, w, h}, CTex{Y, w, h}, CTex{U0, w, h}, P, Tex{out, w, h}, tiles_x, n_tiles);
-    else if (std48)
+    if (std48)
         hipLaunchKernelGGL(bloom_final_kernel<48>, grid_for(w, h), dim3(256), lds, s, Tables{lut, enc, buckets, codes},
                            CTex{col, w, h}, CTex{Y, w, h}, CTex{U0, w, h}, rx, ry, pm, P, Tex{out, w, h});
     else

@@ -1,6 +1,6 @@
 // bh_bloom_host.cpp — the host side of bh_bloom (include/bh_render.h): which same-size passes are identities,
 // the separable plans of the up passes, the chain of launches (bh_bloom.hip holds the kernels and their
-// launchers) and bh_bloom_check's dry run of it.
+// launchers, bh_bloom_plan.cpp the plan builders and host checks) and bh_bloom_check's dry run of it.
 #include <algorithm>
 #include <atomic>
 #include <cmath>
@@ -9,6 +9,7 @@
 #include <cstring>
 #include <thread>
 
+#include "bh_bloom_plan.hpp"
 #include "bh_host.hpp"
 
 void free_bloom_scratch(bh_ctx::BloomScratch& b) {
@@ -151,8 +152,8 @@ void plan_failure(std::string* dry_fail, uint32_t ow, uint32_t oh, uint32_t tw, 
 // Returned by value: the cache is a vector that later plans reallocate.  (Round 4's memory-access fault:
 // a pointer into it, held across the next call, read a freed record's fix-up counts)
 bh_ctx::SepPlan sep_plan(bh_ctx::BloomScratch* b, bool capturing, std::string* dry_fail, uint32_t ow, uint32_t oh,
-                         uint32_t tw, uint32_t th, uint32_t rx, uint32_t ry, int* err, uint32_t org = 0, bool fix = false) {
-    const std::array<uint32_t, 8> key{ow, oh, tw, th, rx, ry, org, fix ? 1u : 0u};
+                         uint32_t tw, uint32_t th, uint32_t rx, uint32_t ry, int* err) {
+    const std::array<uint32_t, 6> key{ow, oh, tw, th, rx, ry};
     for (const auto& p : b->sep_plans)
         if (p.key == key) return p;
     bh_ctx::SepPlan P;
@@ -166,8 +167,8 @@ bh_ctx::SepPlan sep_plan(bh_ctx::BloomScratch* b, bool capturing, std::string* d
     bool ok;
     if (rx) {
         h->resize(32u * ((size_t)ow + oh));
-        P.ext = bh_bloom_sep_plan(ow, oh, tw, th, rx, ry, h->data(), org);
-        ok = P.ext >= 0 && bh_bloom_sep_verify(ow, oh, tw, th, rx, ry, h->data(), P.ext, org, fix, &why);
+        P.ext = bh_bloom_sep_plan(ow, oh, tw, th, rx, ry, h->data());
+        ok = P.ext >= 0 && bh_bloom_sep_verify(ow, oh, tw, th, rx, ry, h->data(), P.ext, &why);
     } else {
         h->resize(2u * ((size_t)ow + oh));
         ok = bh_bloom_same_plan(ow, oh, h->data());
@@ -182,37 +183,16 @@ bh_ctx::SepPlan sep_plan(bh_ctx::BloomScratch* b, bool capturing, std::string* d
             h->insert(h->end(), cols.begin(), cols.end());
             h->insert(h->end(), rows.begin(), rows.end());
             ok = bh_bloom_same_verify(ow, oh, h->data(), P.nc, P.nr, &why);
-            if (ok) {  // the in-block fix's grid origin and residual list (checked where the fix-up launches)
-                std::vector<uint32_t> rc, rr, rc2, rr2;
-                P.org = bh_bloom_same_org(ow, oh, h->data(), &rc, &rr, &rc2, &rr2);
-                P.nrc = (uint32_t)rc.size();
-                P.nrr = (uint32_t)rr.size();
-                P.nrc2 = (uint32_t)rc2.size();
-                P.nrr2 = (uint32_t)rr2.size();
-                for (const auto* v : {&rc, &rr, &rc2, &rr2}) h->insert(h->end(), v->begin(), v->end());
-                // the three lists' records, 16-byte aligned (the kernel reads them as uint4)
-                const size_t lists = 2u * ((size_t)ow + oh), n_all = P.nc + P.nr + P.nrc + P.nrr + P.nrc2 + P.nrr2;
+            if (ok) {
+                // the list's records, 16-byte aligned (the kernel reads them as uint4), as the fix-up kernel reads
+                // them (a failure drops the plan)
+                const size_t lists = 2u * ((size_t)ow + oh);
                 h->resize((h->size() + 3u) & ~(size_t)3u, 0u);
                 P.rec = h->size();
-                h->resize(P.rec + 8u * n_all, 0u);
-                uint32_t* R = h->data() + P.rec;
-                const uint32_t* L = h->data() + lists;
-                bh_bloom_fixup_records(ow, oh, h->data(), L, P.nc, P.nr, R);
-                L += P.nc + P.nr; R += 8u * (P.nc + P.nr);
-                bh_bloom_fixup_records(ow, oh, h->data(), L, P.nrc, P.nrr, R);
-                L += P.nrc + P.nrr; R += 8u * (P.nrc + P.nrr);
-                bh_bloom_fixup_records(ow, oh, h->data(), L, P.nrc2, P.nrr2, R);
-                // every list's records as the fix-up kernels read them (a failure drops the plan)
-                {
-                    const uint32_t* Lc = h->data() + lists;
-                    const uint32_t* Rc = h->data() + P.rec;
-                    const uint32_t nlist[3][2] = {{P.nc, P.nr}, {P.nrc, P.nrr}, {P.nrc2, P.nrr2}};
-                    for (int li = 0; ok && li < 3; ++li) {
-                        ok = bh_bloom_records_verify(ow, oh, h->data(), Lc, nlist[li][0], nlist[li][1], Rc, nullptr, 0u, &why);
-                        Lc += nlist[li][0] + nlist[li][1];
-                        Rc += 8u * (nlist[li][0] + nlist[li][1]);
-                    }
-                }
+                h->resize(P.rec + 8u * ((size_t)P.nc + P.nr), 0u);
+                bh_bloom_fixup_records(ow, oh, h->data(), h->data() + lists, P.nc, P.nr, h->data() + P.rec);
+                ok = bh_bloom_records_verify(ow, oh, h->data(), h->data() + lists, P.nc, P.nr, h->data() + P.rec, nullptr, 0u,
+                                             &why);
                 // the column strips of the final fix-up (BH_BLOOM_NO_STRIPS: off, A/B), within a storage budget
                 static const bool no_strips = std::getenv("BH_BLOOM_NO_STRIPS") != nullptr;
                 if (ok && !no_strips && P.nc > 0u) {
@@ -366,43 +346,24 @@ int bloom_chain(bh_ctx* c, bh_ctx::BloomScratch* B, bool capturing, std::string*
         // inexact columns and rows; other plans run the plain pass and the plan remix kernels.
         const uint32_t* plan = same.dev;
         const uint32_t* list = plan ? plan + 2u * ((size_t)W + H) : nullptr;
-        const uint32_t* residual = list ? list + same.nc + same.nr : nullptr;
-        const uint32_t* residual2 = residual ? residual + same.nrc + same.nrr : nullptr;
-        // The final epilogue's in-block fix (FIX2) only with BH_BLOOM_FIX2 -- measured slower than its fix-up pass
-        // (1920x1080 0.1237 -> 0.1256 ms: three block barriers in the chain's longest-lived waves;
-        // profiles/r05/bloom_fix2/)
-        static const bool fix2 = std::getenv("BH_BLOOM_FIX2") != nullptr;
         // an up pass at full size into `aux` with epilogue `epi` (own0, own1 its own-texel inputs), then the
         // fix-up of the inexact pixels -- or the plain pass and the remix kernel
         auto fused_up = [&](uint32_t epi, const uint32_t* src, uint32_t sw, uint32_t sh, const uint32_t* res,
                             uint32_t* aux, const uint32_t* own0, const uint32_t* own1, uint32_t* dst) {
             if (R.err != 0) return;
             bh_ctx::SepPlan sp{};
-            // the epilogues' in-block fixes (quad kernel: the grid at the same-size plan's origin, the fix-up pass
-            // over the residual list only): the Y epilogue's was removed in round 6 -- it gave wrong bytes at frame
-            // sizes outside the test list (a seeded random-size sweep: e.g. 1846x1392, 177x1706) --, the final
-            // epilogue's (BH_BLOOM_FIX2) is an A/B arm; otherwise the fix-up pass covers every inexact column and row
-            const bool fix = epi == 2u && fix2;
-            const uint32_t org = fix ? same.org : 0u;
             if (bh_bloom_up_uses_sep(W, H, sw, sh, res[0], res[1]))
-                sp = sep_plan(B, capturing, dry_fail, W, H, sw, sh, res[0], res[1], &R.err, org, fix);
+                sp = sep_plan(B, capturing, dry_fail, W, H, sw, sh, res[0], res[1], &R.err);
             if (R.err != 0) return;
             // the final epilogue writes the column strips its fix-up reads (bh_bloom.hip STRIPS)
             const uint32_t* stc = epi == 2u && same.stc ? plan + same.stc : nullptr;
             bool strips = false;
             if (sp.dev && bh_launch_bloom_sep(c->lut, c->enc, c->enc_b, c->enc_e, src, sw, sh, res[0], res[1], sp.dev,
-                                              sp.ext, epi, own0, own1, plan, dst, aux, W, H, org, fix, stc, same.strips,
-                                              same.stw, &strips, s) == 0) {
-                const bool fixed = fix && bh_bloom_sep_fix_ok(sp.ext, W, H, epi);
-                const uint32_t* rl = epi == 1u ? residual : residual2;
-                const uint32_t rc = epi == 1u ? same.nrc : same.nrc2, rr = epi == 1u ? same.nrr : same.nrr2;
-                // the list's records: full, residual 1, residual 2 in that order after same.rec
-                const size_t rk = !fixed ? 0u : epi == 1u ? same.nc + same.nr : same.nc + same.nr + same.nrc + same.nrr;
-                const uint32_t* recs = same.rec ? plan + same.rec + 8u * rk : nullptr;
+                                              sp.ext, epi, own0, own1, plan, dst, aux, W, H, stc, same.strips, same.stw,
+                                              &strips, s) == 0) {
                 R.err = bh_launch_bloom_fixup(c->lut, c->enc, c->enc_b, c->enc_e, epi, own0, epi == 1u ? aux : own1, aux,
-                                              plan, fixed ? rl : list, fixed ? rc : same.nc, fixed ? rr : same.nr, dst, W, H,
-                                              fixed ? (int32_t)same.org : -1, recs, strips && !fixed ? stc : nullptr,
-                                              same.strips, same.stw, s);
+                                              plan, list, same.nc, same.nr, dst, W, H, plan + same.rec,
+                                              strips ? stc : nullptr, same.strips, same.stw, s);
                 return;
             }
             R.pass(bh_bloom_shader_up, src, sw, sh, nullptr, res, aux, W, H);

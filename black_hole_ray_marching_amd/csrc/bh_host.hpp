@@ -89,14 +89,11 @@ struct bh_ctx {
     // ext: the largest block footprint side (up passes); nc, nr: the inexact columns / rows (same plan)
     // host: the plan's host copy in bh_bloom_check's dry mode (dev then points into it; never freed as device memory)
     struct SepPlan {
-        std::array<uint32_t, 8> key{};  // ow, oh, tw, th, rx, ry, grid origin, in-block fix
+        std::array<uint32_t, 6> key{};  // ow, oh, tw, th, rx, ry
         uint32_t* dev = nullptr;
         int ext = 0;
         uint32_t nc = 0, nr = 0;
-        // same-size plan: the quad grid origin of the in-block fix and its residual (crossing) columns / rows,
-        // listed after the full list
-        uint32_t org = 0, nrc = 0, nrr = 0, nrc2 = 0, nrr2 = 0;  // residual lists of the Y / final epilogue
-        size_t rec = 0;  // word offset of the lists' fix-up records (full, residual 1, residual 2; 8 words each)
+        size_t rec = 0;  // same-size plan: word offset of the list's fix-up records (8 words each)
         // the final epilogue's column strips (bh_bloom_strip_table): word offset of the table (0: none), its
         // strip columns and the strip storage (3 images x stw columns x oh rows; not allocated in dry mode)
         size_t stc = 0;
@@ -213,33 +210,22 @@ BH_INTERNAL int bh_launch_tiles_unpack_rgbm(const void* packed, void* out, void*
                 uint32_t rows_in_flight, hipStream_t s);
 BH_INTERNAL int bh_launch_tiles_unpack_rgb(const void* packed, void* out, uint32_t width, uint32_t height,
                 uint32_t shard_count, uint64_t stride_tiles, uint32_t format, uint32_t rows_in_flight, hipStream_t s);
-// the separable plan of an 8-tap pass (bh_bloom.hip): 8 * (ow + oh) entries of 4 words; returns the largest
-// block footprint side (or -1)
-BH_INTERNAL int bh_bloom_sep_plan(uint32_t ow, uint32_t oh, uint32_t tw, uint32_t th, uint32_t rx, uint32_t ry,
-                uint32_t* outp, uint32_t org);
 // an up pass from its separable plan with an epilogue (bh_bloom.hip SepEpi: 0 plain, 1 Y, 2 final)
 BH_INTERNAL int bh_launch_bloom_sep(const float* lut, const float* enc, const uint8_t* buckets, const uint32_t* codes,
                 const uint32_t* a, uint32_t aw, uint32_t ah, uint32_t rx, uint32_t ry, const uint32_t* sep, int ext,
                 uint32_t epi, const uint32_t* own0, const uint32_t* own1, const uint32_t* same, uint32_t* out,
-                uint32_t* aux, uint32_t ow, uint32_t oh, uint32_t org, bool fix, const uint32_t* stc, uint32_t* strips,
-                uint32_t strip_w, bool* strips_written, hipStream_t s);
-// the fix-up pass of a fused epilogue; stc / strips: the final epilogue's column strips (the up pass wrote them)
+                uint32_t* aux, uint32_t ow, uint32_t oh, const uint32_t* stc, uint32_t* strips, uint32_t strip_w,
+                bool* strips_written, hipStream_t s);
+// the fix-up pass of a fused epilogue over the same-size plan's list and its records; stc / strips: the final epilogue's column strips (the up pass wrote them)
 BH_INTERNAL int bh_launch_bloom_fixup(const float* lut, const float* enc, const uint8_t* buckets, const uint32_t* codes,
                 uint32_t epi, const uint32_t* a, const uint32_t* b, const uint32_t* c, const uint32_t* same,
                 const uint32_t* list, uint32_t n_cols, uint32_t n_rows, uint32_t* out, uint32_t w, uint32_t h,
-                int32_t residual_org, const uint32_t* recs, const uint32_t* stc, const uint32_t* strips,
-                uint32_t strip_w, hipStream_t s);
-// the column strips' table of a same-size plan's inexact columns; returns the number of strip columns
-BH_INTERNAL uint32_t bh_bloom_strip_table(uint32_t w, const uint32_t* list, uint32_t nc, uint32_t* stc);
-// the fix-up kernel's records of a list (8 words per entry: the index and the plan entries of it and its neighbours)
-BH_INTERNAL void bh_bloom_fixup_records(uint32_t w, uint32_t h, const uint32_t* plan, const uint32_t* list, uint32_t nc,
-                uint32_t nr, uint32_t* out);
+                const uint32_t* recs, const uint32_t* stc, const uint32_t* strips, uint32_t strip_w, hipStream_t s);
 // two downsamples a -> mw x mh -> out in one pass (the intermediate level not stored)
 BH_INTERNAL int bh_launch_bloom_down2(const float* lut, const float* enc, const uint8_t* buckets, const uint32_t* codes,
                 const uint32_t* a, uint32_t aw, uint32_t ah, uint32_t mw, uint32_t mh, uint32_t* out, uint32_t ow,
                 uint32_t oh, hipStream_t s);
-// the same-size plan of a w x h frame (bh_bloom.hip): (w + h) uint2 entries; the plan remixes
-BH_INTERNAL bool bh_bloom_same_plan(uint32_t w, uint32_t h, uint32_t* outp);
+// the remixes and the same-size copy through the same-size plan (bh_bloom_same_plan)
 BH_INTERNAL int bh_launch_bloom_remix_plan(const float* lut, const float* enc, const uint8_t* buckets,
                 const uint32_t* codes, const uint32_t* a, const uint32_t* b, const uint32_t* plan, uint32_t* out,
                 uint32_t w, uint32_t h, hipStream_t s);
@@ -249,25 +235,6 @@ BH_INTERNAL int bh_launch_bloom_same_copy(const float* lut, const float* enc, co
 BH_INTERNAL int bh_launch_bloom_remix2_plan(const float* lut, const float* enc, const uint8_t* buckets,
                 const uint32_t* codes, const uint32_t* col, const uint32_t* Y, const uint32_t* Bt, const uint32_t* plan,
                 uint32_t* out, uint32_t w, uint32_t h, hipStream_t s);
-// host-side bound checks of the bloom kernels' index arithmetic (bh_bloom.hip): a separable plan for the form
-// bh_launch_bloom_sep takes, a same-size plan with its fix-up list; false with the first violation in *why.
-// Dry mode (bh_bloom_check): between begin and end the bloom launchers check their launch instead of launching.
-BH_INTERNAL bool bh_bloom_sep_verify(uint32_t ow, uint32_t oh, uint32_t tw, uint32_t th, uint32_t rx, uint32_t ry,
-                const uint32_t* plan, int ext, uint32_t org, bool fix, std::string* why);
-BH_INTERNAL bool bh_bloom_sep_fix_ok(int ext, uint32_t ow, uint32_t oh, uint32_t epi);
-// the quad grid origin of the in-block fix for a same-size plan, and its residual (crossing) columns / rows
-BH_INTERNAL uint32_t bh_bloom_same_org(uint32_t w, uint32_t h, const uint32_t* plan, std::vector<uint32_t>* cols,
-                std::vector<uint32_t>* rows, std::vector<uint32_t>* cols2, std::vector<uint32_t>* rows2);
-BH_INTERNAL bool bh_bloom_same_verify(uint32_t w, uint32_t h, const uint32_t* plan, uint32_t nc, uint32_t nr,
-                std::string* why);
-BH_INTERNAL bool bh_bloom_records_verify(uint32_t w, uint32_t h, const uint32_t* plan, const uint32_t* list,
-                uint32_t nc, uint32_t nr, const uint32_t* rec, const uint32_t* stc, uint32_t strip_w,
-                std::string* why);
-BH_INTERNAL void bh_bloom_dry_begin(void);
-BH_INTERNAL bool bh_bloom_dry_end(uint64_t* launches, uint64_t* checks, std::string* fail, std::string* plan);
-BH_INTERNAL bool bh_bloom_dry(void);
-// whether bh_launch_bloom_pass runs an up pass of this shape from its separable plan (bh_bloom.hip)
-BH_INTERNAL bool bh_bloom_up_uses_sep(uint32_t ow, uint32_t oh, uint32_t aw, uint32_t ah, uint32_t rx, uint32_t ry);
 BH_INTERNAL int bh_launch_bloom_pass(uint32_t shader, const float* lut, const float* enc, const uint8_t* buckets,
                 const uint32_t* codes, const uint32_t* a, uint32_t aw, uint32_t ah, const uint32_t* b, uint32_t rx,
                 uint32_t ry, uint32_t* out, uint32_t ow, uint32_t oh, const uint32_t* sep, int sep_ext, hipStream_t s);

@@ -127,18 +127,34 @@ def test_the_checks_catch_a_footprint_that_overfills_its_tile():
     assert "tile" in msg or "footprint" in msg or "span" in msg, msg
 
 
+def test_default_launch_lists_are_the_recorded_ones():
+    """The dry run's list of (form, sizes) per launch, for both schedules at levels 1, 3 and 5, against the lists
+    recorded in tests/golden/bloom_launch_lists.json: the same kernels are launched, in the same order, on the
+    same shapes."""
+    import json
+    want = json.loads((ROOT / "tests" / "golden" / "bloom_launch_lists.json").read_text())
+    sizes = [(1920, 1080), (1280, 720), (1366, 768), (4096, 2048), (512, 256), (3840, 2160), (3440, 1440), (3996, 495),
+             (1846, 1392), (177, 1706), (1, 1), (7, 300), (65536, 8)]
+    seen = set()
+    for W, H in sizes:
+        for levels in (1, 3, 5):
+            for name, schedule in (("auto", bh.BH_BLOOM_AUTO), ("literal", bh.BH_BLOOM_LITERAL)):
+                key = f"{W}x{H}/L{levels}/{name}"
+                got = [list(t) for t in bh.bloom_check(W, H, levels, schedule)]
+                assert got == want[key], key
+                seen.add(key)
+    assert seen == set(want)
+
+
 def test_fixup_lane_addresses_stay_inside(tmp_path):
     """The final fix-up pass's global reads lane by lane (tools/bloom_fixup_addr.cpp, a host emulation of
-    fixup_gather_kernel<EPI_FINAL> with records and column strips, from the library's own plan builders in
-    its bh_bloom.o): every index inside its buffer -- the dead lanes past the list included, whose stale
-    column record indexed rows at 3996 x 495 (round 6's GPU memory fault)."""
-    obj = ROOT / "black_hole_ray_marching_amd" / "_build" / "bh_bloom.o"
-    hipcc = Path(os.environ.get("HIPCC", "/opt/rocm/bin/hipcc"))
-    if not obj.exists() or not hipcc.exists():
-        pytest.skip("needs the built bh_bloom.o and hipcc")
-    o, exe = tmp_path / "fa.o", tmp_path / "fa"
-    subprocess.run(["g++", "-O2", "-std=c++17", "-c", str(ROOT / "tools" / "bloom_fixup_addr.cpp"), "-o", str(o)], check=True)
-    subprocess.run([str(hipcc), "--offload-arch=gfx950", str(o), str(obj), "-o", str(exe)], check=True)
+    fixup_gather_kernel<EPI_FINAL> with records and column strips, from the library's own plan builders,
+    csrc/bh_bloom_plan.cpp, compiled with it by g++): every index inside its buffer -- the dead lanes past the
+    list included, whose stale column record indexed rows at 3996 x 495 (round 6's GPU memory fault, DESIGN.md
+    §7b)."""
+    exe = tmp_path / "fa"
+    subprocess.run(["g++", "-O2", "-std=c++17", "-ffp-contract=off", str(ROOT / "tools" / "bloom_fixup_addr.cpp"),
+                    str(ROOT / "black_hole_ray_marching_amd" / "csrc" / "bh_bloom_plan.cpp"), "-o", str(exe)], check=True)
     named = ["3996", "495", "1868", "83", "3840", "2160", "1920", "1080", "1", "1", "4096", "1"]
     r = subprocess.run([str(exe), *named], capture_output=True, text=True, timeout=120)
     assert r.returncode == 0, r.stdout[-2000:]

@@ -49,9 +49,8 @@ def _gpu_bloom(torch, scene, col, bo, levels, schedule):
                                         # fuses them; the up passes take the separable plan (per-column /
                                         # per-row taps from the host); also thin frames
                                         (1080, 1920, 3), (720, 1280, 3), (1080, 1920, 5), (7, 300, 3), (300, 7, 3),
-                                        # the Y epilogue's in-block fix with a residual fix-up list (1366: at
-                                        # every grid origin some inexact columns cross a block edge; 3 at the
-                                        # best) and nonzero grid origins (1920: 8, 720 rows: 14)
+                                        # a width whose inexact columns' samples cross 32-pixel block edges
+                                        # (the case of the in-block fixes, since deleted: DESIGN.md §7b)
                                         (768, 1366, 3),
                                         # common display widths the CPU sweep (1..2100) does not reach:
                                         # their strip tables and records
@@ -84,7 +83,7 @@ def test_bloom_bitexact(torch_cuda, sky_small, H, W, levels, schedule):
 
 @pytest.mark.parametrize("H,W,levels,sparse", [(128, 256, 3, False), (256, 512, 3, False), (120, 200, 3, False),
                                                (256, 512, 3, True), (512, 1024, 3, True),
-                                               # the general fused chain's quad passes and in-block fix
+                                               # the general fused chain's quad passes and fix-up
                                                # with alpha below 255 (no opaque-block form)
                                                (1080, 1920, 3, False), (720, 1280, 3, True), (768, 1366, 3, False)])
 def test_bloom_bitexact_any_alpha(torch_cuda, sky_small, H, W, levels, sparse):
@@ -183,27 +182,20 @@ STANDARD_FRAMES = ["512x1024", "256x512:any", "2048x4096"]  # powers of two: the
 
 
 @pytest.mark.parametrize("env,frames", [
-    ({"BH_BLOOM_FIX2": "1"}, GENERAL_FRAMES),
-    ({"BH_BLOOM_ORG_KEEP": "1"}, GENERAL_FRAMES), ({"BH_BLOOM_NO_STRIPS": "1"}, GENERAL_FRAMES),
-    ({"BH_BLOOM_FIXUP_NOREC": "1"}, GENERAL_FRAMES), ({"BH_BLOOM_FIXUP_SAMPLE": "1"}, GENERAL_FRAMES),
+    ({"BH_BLOOM_NO_STRIPS": "1"}, GENERAL_FRAMES),
     ({"BH_BLOOM_NO_SEPQ": "1"}, GENERAL_FRAMES), ({"BH_BLOOM_NO_SEP": "1"}, GENERAL_FRAMES),
-    ({"BH_BLOOM_SEPQ_RAW": "3"}, GENERAL_FRAMES), ({"BH_BLOOM_SEPQ_MIN_BLOCKS": "100000"}, GENERAL_FRAMES),
-    ({"BH_BLOOM_CAP_PLAIN": "2", "BH_BLOOM_CAP_Y": "2", "BH_BLOOM_CAP_FINAL": "2"}, GENERAL_FRAMES),
     ({"BH_BLOOM_NO_STD": "1"}, STANDARD_FRAMES), ({"BH_BLOOM_NO_UP2": "1"}, STANDARD_FRAMES),
     ({"BH_BLOOM_NO_YQUAD": "1"}, STANDARD_FRAMES), ({"BH_BLOOM_NO_DOWN2": "1"}, STANDARD_FRAMES),
-    ({"BH_BLOOM_PERSIST": "1"}, STANDARD_FRAMES), ({"BH_BLOOM_NO_YDOWN2": "1"}, STANDARD_FRAMES),
+    ({"BH_BLOOM_NO_YDOWN2": "1"}, STANDARD_FRAMES),
     ({"BH_BLOOM_NO_GENERAL_COPIES": "1"}, ["1080x3840", "700x1000:any"])],
-    ids=["fix2", "org_keep", "no_strips", "fixup_norec", "fixup_sample", "no_sepq", "no_sep", "sepq_raw",
-         "sepq_min_blocks", "cap", "no_std", "no_up2", "no_yquad", "no_down2", "persist",
-         "no_ydown2", "no_general_copies"])
+    ids=["no_strips", "no_sepq", "no_sep", "no_std", "no_up2", "no_yquad", "no_down2", "no_ydown2",
+         "no_general_copies"])
 def test_bloom_switches_stay_bitexact(torch_cuda, env, frames):
     """Every run-time A/B switch of the chain (the library reads them once per process), in a child process each,
-    against the oracle bit for bit: on display sizes (the general fused chain: the final epilogue's in-block fix,
-    grid origins that keep the block count, the final fix-up from the row-major textures instead
-    of its column strips, the fix-up without its records, its per-sample form, the one-pixel separable kernel,
-    the per-pixel sampler, raw tiles, quad passes capped in blocks per CU) and on powers of two (the standard
-    plans: off, the general up pass instead of the 2:1 form, the Y pass one pixel per lane, no fused double
-    downsample, the persistent blocks, the two downsamples in their own pass instead of the Y pass), and sizes whose
+    against the oracle bit for bit: on display sizes (the general fused chain: the final fix-up from the row-major
+    textures instead of its column strips, the one-pixel separable kernel, the per-pixel sampler) and on powers of
+    two (the standard plans: off, the general up pass instead of the 2:1 form, the Y pass one pixel per lane, no
+    fused double downsample, the two downsamples in their own pass instead of the Y pass), and sizes whose
     same-size copies are not identities through the literal pass list instead of the general chain."""
     import os
     import subprocess

@@ -1,10 +1,10 @@
 // Host emulation of the final fix-up pass's global reads (bh_bloom.hip fixup_gather_kernel<EPI_FINAL> with its
 // records and column strips) and of the quad pass's strip writes (up_sepq_kernel's STRIPS epilogue), for one
 // frame size: every index each lane would form is checked against its buffer's size.  A debugging aid for a
-// GPU memory fault -- it runs on the CPU from the same host plan builders the library uploads.
-//   g++ -O1 -std=c++17 -c tools/bloom_fixup_addr.cpp -o /tmp/fa.o &&
-//   hipcc --offload-arch=gfx950 /tmp/fa.o black_hole_ray_marching_amd/_build/bh_bloom.o -o /tmp/fa
-//   /tmp/fa W H [W H ...]          or          /tmp/fa sweep N SEED MAXW MAXH
+// GPU memory fault -- it runs on the CPU from the same host plan builders the library uploads (bh_bloom_plan.cpp,
+// plain C++: any host compiler, with or without sanitizers).
+//   g++ -O1 -std=c++17 -ffp-contract=off tools/bloom_fixup_addr.cpp black_hole_ray_marching_amd/csrc/bh_bloom_plan.cpp -o fa
+//   ./fa W H [W H ...]          or          ./fa sweep N SEED MAXW MAXH
 // Exit status 1 when any index leaves its buffer.
 #include <cstdint>
 #include <cstdio>
@@ -13,10 +13,7 @@
 #include <string>
 #include <vector>
 
-extern "C" bool bh_bloom_same_plan(uint32_t w, uint32_t h, uint32_t* outp);
-extern "C" uint32_t bh_bloom_strip_table(uint32_t w, const uint32_t* list, uint32_t nc, uint32_t* stc);
-extern "C" void bh_bloom_fixup_records(uint32_t w, uint32_t h, const uint32_t* plan, const uint32_t* list, uint32_t nc,
-                                       uint32_t nr, uint32_t* out);
+#include "../black_hole_ray_marching_amd/csrc/bh_bloom_plan.hpp"
 
 static uint64_t bad = 0;
 static void check(const char* what, uint64_t idx, uint64_t n, uint64_t lane) {
