@@ -38,7 +38,7 @@ struct MarchArgs {
     // Uniforms (src/black_hole_maybe.wgsl:58-69)
     float rs, dtm, max_dist, dp;
     uint32_t blackout_eh;
-    uint32_t skip_sdf;         // the root-free step may run (bh_march.hpp, sdf_skip: dtm > 0, 0 < rs <= 8)
+    uint32_t skip_sdf;         // the root-free step may run (bh_march_step.hpp, sdf_skip_slack: dtm > 0, 0 < rs <= 8)
     float far_r2;              // r^2 beyond which a step needs no SDF argument (bh_host.cpp sdf_far_r2; +inf: off)
     // unused: the per-term radii of a root-free-step variant measured slower and removed;
     // kept so that the kernel argument layout -- and the kernels' machine code -- stay those measured
@@ -106,7 +106,7 @@ static_assert(offsetof(MarchArgs, order) == 144 && offsetof(MarchArgs, sky) == 2
 // The adaptive render's device-side work (bh_render_adaptive; bh_refine.hpp), a second kernel argument of
 // the two kernels that use it -- MarchArgs stays as the existing kernels were compiled against.  The detect
 // kernel (bh_tiles.hip) fills mask, list and counts from the plain frame in the frames' targets; the
-// work-list march (bh_march.hpp, march_refine_kernel) consumes the list.
+// work-list march (bh_march_tile.hpp, march_refine_kernel) consumes the list.
 struct RefineArgs {
     uint32_t* list;      // `capacity` entries of refine::ENTRY_WORDS words: frame, output tile
     uint32_t* ctr;       // [0] entries appended at the front, [1] at the back; from word REFINE_HEAD0 on the
@@ -119,7 +119,7 @@ struct RefineArgs {
     uint32_t tiles_x, tiles_y;  // its 8x8 tile grid
     uint32_t n_frames;
     uint32_t capacity;   // entries the list holds: n_frames * tiles_x * tiles_y at least
-    uint32_t n_heads;    // 1..REFINE_HEADS head words in use (bh_march.hpp, march_refine_kernel)
+    uint32_t n_heads;    // 1..REFINE_HEADS head words in use (bh_march_tile.hpp, march_refine_kernel)
     float thr;           // refine::threshold(format, T)
 };
 

@@ -9,7 +9,7 @@
 // on the device allow (tools/ubench/cr_forms.hip).  Each form is the SAME arithmetic as hipcc's
 // correctly-rounded expansion inside its safe domain, and each caller accumulates a "bad" flag for
 // operands outside that domain; the march loop then redoes that RK step with plain IEEE ops
-// (bh_march.hpp, march_step).  tests/test_gpu_crmath.py checks every form against IEEE results on
+// (bh_march_step.hpp, march_step_io).  tests/test_gpu_crmath.py checks every form against IEEE results on
 // ~10^9 inputs per form on the GPU (bh_selftest_crmath), including the boundaries.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -116,7 +116,7 @@ __device__ __forceinline__ float div12(float x) { return __builtin_fmaf(x, R12_H
 constexpr uint32_t KEY_MIN = (0x21800000u << 1) - 1u;  // key(2^-60)
 // The march's acceleration numerators s * p_i are held to the stricter 0 or >= 2^-40 (ACC_N_MIN): then
 // every acceleration component is 0 or >= 2^-100 (Q <= 2^60), which the fma form of the RK stage
-// directions relies on (bh_march.hpp, XOps::rd_half).  Still inside the division core's domain.
+// directions relies on (bh_march_ops.hpp, XOps::rd_half).  Still inside the division core's domain.
 constexpr float ACC_N_MIN = 0x1p-40f;
 constexpr uint32_t KEY_ACC_MIN = (0x2B800000u << 1) - 1u;  // key(2^-40)
 __device__ __forceinline__ uint32_t key(float n) { return (__float_as_uint(n) << 1) - 1u; }

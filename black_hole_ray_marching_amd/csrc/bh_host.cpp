@@ -438,7 +438,7 @@ int bh_render(bh_ctx* c, const bh_camera_uniform* cam, const bh_uniforms* U, con
     return bh_render_frames(c, 1u, cam, U, d, stream);
 }
 
-// The far-field radius of the root-free step (bh_march.hpp): r^2 beyond which every SDF term of a step
+// The far-field radius of the root-free step (bh_march_step.hpp, step_bf): r^2 beyond which every SDF term of a step
 // provably exceeds the root-free test's threshold T = RN(1.125 RN(dtm r) + 0.002) <= 1.1251 dtm R + 0.003
 // (R = |p| exact; the roundings of r, dtm r and T are within 2^-21 of R).  For a point at distance R:
 //   disc (:121)  >= R / sqrt2 - max(6 rs, 0.02)   (rho^2 + y^2 = R^2: rho or |y| is >= R / sqrt2, and the
@@ -459,7 +459,7 @@ static float sdf_far_r2(float rs, float dtm) {
     return std::nextafter((float)(R * R), INFINITY);
 }
 
-// A/B switch (diagnostics): BH_NO_SDF_SKIP set => every step evaluates its SDF roots (bh_march.hpp, sdf_skip)
+// A/B switch (diagnostics): BH_NO_SDF_SKIP set => every step evaluates its SDF roots (bh_march_step.hpp, sdf_skip_slack)
 static bool sdf_skip_disabled() {
     static const bool off = std::getenv("BH_NO_SDF_SKIP") != nullptr;
     return off;

@@ -21,7 +21,7 @@ namespace lens {
 
 constexpr uint32_t ROWS = 4;  // rows of 64 pixels per 256-thread workgroup
 
-// the output formats' stores: store_px's (bh_march.hpp), vector stores only
+// the output formats' stores: store_px's (bh_march_shade.hpp), vector stores only
 template <uint32_t FMT>
 __device__ __forceinline__ void store_texel(void* base, size_t idx, Rgb c, const float* enc) {
     if constexpr (FMT == BH_OUT_RGBA32F) {

@@ -2,7 +2,7 @@
 // here.  The shade kernel (bh_lens.hip) runs them per output pixel, bh_lens_shade_host (bh_mirror.cpp) runs the
 // very same functions in a loop on the CPU.  Both translation units are built without contraction, the device
 // one with correctly rounded fp32 sqrt, so every op here rounds once, as the same op of the march kernel's
-// shading does (bh_march.hpp: sample_sky, pow15_x, write_pixel's blackout test, ss_resolve's tree).
+// shading does (bh_march_shade.hpp: sample_sky, write_pixel's blackout test; bh_march_ops.hpp: pow15_x; bh_march_resolve.hpp: ss_resolve's tree).
 #pragma once
 #include <math.h>
 #include <stddef.h>
@@ -29,7 +29,7 @@ BH_LENS_HD Rgb decode(const float* lut, uint32_t t) { return {lut[t & 0xffu], lu
 // a sky holds at most 2^30 texels (bh_create, bh_sky_create): a 32-bit element index
 BH_LENS_HD uint32_t texel(const SkyView& s, int32_t x, int32_t y) { return s.texels[(uint32_t)y * s.w + (uint32_t)x]; }
 
-// textureSampleLevel on Rgba8UnormSrgb, mag Linear, clamp to edge: sample_sky's arithmetic (bh_march.hpp),
+// textureSampleLevel on Rgba8UnormSrgb, mag Linear, clamp to edge: sample_sky's arithmetic (bh_march_shade.hpp),
 // op for op.  A NaN coordinate takes texel (0, 0).
 BH_LENS_HD Rgb sample(const SkyView& s, const float* lut, float u, float v) {
     if (u != u || v != v) return decode(lut, texel(s, 0, 0));

@@ -1,4 +1,4 @@
-// The adaptive render's work-list march (bh_render_adaptive; bh_march.hpp, march_refine_kernel) in the
+// The adaptive render's work-list march (bh_render_adaptive; bh_march_tile.hpp, march_refine_kernel) in the
 // scheduled build's arithmetic and schedule (bh_march_exact_lat.hip), as a translation unit of its own: the
 // kernel is a loop of march_slot calls, and machine LICM hoists the march's loop invariants out of that loop and
 // keeps them live across it -- 129 VGPRs and 29 spilled SGPRs, 3 waves per SIMD, against 78 VGPRs and 6 waves

@@ -1,0 +1,290 @@
+// bh_march_tile.hpp -- the tile schedule (BH_SCHED_TILE, the default): one dispatch slot marched by one wave
+// (march_slot), the shader-clock probe, the plain, supersampled, lens and work-list kernels, and their launchers.
+// Needs bh_march_ray.hpp, bh_march_shade.hpp, bh_march_resolve.hpp and bh_refine.hpp (the work list).
+#pragma once
+#include "bh_march_ray.hpp"
+#include "bh_march_resolve.hpp"
+#include "bh_march_shade.hpp"
+#include "bh_refine.hpp"
+
+namespace bh {
+namespace BH_NS {
+
+// ---- schedule BH_SCHED_TILE: one wave64 = one 8x8 tile (default) ---------------------------------
+// Dispatch slot -> tile through `order` (previous frame's per-tile cost, expensive tiles first) or
+// the centre-out permutation; each wave records its tile's max n_rk for the next frame's order.
+// wave_max_u32: bh_common.hpp
+
+// The per-frame fields of frame f of a multi-frame launch: its camera (read before and in the march
+// loop) and its outputs (read after it).
+__device__ __forceinline__ void select_camera(MarchArgs& a, const FrameArgs& F) {
+    for (int k = 0; k < 3; ++k) {
+        a.pos[k] = F.pos[k]; a.c0[k] = F.c0[k]; a.c1[k] = F.c1[k]; a.c2[k] = F.c2[k]; a.cps[k] = F.cps[k];
+    }
+}
+__device__ __forceinline__ void select_outputs(MarchArgs& a, const FrameArgs& F) {
+    a.out_col = F.out_col; a.out_blackout = F.out_blackout;
+    a.dbg_n_rk = F.dbg_n_rk; a.dbg_fate = F.dbg_fate; a.dbg_steps = F.dbg_steps;
+}
+
+// Several frames in one launch (bh_render_frames): dispatch slot s is tile s / n_frames of the order
+// in frame s % n_frames, so every frame's expensive tiles start first and one frame's serial tail
+// overlaps the others' bulk instead of ending the launch alone.  Only frame 0
+// records the tile costs for the next launch's order (the histogram must count each tile once).
+//
+// One dispatch slot, marched by one wave.  SS: the supersampled form (march_tile_ss_kernel).  ITEM (with SS):
+// a work item of the adaptive render (march_refine_kernel) -- `slot` is the frame and (item_tx, item_ty) the
+// tile of the virtual frame, both given by the caller's work list: no dispatch order, no cost feedback.
+// LENS (exact math, march_tile_lens_kernel): the epilogue stores the ray's lens record instead of shading it;
+// `lut` is not read.
+template <uint32_t FMT, uint32_t SF, bool SS = false, bool ITEM = false, bool LENS = false>
+__device__ __forceinline__ void march_slot(const MarchArgs& A, uint32_t slot, const float* lut,
+                                           uint32_t lane, uint32_t item_tx = 0u, uint32_t item_ty = 0u) {
+    static_assert(SS || !ITEM, "work items are supersampled tiles");
+    static_assert(!LENS || (!SS && !BH_FAST), "a lens is one record per ray, in exact math");
+    const uint32_t nf = A.n_frames;
+    uint32_t fi = 0, j = slot;
+    if constexpr (ITEM) {
+        fi = slot;
+    } else if (nf > 1u) {
+        j = slot / nf;
+        fi = slot - j * nf;
+    }
+    MarchArgs a = A;
+    // frames[0] == the top-level fields for a one-frame launch; launches of more than
+    // BH_INLINE_FRAMES frames read them from the device table (wave-uniform index: one load per wave)
+    if (A.frame_table) select_camera(a, A.frame_table[fi]);
+    else select_camera(a, A.frames[fi]);
+    if (ITEM || fi != 0u) a.tile_cost = nullptr;
+    uint32_t t = 0u, tx, ty;
+    if constexpr (ITEM) {
+        tx = item_tx;
+        ty = item_ty;
+    } else {
+    t = a.order ? a.order[j] : centre_out(j, a.n_tiles, a.order_block, a.order_centre);
+    if (t >= a.n_tiles) return;  // defensive: a corrupt order must not address outside the shard
+    if (a.tile_list) {  // weighted partition (bh_partition): the shard's tile list
+        const uint32_t v = a.tile_list[t];
+        tx = v & 0xFFFFu;
+        ty = v >> 16;
+    } else {
+        shard_tile_coords(t, a.tiles_x, a.shard_index, a.shard_count, &tx, &ty);
+    }
+    }
+    const uint32_t px = tx * 8u + (lane & 7u), py = ty * 8u + (lane >> 3);
+    const bool valid = px < a.width && py < a.height;
+    const Frame f = make_frame(a);
+    RayState st;
+    st.ro = f.ro0;
+    st.rd = pixel_ray(a, valid ? px : 0u, valid ? py : 0u);
+    st.s = ray_s(f, st.rd);
+    st.travelled = 0.0f;
+    st.n_rk = 0;
+    st.outside = 0u;
+    uint32_t fate = 0xFFu, steps = 0;
+    if (valid) {
+        // the camera outside the unit sphere (1.01 leaves room for any rounding of |ro0|^2 against the
+        // step's own r^2 > 1 + 2^-23 at iteration 0) and |s| <= 2^30 on every lane: the step without the
+        // ingoing test and the |s| guard (wave-uniform: a scalar branch)
+        if constexpr (SF != SF_DYN) {
+            const bool out = (dot(f.ro0, f.ro0) > 1.01f) && (__builtin_amdgcn_ballot_w64(!(fabsf(st.s) <= 0x1p30f)) == 0ull);
+            if (__builtin_amdgcn_readfirstlane((int)out)) march_ray<SF | SF_CAM_OUT>(a, f, st, fate, steps, lane);
+            else march_ray<SF>(a, f, st, fate, steps, lane);
+        } else {
+            march_ray<SF>(a, f, st, fate, steps, lane);
+        }
+    }
+    if constexpr (SS) {
+        // every lane takes the resolve (its butterfly reads the wave's other lanes); invalid lanes hold 0
+        uint32_t fo = fi;
+        asm volatile("" : "+s"(fo));
+        if (A.frame_table) select_outputs(a, A.frame_table[fo]);
+        else select_outputs(a, A.frames[fo]);
+        v3 sc, sb;
+        ss_samples(a, lut, lane, valid, fate, st, steps, sc, sb);
+        ss_resolve_store<FMT>(a, lut, lane, px, py, valid, sc, sb);
+    } else
+    if (valid) {
+        // the frame's output pointers are loaded here, from an opaque copy of the frame index: loaded
+        // up front they would hold 10 SGPRs through the march loop, over the 80 that keep 8
+        // workgroups per CU resident (MI355X_MICROARCH.md, Residency)
+        uint32_t fo = fi;
+        asm volatile("" : "+s"(fo));
+        if (A.frame_table) select_outputs(a, A.frame_table[fo]);
+        else select_outputs(a, A.frames[fo]);
+#if !BH_FAST
+        if constexpr (LENS) {
+            // out_col is the lens (bh_render_lens: row-major, whole frame): one 8-byte vector store per lane
+            reinterpret_cast<float2*>(a.out_col)[(size_t)py * a.width + px] = lens_record(fate, st.rd);
+        } else
+#endif
+        {
+        const v3 col = shade(a, lut, fate, st.rd);
+        write_pixel<FMT>(a, lut, out_index(a, t, lane, px, py), col, st.n_rk, fate, steps);
+        }
+    }
+    if (a.tile_cost) {
+        // the next frame's cost and its bucket histogram (a no-return atomic: the wave does not wait);
+        // the last bucket is the remainder and is not counted
+        const uint32_t m = min(wave_max_u32(steps) >> 1, 255u);
+        if (lane == 0u) {
+            a.tile_cost[t] = (uint8_t)m;
+            const uint32_t b = cost_bucket(m);
+            if (b < ORDER_BUCKETS - 1u)
+                __hip_atomic_fetch_add(&a.order_tot[b], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        }
+    }
+}
+
+// Shader-clock probe (bh_set_clock_probe): a sampled wave reads both counters when it starts and adds
+// the differences at its end to its XCD's accumulators (vector atomics from lane 0, no return).  (A
+// divergent lane-0 branch before the march trips an "illegal VGPR to SGPR copy" in this compiler, so
+// the start values are held in 2 SGPRs instead: their low 32 bits, since a wave lives far less than
+// 2^32 shader cycles.)
+struct ClockStart { uint32_t t, r; };
+__device__ __forceinline__ ClockStart clock_start() {
+    return {(uint32_t)__builtin_amdgcn_s_memtime(), (uint32_t)__builtin_amdgcn_s_memrealtime()};
+}
+__device__ __forceinline__ void clock_end(unsigned long long* acc, const ClockStart& c0) {
+    const uint32_t t = (uint32_t)__builtin_amdgcn_s_memtime() - c0.t;      // shader clock
+    const uint32_t r = (uint32_t)__builtin_amdgcn_s_memrealtime() - c0.r;  // constant 100 MHz
+    const uint32_t x = __builtin_amdgcn_s_getreg((3 << 11) | (0 << 6) | 20) & 7u;  // HW_REG_XCC_ID[2:0]
+    // a sample whose ratio is outside 0.5-4 GHz is dropped: a wave saved and restored elsewhere (queue
+    // preemption) reads another XCD's shader counter at its end (seen once: 20 GHz on two XCDs)
+    const bool sane = (uint64_t)t >= 5ull * r && (uint64_t)t <= 40ull * r;
+    if ((threadIdx.x & 63u) == 0u && sane) {
+        unsigned long long* p = acc + 16u * x;
+        __hip_atomic_fetch_add(p, (unsigned long long)t, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        __hip_atomic_fetch_add(p + 1, (unsigned long long)r, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        __hip_atomic_fetch_add(p + 2, 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+}
+
+// One wave of the tile schedule: its dispatch slot (the grid covers every slot, WG_WAVES waves per workgroup),
+// marched with march_slot's SS / LENS form, between the clock probe's two readings.
+template <uint32_t FMT, uint32_t SF, bool SS, bool LENS = false>
+__device__ __forceinline__ void march_tile_wave(const MarchArgs& A, const float* lut) {
+    const uint32_t slot = __builtin_amdgcn_readfirstlane(blockIdx.x * WG_WAVES + (threadIdx.x >> 6));
+    if (slot >= A.n_tiles * A.n_frames) return;  // wave-uniform
+    // one slot in `stride`, rotated by slot / stride: the dispatcher deals workgroups to the 8 XCDs
+    // round robin, so plain multiples of the stride would all land on one XCD
+    const bool probe = A.clk && ((slot + (slot >> 8)) & A.clk_mask) == 0u;
+    ClockStart c0{0u, 0u};
+    if (probe) c0 = clock_start();
+    march_slot<FMT, SF, SS, false, LENS>(A, slot, lut, threadIdx.x & 63u);
+    if (probe) clock_end(A.clk, c0);
+}
+
+// The plain form: march_tile_wave<FMT, SF, false>, written out.  (Called through the helper -- whole, or only
+// its probe and march_slot -- the eight RGBA16F instantiations of this kernel come out at the same size with
+// other register numbers and instruction order in their store epilogue; the supersampled and lens kernels keep
+// their machine code either way: profiles/r12/march_split/.)
+template <uint32_t FMT, uint32_t SF>
+__global__ void __launch_bounds__(64 * WG_WAVES) march_tile_kernel(MarchArgs A) {
+    __shared__ float lut[lds_tables<FMT>()];
+    load_tables<FMT, 64u * WG_WAVES>(A, lut);
+    __syncthreads();
+    const uint32_t slot = __builtin_amdgcn_readfirstlane(blockIdx.x * WG_WAVES + (threadIdx.x >> 6));
+    if (slot >= A.n_tiles * A.n_frames) return;  // wave-uniform
+    const bool probe = A.clk && ((slot + (slot >> 8)) & A.clk_mask) == 0u;  // as march_tile_wave
+    ClockStart c0{0u, 0u};
+    if (probe) c0 = clock_start();
+    march_slot<FMT, SF>(A, slot, lut, threadIdx.x & 63u);
+    if (probe) clock_end(A.clk, c0);
+}
+
+// The tile schedule's supersampled form (bh_render_ss, ss > 1): the same waves over the virtual frame's
+// tiles -- order, cost feedback, cycle fast-forward, frame interleave and shading as march_tile_kernel --
+// with the k x k resolve as the epilogue (ss_resolve_store).  k is a run-time value (a.ss_log2): one more
+// kernel per format and scene-flag fold, not three.
+template <uint32_t FMT, uint32_t SF>
+__global__ void __launch_bounds__(64 * WG_WAVES) march_tile_ss_kernel(MarchArgs A) {
+    __shared__ float lut[lds_tables<FMT>()];
+    load_tables<FMT, 64u * WG_WAVES>(A, lut);
+    __syncthreads();
+    march_tile_wave<FMT, SF, true>(A, lut);
+}
+
+#if !BH_FAST
+// The tile schedule's lens form (bh_render_lens): march_tile_kernel's waves -- order, cost feedback, cycle
+// fast-forward -- with the lens record as the epilogue: no sky, no tables, no encode, one kernel per
+// scene-flag fold.
+template <uint32_t SF>
+__global__ void __launch_bounds__(64 * WG_WAVES) march_tile_lens_kernel(MarchArgs A) {
+    march_tile_wave<BH_OUT_RGBA32F, SF, false, true>(A, nullptr);
+}
+#endif
+
+// The adaptive render's second pass (bh_render_adaptive; bh_refine.hpp): the supersampled march over a work
+// list that the detect kernel (bh_tiles.hip) left on the device.  The host never learns the list's length, so
+// the grid is a bounded number of waves (RefineArgs::capacity bounds the list, the launcher the grid) and each
+// wave pulls work items until they pass entries * k^2: lane 0's vector atomic on a head word, broadcast.  One
+// head word serves about 88 pulls per microsecond however many waves pull (MI355X), less than these waves ask
+// for, so the items are dealt to R.n_heads heads (item i to head i % n_heads, its pulls in order, each head on
+// a 128-byte line of its own): a wave starts on head blockIdx % n_heads -- workgroups go to the XCDs round
+// robin -- and moves to the next head when one is exhausted, after a plain look at it.  An
+// item marches one tile of the virtual frame with march_slot's supersampled code -- ray, march, samples,
+// resolve and stores are march_tile_ss_kernel's, so a refined pixel holds bh_render_ss's bytes -- and reads or
+// writes no order state (A.order, A.tile_cost and A.order_tot are null).  An entry or a virtual tile out of
+// range touches no memory.
+template <uint32_t FMT, uint32_t SF>
+__global__ void __launch_bounds__(64 * WG_WAVES) march_refine_kernel(MarchArgs A, RefineArgs R) {
+    __shared__ float lut[lds_tables<FMT>()];
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t lk = A.ss_log2;
+    const uint32_t n_front = __builtin_amdgcn_readfirstlane(
+        min(__hip_atomic_load(R.ctr, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT), R.capacity));
+    const uint32_t n_back = __builtin_amdgcn_readfirstlane(
+        min(__hip_atomic_load(R.ctr + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT), R.capacity - n_front));
+    const uint32_t total = (n_front + n_back) << (2u * lk);  // <= 0xFFFF0000 (bh_host.cpp)
+    if (total == 0u) return;  // nothing refined (the same for every wave of the launch): no table, no pull
+    load_tables<FMT, 64u * WG_WAVES>(A, lut);
+    __syncthreads();
+    const uint32_t nh = R.n_heads ? R.n_heads : 1u;
+    uint32_t q = (blockIdx.x * WG_WAVES + (threadIdx.x >> 6)) % nh, tried = 0u;
+    while (tried < nh) {  // wave-uniform throughout
+        uint32_t* head = R.ctr + REFINE_HEAD0 + REFINE_HEAD_STRIDE * q;
+        // pull n of head q is item n * nh + q; a head seen exhausted is not pulled from again
+        uint32_t n = 0xFFFFFFFFu;
+        if (tried == 0u || (uint64_t)__builtin_amdgcn_readfirstlane(__hip_atomic_load(head, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) * nh + q < total) {
+            if (lane == 0u) n = __hip_atomic_fetch_add(head, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            n = __builtin_amdgcn_readfirstlane(n);
+        }
+        const uint64_t item64 = (uint64_t)n * nh + q;
+        if (item64 >= total) {
+            q = q + 1u == nh ? 0u : q + 1u;
+            ++tried;
+            continue;
+        }
+        const uint32_t item = (uint32_t)item64;
+        const uint32_t* e = R.list + (size_t)refine::ENTRY_WORDS * refine::entry_slot(refine::item_entry(item, lk), n_front, R.capacity);
+        const uint32_t fi = __builtin_amdgcn_readfirstlane(e[0]), tile = __builtin_amdgcn_readfirstlane(e[1]);
+        uint32_t vtx, vty;
+        if (fi >= A.n_frames ||
+            !refine::item_tile(tile, refine::item_sub(item, lk), lk, R.tiles_x, R.tiles_y, A.tiles_x, A.tiles_y, &vtx, &vty))
+            continue;
+        march_slot<FMT, SF, true, true>(A, fi, lut, lane, vtx, vty);
+        __builtin_amdgcn_s_setprio(0);  // a tail wave raised it (march_ray); the next item starts as any wave does
+    }
+}
+
+// Host side: launch the tile schedule, one wave per dispatch slot; `kernel` is march_tile_kernel, its
+// supersampled form (a.ss_log2 in 1..3, the geometry fields the virtual frame's) or its lens form (a.lens set,
+// out_col the lens).  (A persistent form -- resident
+// waves claiming slots in order from one device-scope counter -- measured 2.5x slower: a returning
+// atomic on one word is serialised across the 8 XCDs at ~85 M claims/s)
+template <class K>
+inline void launch_tile_schedule(K kernel, const MarchArgs& a, hipStream_t s) {
+    const uint32_t waves = a.n_tiles * a.n_frames;
+    const uint32_t blocks = (waves + (WG_WAVES - 1u)) / WG_WAVES;
+    hipLaunchKernelGGL(kernel, dim3(blocks), dim3(64u * WG_WAVES), 0, s, a);
+}
+// ... and the adaptive render's work-list march: `waves` resident waves that pull (march_refine_kernel)
+template <uint32_t FMT, uint32_t SF>
+inline void launch_refine_schedule(const MarchArgs& a, const RefineArgs& r, uint32_t waves, hipStream_t s) {
+    const uint32_t blocks = (waves + (WG_WAVES - 1u)) / WG_WAVES;
+    hipLaunchKernelGGL((march_refine_kernel<FMT, SF>), dim3(blocks), dim3(64u * WG_WAVES), 0, s, a, r);
+}
+
+}  // namespace BH_NS
+}  // namespace bh

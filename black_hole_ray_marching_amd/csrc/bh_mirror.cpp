@@ -12,7 +12,7 @@
 extern "C" {
 
 // The supersampled march kernel's epilogue on the host: the functions of bh_ss.hpp that each lane of a wave
-// runs (ss_resolve_store, bh_march.hpp), run here wave by wave over 64-entry arrays -- one 8x8 tile of the
+// runs (ss_resolve_store, bh_march_resolve.hpp), run here wave by wave over 64-entry arrays -- one 8x8 tile of the
 // virtual frame per wave, invalid lanes 0, every lane taking each butterfly level together.
 int bh_ss_resolve_host(const float* samples, uint32_t width, uint32_t height, uint32_t ss, float* out) {
     const uint32_t lk = bh::ss::log2_k(ss);

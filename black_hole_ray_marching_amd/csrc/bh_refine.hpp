@@ -1,7 +1,7 @@
 // bh_refine.hpp — lane logic of the adaptive supersampled render (bh_render_adaptive): which 8x8 OUTPUT
 // tiles of a plain frame show an edge, and which tiles of the virtual frame (bh_ss.hpp) re-march them.
 // Host and device share every function here: the detect kernel (bh_tiles.hip) and the work-list march
-// (bh_march.hpp, march_refine_kernel) run them per lane / per wave, bh_refine_mask_host and
+// (bh_march_tile.hpp, march_refine_kernel) run them per lane / per wave, bh_refine_mask_host and
 // bh_refine_cover_host (bh_mirror.cpp) run the very same functions lane by lane.
 //
 // The rule (normative, include/bh_render.h): a pixel is an edge pixel when it differs from one of its

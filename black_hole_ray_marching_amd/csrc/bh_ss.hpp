@@ -1,6 +1,6 @@
 // bh_ss.hpp — lane logic of the supersampled render (bh_render_ss): k x k rays per output pixel, k in
 // {2, 4, 8}, resolved inside the wave that marched them.  Host and device share every function here: the
-// march kernel's epilogue (bh_march.hpp, ss_resolve_store) runs them per lane, bh_ss_resolve_host
+// march kernel's epilogue (bh_march_resolve.hpp, ss_resolve_store) runs them per lane, bh_ss_resolve_host
 // (bh_mirror.cpp) runs the very same functions over a 64-entry array per wave.
 //
 // A wave64 owns one 8x8 tile of the VIRTUAL frame (kW x kH), lane = (y & 7) * 8 + (x & 7).  k divides 8,

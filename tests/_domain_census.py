@@ -18,8 +18,8 @@ DIV_D_MAX = f32(2.0 ** 60)     # bh_crmath.hpp  crm::DIV_D_MAX  (div_d_bad: Q <=
 ACC_N_MIN = f32(2.0 ** -40)    # bh_crmath.hpp  crm::ACC_N_MIN / KEY_ACC_MIN  (step_bf: kmin, amin)
 DIV_N_MIN = f32(2.0 ** -60)    # bh_crmath.hpp  crm::DIV_N_MIN  (step_bf: amin6, the x/6 numerators)
 SQRT_MIN = f32(2.0 ** -96)     # bh_crmath.hpp  crm::SQRT_MIN   (sqrt_bad, sqrt_bad2)
-DT_MIN = f32(2.0 ** -25)       # bh_march.hpp   step_bf, "rd_half's premise": |dt| >= 0x1p-25f or dt == 0
-S_MAX = f32(2.0 ** 30)         # bh_march.hpp   step_bf / the pair step / march_slot's ballot: |s| <= 0x1p30f
+DT_MIN = f32(2.0 ** -25)       # bh_march_step.hpp   step_bf, "rd_half's premise": |dt| >= 0x1p-25f or dt == 0
+S_MAX = f32(2.0 ** 30)         # bh_march_step.hpp   step_bf / the pair step; bh_march_tile.hpp march_slot's ballot: |s| <= 0x1p30f
 
 COUNTERS = ("q_hi", "q_lo", "n_lo", "n6_lo", "dt_tiny", "dt_zero", "dt_neg", "root_lo", "nonfinite")
 

@@ -82,7 +82,7 @@ def test_full_frame_bitexact(torch_cuda, sky_full, cid, W, H, cap, cam, flags, f
     scene.camera_uniform = cu
     oc, ob, on, of = oracle.render_rows(cu.to_bytes(), bytes(U.to_c()), sky_full, W, H, cap, flags)
     # first frame (centre-out order) and second (learned cost order); then both exact builds forced (camera B:
-    # photon-sphere rays whose tail steps take the tiny-dt form, bh_march.hpp step_bf TINY / step_tail)
+    # photon-sphere rays whose tail steps take the tiny-dt form, bh_march_step.hpp step_bf TINY / step_tail)
     scheds = [0, 0] + ([bh.BH_SCHED_FLAG_ISSUE_ORDER, bh.BH_SCHED_FLAG_LATENCY] if cam == "B" else [])
     for frame, sched in enumerate(scheds):
         gc, gb, gn, gf = render_full(torch, scene, W, H, bh.BH_OUT_RGBA32F, dbg=True, schedule=sched)

@@ -1,5 +1,5 @@
 """GPU parity at the input edges the reference's key bindings reach (tests/_cases.py EDGE_CASES): the domain
-guards of the correctly rounded cores (bh_crmath.hpp, bh_march.hpp step_bf) and the host's specialisation
+guards of the correctly rounded cores (bh_crmath.hpp, bh_march_step.hpp step_bf) and the host's specialisation
 gates (bh_host.cpp fill_args, sdf_far_r2), with whole frames.
 
 tests/test_edge_inputs.py shows on the CPU that the oracle is well defined on every case and that each case

@@ -186,7 +186,7 @@ def test_srgb_round_trip():
 
 
 def test_exit_tests_on_r_squared_equal_tests_on_r():
-    # The kernel's blackout/outside tests (bh_march.hpp step_bf) read r2 = dot(ro, ro) instead of
+    # The kernel's blackout/outside tests (bh_march_step.hpp step_bf) read r2 = dot(ro, ro) instead of
     # r = RN(sqrt(r2)) (src/black_hole_maybe.wgsl:271-283 compares r with 1):
     #   r < 1 <=> r2 < 1   and   r > 1 <=> r2 > 1 + 2^-23.
     # RN(sqrt) is monotone, so checking every float in [1/4, 4] (both sides of both thresholds)
@@ -202,7 +202,7 @@ def test_exit_tests_on_r_squared_equal_tests_on_r():
 
 
 def test_marker_pair_reduction():
-    # bh_march.hpp XOps::sdf evaluates the marker term (src/black_hole_maybe.wgsl:107-117) as
+    # bh_march_ops.hpp XOps::sdf_args evaluates the marker term (src/black_hole_maybe.wgsl:107-117) as
     # sqrt(min(qy, qx)) - 0.5 with qy = (x*x + t*t) + zz, t = RN(10 - |y|), qx = (u*u + y*y) + zz,
     # u = RN(10 - |x|): only the sphere on the point's side of each pair can be nearest.  Checked
     # bit for bit against the oracle's four-sphere min on random and adversarial points.

@@ -1,5 +1,5 @@
-"""The root-free march step (bh_march.hpp, sdf_skip): a lane that passes the test must have dt == dtm*r and
-no surface hit in the full step -- checked here on the step's own float32 arithmetic (numpy: IEEE
+"""The root-free march step (bh_march_step.hpp, sdf_term_slacks / sdf_skip_slack): a lane that passes the
+test must have dt == dtm*r and no surface hit in the full step -- checked here on the step's own float32 arithmetic (numpy: IEEE
 add/mul and correctly rounded sqrt, as the exact mode's cores), with samples packed against the test's
 thresholds and the dt boundary (src/black_hole_maybe.wgsl:285-310)."""
 import numpy as np
@@ -91,7 +91,7 @@ def term_slacks(flags, dtr, rho2, yy, qm, qps, rs):
 
 
 def step_without(flags, dtr, rho2, y, qm, qps, rs, skip_d, skip_m, skip_p):
-    """the per-term step (bh_march.hpp, BH_SDF_TERMS): a left-out term enters dist as +inf"""
+    """the per-term step (bh_march_step.hpp, sdf_term_slacks and step_bf's per-term arm): a left-out term enters dist as +inf"""
     rho = np.sqrt(rho2)
     inf = f32(np.inf)
     disc = np.where(skip_d, inf, np.fmax(np.fmax(rho - f32(6.0) * rs, -(rho - f32(3.0) * rs)), np.abs(y) - f32(0.02)))
@@ -150,7 +150,7 @@ def far_r2(rs, dtm):
 
 def step_from_point(p, rs, dtm, cam):
     """dt and the surface test of the full step at positions p (n, 3) float32 -- the exact mode's op
-    sequence from the position itself (bh_march.hpp sdf_args / sdf_from, :285-310)."""
+    sequence from the position itself (bh_march_ops.hpp sdf_args / sdf_from, :285-310)."""
     x, y, z = p[:, 0], p[:, 1], p[:, 2]
     r2 = (x * x + y * y) + z * z
     r = np.sqrt(r2)
@@ -171,7 +171,7 @@ def step_from_point(p, rs, dtm, cam):
 
 @pytest.mark.parametrize("rs,dtm", [(1.0, 0.5), (0.25, 0.5), (8.0, 0.5), (1.0, 0.1), (1.0, 0.6), (0.003, 0.3)])
 def test_far_field_implies_dt_equals_dtm_r(rs, dtm):
-    """bh_march.hpp's far-field level: every lane with far_r2 <= r^2 <= FLT_MAX has dt == RN(dtm r) and no
+    """bh_march_step.hpp's far-field level (step_bf): every lane with far_r2 <= r^2 <= FLT_MAX has dt == RN(dtm r) and no
     surface hit, checked on points just beyond the radius (all directions, the markers' and the disc plane's
     included) and far out."""
     rng = np.random.default_rng(int(rs * 1000 + dtm * 10))

@@ -1,5 +1,5 @@
 """Count guarded-fallback (IEEE) steps of the exact kernel, and the wave-steps that skipped the SDF roots
-(sdf_skip): BH_LIB=tools/variants/diag.so python tools/diag_slow.py  (diag.so: -DBH_DIAG_SLOW)"""
+(sdf_skip_slack, bh_march_step.hpp): BH_LIB=tools/variants/diag.so python tools/diag_slow.py  (diag.so: -DBH_DIAG_SLOW)"""
 import ctypes as C
 import sys
 from pathlib import Path

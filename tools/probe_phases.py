@@ -5,7 +5,8 @@
 run with BH_LIB=tools/variants/phases/libbh_render.so).
 
 The clock-probed waves (one in `stride`) add the shader cycles of five phases to their XCD's
-accumulator (bh_march.hpp, BH_DIAG_PHASES): tables staged, tile + pixel ray, march, shading + store,
+accumulator (the BH_DIAG_PHASES probes stood in march_slot, now bh_march_tile.hpp, until commit bbbdf1b pruned them;
+put them back to use this tool): tables staged, tile + pixel ray, march, shading + store,
 cost bookkeeping.  Prints the mean cycles per sampled wave and each phase's share of the lifetime, for
 the headline workload (4096x2048, cap 512, camera A, 32 frames per launch, RGBA16F, two targets).
     BH_LIB=tools/variants/phases/libbh_render.so python tools/probe_phases.py [--launches 20]
