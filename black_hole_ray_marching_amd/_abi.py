@@ -116,6 +116,12 @@ SIGNATURES = {
     "bh_render_frames_ss": (C.c_int, [C.c_void_p, C.c_uint32, C.POINTER(bh_camera_uniform), C.POINTER(bh_uniforms),
                                       C.POINTER(bh_render_desc), C.c_uint32, C.c_void_p]),
     "bh_ss_resolve_host": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p]),
+    "bh_render_shutter": (C.c_int, [C.c_void_p, C.c_uint32, C.POINTER(bh_camera_uniform), C.POINTER(bh_uniforms),
+                                    C.POINTER(bh_render_desc), C.c_uint32, C.c_void_p]),
+    "bh_render_frames_shutter": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(bh_camera_uniform),
+                                           C.POINTER(bh_uniforms), C.POINTER(bh_render_desc), C.c_uint32, C.c_void_p]),
+    "bh_shutter_resolve_host": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,
+                                          C.c_void_p]),
     "bh_render_adaptive": (C.c_int, [C.c_void_p, C.POINTER(bh_camera_uniform), C.POINTER(bh_uniforms),
                                      C.POINTER(bh_render_desc), C.POINTER(bh_adaptive_desc), C.c_void_p]),
     "bh_render_frames_adaptive": (C.c_int, [C.c_void_p, C.c_uint32, C.POINTER(bh_camera_uniform), C.POINTER(bh_uniforms),

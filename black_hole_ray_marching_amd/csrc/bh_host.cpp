@@ -16,6 +16,7 @@
 #include "bh_host.hpp"
 #include "bh_srgb.hpp"
 #include "bh_refine.hpp"
+#include "bh_shutter.hpp"
 #include "bh_ss.hpp"
 
 namespace {
@@ -492,6 +493,7 @@ struct Launch {
     bh::MarchArgs a;                   // the kernel argument
     std::vector<bh::FrameArgs> table;  // more than BH_INLINE_FRAMES frames: staged in the stream's device table
     uint64_t n_tiles = 0;              // the shard's tiles
+    uint32_t shutter_log2 = 0;         // bh_render_shutter: log2 of the cameras per output frame (a.n_frames counts cameras)
 };
 
 // Every argument check of a launch; no HIP call.  Leaves the launch's desc and tile count in L.
@@ -640,10 +642,16 @@ static int launch_march(bh_ctx* c, const Launch& L, bh_ctx::OrderState* os, hipS
     const bh_render_desc* d = &L.d;
     const bh::MarchArgs& a = L.a;
     const uint32_t sched = d->schedule & 0xFFu;
-    int e = d->math != BH_MATH_EXACT ? bh_launch_march_fast(a, sched, c->counters, c->grid_fast, s)
-            : march_variant_issue_order(d, a.n_tiles, a.n_frames, c->cus)
-                ? bh_launch_march_exact(a, sched, c->counters, c->grid_exact, s)
-                : bh_launch_march_exact_lat(a, sched, c->counters, c->grid_exact, s);
+    const bool issue = march_variant_issue_order(d, a.n_tiles, a.n_frames, c->cus);  // every camera's tiles
+    int e;
+    if (const uint32_t ln = L.shutter_log2)
+        e = d->math != BH_MATH_EXACT ? bh_launch_shutter_fast(a, ln, s)
+            : issue                  ? bh_launch_shutter_exact(a, ln, s)
+                                     : bh_launch_shutter_exact_lat(a, ln, s);
+    else
+        e = d->math != BH_MATH_EXACT ? bh_launch_march_fast(a, sched, c->counters, c->grid_fast, s)
+            : issue                  ? bh_launch_march_exact(a, sched, c->counters, c->grid_exact, s)
+                                     : bh_launch_march_exact_lat(a, sched, c->counters, c->grid_exact, s);
     if (e != 0) {
         // the costs and their histogram are written together by the march kernel; without it they
         // may disagree, so the next frame of this state starts the temporal order afresh
@@ -731,6 +739,44 @@ int bh_render_frames_ss(bh_ctx* c, uint32_t n_frames, const bh_camera_uniform* c
     const int st = check_launch(c, n_frames, cams, U, descs, ss, &L);
     if (st != BH_OK) return st;
     fill_args(c, n_frames, cams, U, descs, ss, &L);
+    return march_in_order(c, &L, cams, U, stream);
+}
+
+// ---- shutter renders (include/bh_render.h; the mapping and the tree: bh_shutter.hpp) -----------------------
+int bh_render_shutter(bh_ctx* c, uint32_t n_sub, const bh_camera_uniform* cams, const bh_uniforms* U,
+                      const bh_render_desc* d, uint32_t ss, void* stream) {
+    return bh_render_frames_shutter(c, 1u, n_sub, cams, U, d, ss, stream);
+}
+
+// The launch of n_frames * n_sub cameras as bh_render_frames(_ss) would launch them -- geometry, order state,
+// repeated-frame key (camera 0 of frame 0: the order it stands for is the same array of tiles whichever kernel
+// walks it), frame table -- marched by the shutter kernels: one FrameArgs entry per camera, the output pointers
+// of frame f in every entry of its group (a writer wave reads its own camera's entry).
+int bh_render_frames_shutter(bh_ctx* c, uint32_t n_frames, uint32_t n_sub, const bh_camera_uniform* cams,
+                             const bh_uniforms* U, const bh_render_desc* descs, uint32_t ss, void* stream) {
+    const uint32_t ln = bh::shutter::log2_n(n_sub);
+    if (ln > bh::shutter::MAX_LOG2 || bh::ss::log2_k(ss) > 3u) return bad_arg(__func__, __LINE__);
+    if (n_sub == 1u) return bh_render_frames_ss(c, n_frames, cams, U, descs, ss, stream);
+    if (!c || !cams || !U || !descs || n_frames == 0 || (uint64_t)n_frames * n_sub > BH_MAX_FRAMES) return bad_arg(__func__, __LINE__);
+    if (!frame_shape_ok(descs[0].width, descs[0].height, ss)) return bad_arg(__func__, __LINE__);
+    if (const char* why = ss_needs(descs, n_frames)) {
+        g_last_error = std::string("bh_render_shutter: a shutter render (n_sub > 1) needs ") + why + ".";
+        return BH_ERR_UNSUPPORTED;
+    }
+    const uint32_t n_cams = n_frames * n_sub;
+    std::vector<bh_render_desc> per_cam;
+    try {
+        per_cam.reserve(n_cams);
+    } catch (const std::bad_alloc&) {
+        return BH_ERR_OUT_OF_MEMORY;
+    }
+    for (uint32_t i = 0; i < n_cams; ++i) per_cam.push_back(descs[i / n_sub]);
+    Launch L;
+    const int st = check_launch(c, n_cams, cams, U, per_cam.data(), ss, &L);
+    if (st != BH_OK) return st;
+    fill_args(c, n_cams, cams, U, per_cam.data(), ss, &L);
+    L.a.ss_out_width = descs[0].width;  // the shutter kernels index the output through it at every ss
+    L.shutter_log2 = ln;
     return march_in_order(c, &L, cams, U, stream);
 }
 

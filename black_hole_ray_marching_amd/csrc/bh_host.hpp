@@ -193,6 +193,10 @@ BH_INTERNAL int bh_launch_march_exact_lat(const bh::MarchArgs& a, uint32_t sched
                 hipStream_t s);
 BH_INTERNAL int bh_launch_march_fast(const bh::MarchArgs& a, uint32_t schedule, uint32_t* counters, uint32_t grid,
                 hipStream_t s);
+// the shutter render's march: 2^ln cameras per output frame, a.n_frames cameras in all (ln in 1..4)
+BH_INTERNAL int bh_launch_shutter_exact(const bh::MarchArgs& a, uint32_t ln, hipStream_t s);
+BH_INTERNAL int bh_launch_shutter_exact_lat(const bh::MarchArgs& a, uint32_t ln, hipStream_t s);
+BH_INTERNAL int bh_launch_shutter_fast(const bh::MarchArgs& a, uint32_t ln, hipStream_t s);
 // the adaptive render's work-list march (a.ss_log2 in 1..3, `waves` pulling waves) and its detect kernel
 BH_INTERNAL int bh_launch_refine_exact(const bh::MarchArgs& a, const bh::RefineArgs& r, uint32_t waves, hipStream_t s);
 BH_INTERNAL int bh_launch_refine_exact_lat(const bh::MarchArgs& a, const bh::RefineArgs& r, uint32_t waves,

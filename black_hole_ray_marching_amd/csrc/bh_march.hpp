@@ -18,8 +18,8 @@
 //   bh_march_step.hpp     one iteration: the ray state, the root-free tests, step_bf, the packed tail step
 //   bh_march_shade.hpp    sky sample, shading, the output encoders, write_pixel
 //   bh_march_ray.hpp      one ray to its end: the ping-pong loop, the tail's cycle fast-forward
-//   bh_march_resolve.hpp  the supersampled render's resolve in the wave
-//   bh_march_tile.hpp     the tile schedule: march_slot, the tile / ss / lens / work-list kernels
+//   bh_march_resolve.hpp  the supersampled render's resolve in the wave, the shutter render's in the workgroup
+//   bh_march_tile.hpp     the tile schedule: march_slot, the tile / ss / shutter / lens / work-list kernels
 //   bh_march_alt.hpp      the persistent and pair schedules (A/B options)
 #pragma once
 #include <hip/hip_runtime.h>
@@ -88,6 +88,17 @@ __attribute__((visibility("hidden"))) inline int launch_march(const MarchArgs& a
             if (e != hipSuccess) return (int)e;
             hipLaunchKernelGGL(march_persistent_kernel<FMT>, dim3(grid), dim3(256), 0, s, a, counters);
         }
+        return (int)hipGetLastError();
+    });
+}
+// The shutter render's march (bh_render_shutter, n = 2^ln cameras per output frame; tile schedule): the same folds.
+template <bool FOLD_NONE>
+__attribute__((visibility("hidden"))) inline int launch_shutter(const MarchArgs& a, uint32_t ln, hipStream_t s) {
+    if (ln == 0u || ln > shutter::MAX_LOG2 || (a.n_frames & ((1u << ln) - 1u)) != 0u) return (int)hipErrorInvalidValue;
+    return with_format(a.format, [&](auto fmt) {
+        with_scene_fold<FOLD_NONE>(a.scene_flags, [&](auto sf) {
+            launch_shutter_schedule<decltype(fmt)::value, decltype(sf)::value>(a, ln, s);
+        });
         return (int)hipGetLastError();
     });
 }

@@ -13,6 +13,7 @@
 #define BH_NS exact
 #define BH_EXACT_LAUNCH bh_launch_march_exact
 #define BH_EXACT_BLOCKS bh_march_blocks_per_cu_exact
+#define BH_EXACT_SHUTTER bh_launch_shutter_exact
 #define BH_EXACT_REFINE bh_launch_refine_exact
 #define BH_EXACT_AUX 1
 #endif
@@ -29,6 +30,10 @@ extern "C" __attribute__((visibility("hidden"))) int BH_EXACT_BLOCKS(void) {
     int n = 0;
     if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, bh::BH_NS::march_persistent_kernel<BH_OUT_BGRA8_SRGB>, 256, 0) != hipSuccess) return 1;
     return n > 0 ? n : 1;
+}
+// The shutter render's march (bh_render_shutter): 2^ln cameras per output frame.
+extern "C" __attribute__((visibility("hidden"))) int BH_EXACT_SHUTTER(const bh::MarchArgs& a, uint32_t ln, hipStream_t s) {
+    return bh::BH_NS::launch_shutter<true>(a, ln, s);
 }
 #endif  // BH_REFINE_ONLY
 

@@ -5,4 +5,5 @@
 #define BH_TAIL_PACKED 1
 #define BH_EXACT_LAUNCH bh_launch_march_exact_lat
 #define BH_EXACT_BLOCKS bh_march_blocks_per_cu_exact_lat
+#define BH_EXACT_SHUTTER bh_launch_shutter_exact_lat
 #include "bh_march_exact.hip"

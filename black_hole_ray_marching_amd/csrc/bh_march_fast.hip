@@ -13,6 +13,9 @@ extern "C" __attribute__((visibility("hidden"))) int bh_launch_refine_fast(const
                                                                          uint32_t waves, hipStream_t s) {
     return bh::fast::launch_refine<false>(a, r, waves, s);
 }
+extern "C" __attribute__((visibility("hidden"))) int bh_launch_shutter_fast(const bh::MarchArgs& a, uint32_t ln, hipStream_t s) {
+    return bh::fast::launch_shutter<false>(a, ln, s);
+}
 // Resident 256-thread blocks per CU of the persistent kernel (sizes its grid: every block resident).
 extern "C" __attribute__((visibility("hidden"))) int bh_march_blocks_per_cu_fast(void) {
     int n = 0;

@@ -58,6 +58,18 @@ __device__ __forceinline__ HistLds* hist_lds() {
     __shared__ HistLds hist[WG_WAVES];
     return hist;
 }
+// The shutter kernel's workgroups (march_tile_shutter_kernel: n waves, n a launch-time value) hold their n
+// areas at the start of the dynamic LDS instead, the tables behind them.
+__device__ __forceinline__ HistLds* shutter_hist_lds() {
+    extern __shared__ float4 shutter_lds[];
+    return reinterpret_cast<HistLds*>(shutter_lds);
+}
+// This wave's area; SHUT: in a workgroup of the shutter kernel.
+template <bool SHUT>
+__device__ __forceinline__ HistLds& wave_hist() {
+    if constexpr (SHUT) return shutter_hist_lds()[threadIdx.x >> 6];
+    else return hist_lds<0>()[threadIdx.x >> 6];
+}
 
 // March `st` to termination with the fast-forward; `steps` = RK updates actually executed.
 // (The tail waves are latency-bound: a ping-pong / uniform-trip form of this loop measured slower.)
@@ -104,7 +116,7 @@ __device__ __forceinline__ uint32_t march_cycles(const MarchArgs& a, const Frame
 }
 
 // March one ray to its end (the tile schedule's loop): `fate` and `steps` (RK updates executed).
-template <uint32_t SF>
+template <uint32_t SF, bool SHUT = false>
 __device__ __forceinline__ void march_ray(const MarchArgs& a, const Frame& f, RayState& st, uint32_t& fate,
                                           uint32_t& steps, uint32_t lane) {
     // Two iterations per trip, ping-ponging the state between st and sb (march_step_io never
@@ -149,7 +161,7 @@ __device__ __forceinline__ void march_ray(const MarchArgs& a, const Frame& f, Ra
         // photon-sphere ray that may run to the cap: raise its issue priority so its serial chain
         // is not stretched by the SIMD's other waves (the frame's tail), and watch for cycles.
         __builtin_amdgcn_s_setprio(2);
-        fate = march_cycles<SF>(a, f, st, steps, hist_lds<0>()[threadIdx.x >> 6], lane);
+        fate = march_cycles<SF>(a, f, st, steps, wave_hist<SHUT>(), lane);
     }
 }
 

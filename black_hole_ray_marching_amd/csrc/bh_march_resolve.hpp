@@ -1,10 +1,13 @@
 // bh_march_resolve.hpp -- the supersampled render's resolve, in the wave: a ray's two samples (ss_samples; the
 // fast build stages them through the wave's LDS area, ss_stage_sample), the butterfly over the k x k group
-// (ss_lane_xor, ss_level, ss_resolve) and the group's store (ss_resolve_store).  Needs bh_march_shade.hpp,
-// bh_march_ray.hpp (the LDS area) and bh_ss.hpp (the level sequence, shared with the host).
+// (ss_lane_xor, ss_level, ss_resolve) and the group's store (ss_resolve_store); and the shutter render's resolve
+// across the waves of a workgroup (shutter_stage, shutter_resolve_store).  Needs bh_march_shade.hpp,
+// bh_march_ray.hpp (the LDS area), bh_ss.hpp and bh_shutter.hpp (the level sequence and the time tree, shared with
+// the host).
 #pragma once
 #include "bh_march_ray.hpp"
 #include "bh_march_shade.hpp"
+#include "bh_shutter.hpp"
 #include "bh_ss.hpp"
 
 namespace bh {
@@ -45,10 +48,12 @@ __device__ __forceinline__ void ss_stage_sample(const MarchArgs& a, const float*
 }
 #endif
 // The two samples of this lane's ray (0 for a lane outside the virtual frame); every lane of the wave.
+// SHUT: a wave of the shutter kernel (its LDS area: wave_hist).
+template <bool SHUT = false>
 __device__ __forceinline__ void ss_samples(const MarchArgs& a, const float* lut, uint32_t lane, bool valid, uint32_t fate,
                                            const RayState& st, uint32_t steps, v3& sc, v3& sb) {
 #if BH_FAST
-    float4* tiles = reinterpret_cast<float4*>(&hist_lds<0>()[threadIdx.x >> 6]) + SS_TILES_AT;
+    float4* tiles = reinterpret_cast<float4*>(&wave_hist<SHUT>()) + SS_TILES_AT;
     if (valid) {
         ss_stage_sample(a, lut, tiles, lane, shade(a, lut, fate, st.rd), st.n_rk, fate, steps);
     } else {
@@ -137,6 +142,47 @@ __device__ __forceinline__ void ss_resolve_store(const MarchArgs& a, const float
         ss_resolve(v, lk, lane);
         if (w) store_px<FMT>(a.out_col, idx, mk(v[0], v[1], v[2]), tab + 256);
     }
+}
+
+// ---- shutter render (bh_render_shutter): the resolve of n cameras per output frame, in the workgroup ----
+// Wave w of a workgroup marched the tile with camera w (bh_shutter.hpp).  Once its march has ended it leaves
+// its lanes' six sample channels in its OWN history area -- a plane of 64 floats per channel, beside the fast
+// build's sample tiles, which ss_samples has read by then -- and after the workgroup's barrier the writer lanes
+// of one wave per target read the n waves' planes in bh_shutter.hpp's tree order.
+// float offset of channel plane c (0..2 col, 3..5 blackout_col) in a wave's area
+__host__ __device__ constexpr uint32_t shutter_plane_at(uint32_t c) { return c < 4u ? c * 64u : 768u + (c - 4u) * 64u; }
+static_assert(shutter_plane_at(5u) + 64u <= sizeof(HistLds) / sizeof(float), "the sample planes fit the history area");
+#if BH_FAST
+static_assert(shutter_plane_at(3u) + 64u <= SS_TILES_AT * 4u && shutter_plane_at(4u) >= (SS_TILES_AT + 2u * 64u) * 4u,
+              "the sample planes lie beside the fast build's sample tiles");
+#endif
+// This lane's samples (ss > 1: its k x k group's resolved pixel, in every lane of the group) into the wave's
+// planes; every lane of the wave, invalid lanes hold 0.
+__device__ __forceinline__ void shutter_stage(const MarchArgs& a, const float* lut, uint32_t lane, bool valid,
+                                              uint32_t fate, const RayState& st, uint32_t steps) {
+    v3 sc, sb;
+    ss_samples<true>(a, lut, lane, valid, fate, st, steps, sc, sb);
+    float v[6] = {sc.x, sc.y, sc.z, sb.x, sb.y, sb.z};
+    if (a.ss_log2 != 0u) ss_resolve(v, a.ss_log2, lane);  // wave-uniform
+    float* P = reinterpret_cast<float*>(&wave_hist<true>());
+#pragma unroll
+    for (uint32_t c = 0; c < 6u; ++c) P[shutter_plane_at(c) + lane] = v[c];
+}
+// A writer lane, after the barrier: target 0 (col) or 1 (blackout_col; wave-uniform) of its pixel from the
+// n = 2^ln waves' planes -- tree, scale, encode, store.
+template <uint32_t FMT>
+__device__ __forceinline__ void shutter_resolve_store(void* out, uint32_t target, uint32_t ln, uint32_t lane,
+                                                      size_t idx, const float* tab) {
+#pragma clang fp contract(off)
+    const float* base = reinterpret_cast<const float*>(shutter_hist_lds());
+    float v[3];
+#pragma unroll
+    for (uint32_t c = 0; c < 3u; ++c) {
+        const uint32_t off = shutter_plane_at(3u * target + c) + lane;
+        const float s = shutter::tree_sum(ln, [&](uint32_t t) { return base[t * (uint32_t)(sizeof(HistLds) / sizeof(float)) + off]; });
+        v[c] = s * shutter::scale(ln);
+    }
+    store_px<FMT>(out, idx, mk(v[0], v[1], v[2]), tab + 256);
 }
 
 }  // namespace BH_NS

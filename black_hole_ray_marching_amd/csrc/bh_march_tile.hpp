@@ -1,5 +1,6 @@
 // bh_march_tile.hpp -- the tile schedule (BH_SCHED_TILE, the default): one dispatch slot marched by one wave
-// (march_slot), the shader-clock probe, the plain, supersampled, lens and work-list kernels, and their launchers.
+// (march_slot), the shader-clock probe, the plain, supersampled, shutter, lens and work-list kernels, and their
+// launchers.
 // Needs bh_march_ray.hpp, bh_march_shade.hpp, bh_march_resolve.hpp and bh_refine.hpp (the work list).
 #pragma once
 #include "bh_march_ray.hpp"
@@ -37,11 +38,17 @@ __device__ __forceinline__ void select_outputs(MarchArgs& a, const FrameArgs& F)
 // tile of the virtual frame, both given by the caller's work list: no dispatch order, no cost feedback.
 // LENS (exact math, march_tile_lens_kernel): the epilogue stores the ray's lens record instead of shading it;
 // `lut` is not read.
-template <uint32_t FMT, uint32_t SF, bool SS = false, bool ITEM = false, bool LENS = false>
+// SHUT (march_tile_shutter_kernel): a wave of a shutter workgroup -- the epilogue leaves the lane's samples in the
+// wave's LDS area (after the k x k butterfly when A.ss_log2 != 0) and stores nothing; *sl receives the lane's
+// pixel for the workgroup's resolve.  It stays as the caller set it (ok = false) when the tile is out of range.
+struct ShutterLane { uint32_t px, py; bool valid, ok; };
+template <uint32_t FMT, uint32_t SF, bool SS = false, bool ITEM = false, bool LENS = false, bool SHUT = false>
 __device__ __forceinline__ void march_slot(const MarchArgs& A, uint32_t slot, const float* lut,
-                                           uint32_t lane, uint32_t item_tx = 0u, uint32_t item_ty = 0u) {
+                                           uint32_t lane, uint32_t item_tx = 0u, uint32_t item_ty = 0u,
+                                           ShutterLane* sl = nullptr) {
     static_assert(SS || !ITEM, "work items are supersampled tiles");
     static_assert(!LENS || (!SS && !BH_FAST), "a lens is one record per ray, in exact math");
+    static_assert(!SHUT || (!SS && !ITEM && !LENS), "a shutter wave takes its ss from the argument");
     const uint32_t nf = A.n_frames;
     uint32_t fi = 0, j = slot;
     if constexpr (ITEM) {
@@ -88,12 +95,17 @@ __device__ __forceinline__ void march_slot(const MarchArgs& A, uint32_t slot, co
         // ingoing test and the |s| guard (wave-uniform: a scalar branch)
         if constexpr (SF != SF_DYN) {
             const bool out = (dot(f.ro0, f.ro0) > 1.01f) && (__builtin_amdgcn_ballot_w64(!(fabsf(st.s) <= 0x1p30f)) == 0ull);
-            if (__builtin_amdgcn_readfirstlane((int)out)) march_ray<SF | SF_CAM_OUT>(a, f, st, fate, steps, lane);
-            else march_ray<SF>(a, f, st, fate, steps, lane);
+            if (__builtin_amdgcn_readfirstlane((int)out)) march_ray<SF | SF_CAM_OUT, SHUT>(a, f, st, fate, steps, lane);
+            else march_ray<SF, SHUT>(a, f, st, fate, steps, lane);
         } else {
-            march_ray<SF>(a, f, st, fate, steps, lane);
+            march_ray<SF, SHUT>(a, f, st, fate, steps, lane);
         }
     }
+    if constexpr (SHUT) {
+        // every lane (the k x k butterfly reads the wave's other lanes); no output pointer is read here
+        shutter_stage(a, lut, lane, valid, fate, st, steps);
+        *sl = ShutterLane{px, py, valid, true};
+    } else
     if constexpr (SS) {
         // every lane takes the resolve (its butterfly reads the wave's other lanes); invalid lanes hold 0
         uint32_t fo = fi;
@@ -205,6 +217,56 @@ __global__ void __launch_bounds__(64 * WG_WAVES) march_tile_ss_kernel(MarchArgs 
     march_tile_wave<FMT, SF, true>(A, lut);
 }
 
+// The tile schedule's shutter form (bh_render_shutter): one workgroup of n = 2^ln waves per (output frame, tile)
+// -- workgroup g takes order index g / n_frames of output frame g % n_frames, wave w the frame's camera w
+// (bh_shutter.hpp; A.n_frames counts CAMERAS, n per output frame, and wave_slot names march_slot's own slot of
+// that pair) -- marched by march_slot as any other tile: order, cost feedback (camera 0 of frame 0 only), cycle
+// fast-forward, shading, and bh_render_ss's butterfly when A.ss_log2 != 0.  Then the resolve: each wave leaves
+// its samples in its own history area (shutter_stage), one barrier, and the writer lanes of wave 0 (col) and
+// wave 1 (blackout_col, when the frame has that target) sum the n waves' samples in tree order, scale, encode
+// and store (shutter_resolve_store).  No intermediate in global memory.
+// Dynamic LDS: n history areas, then one copy of the tables (shutter_lds_bytes) -- 9 to 10 KiB at n = 2 (per wave no
+// more than the plain kernel's workgroups hold), 65 to 66 KiB at n = 16 (two workgroups per CU).
+// Registers: 8 waves per SIMD are asked for (64 VGPRs; the exact builds' default-scene kernels then spill 3 to 5
+// of them to scratch).  At the 67 to 71 the compiler takes unasked, a SIMD holds 7 waves, a CU 28, and a
+// workgroup of 16 waves fits once, not twice: n = 16 measured 1.41x its yardstick, 1.05 to 1.07x with the
+// request, n = 8 1.03 to 1.05x in place of 1.07 to 1.08x, n = 4 unchanged.
+template <uint32_t FMT>
+constexpr uint32_t shutter_lds_bytes(uint32_t ln) { return (uint32_t)(sizeof(HistLds) << ln) + (uint32_t)(lds_tables<FMT>() * sizeof(float)); }
+template <uint32_t FMT, uint32_t SF>
+__global__ void __launch_bounds__(64u << shutter::MAX_LOG2) __attribute__((amdgpu_waves_per_eu(8)))
+march_tile_shutter_kernel(MarchArgs A, uint32_t ln) {
+    float* lut = reinterpret_cast<float*>(shutter_hist_lds() + (1u << ln));
+    const uint32_t nt = 64u << ln;
+    for (uint32_t i = threadIdx.x; i < (uint32_t)lds_tables<FMT>(); i += nt)
+        lut[i] = i < 256u ? A.srgb_lut[i] : A.srgb_enc[i - 256u];
+    __syncthreads();
+    const uint32_t n_out = A.n_frames >> ln;  // output frames
+    const uint32_t g = blockIdx.x;
+    if (g >= A.n_tiles * n_out) return;  // blockIdx and kernel arguments only: the whole workgroup or none of it
+    const uint32_t w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63u;
+    const uint32_t slot = shutter::wave_slot(g, w, n_out, ln);
+    const bool probe = A.clk && ((slot + (slot >> 8)) & A.clk_mask) == 0u;  // as march_tile_wave
+    ClockStart c0{0u, 0u};
+    if (probe) c0 = clock_start();
+    ShutterLane sl{0u, 0u, false, false};
+    march_slot<FMT, SF, false, false, false, true>(A, slot, lut, lane, 0u, 0u, &sl);
+    if (probe) clock_end(A.clk, c0);
+    // Every wave of the workgroup arrives here, whatever its march did.  Between the table load's barrier and
+    // this one there is one return in this kernel, on blockIdx and kernel arguments alone; march_slot's
+    // defensive return (a tile index out of range: the same order entry for all n waves) only returns to this
+    // kernel, ahead of this barrier; and no code on the way sits under a lane- or wave-dependent branch that
+    // holds a barrier.  A wave whose lanes are all outside the frame marches nothing and stages zeros.
+    __syncthreads();
+    if (!sl.ok || w > 1u) return;
+    const FrameArgs& F = A.frame_table ? A.frame_table[slot % A.n_frames] : A.frames[slot % A.n_frames];
+    void* out = w == 0u ? F.out_col : F.out_blackout;
+    if (!out) return;  // wave 1 of a frame without the second target: neither resolved nor written
+    const uint32_t lk = A.ss_log2;
+    if (sl.valid && ss::writer(lane, lk))
+        shutter_resolve_store<FMT>(out, w, ln, lane, ss::out_index(sl.px, sl.py, lk, A.ss_out_width), lut);
+}
+
 #if !BH_FAST
 // The tile schedule's lens form (bh_render_lens): march_tile_kernel's waves -- order, cost feedback, cycle
 // fast-forward -- with the lens record as the epilogue: no sky, no tables, no encode, one kernel per
@@ -278,6 +340,18 @@ inline void launch_tile_schedule(K kernel, const MarchArgs& a, hipStream_t s) {
     const uint32_t waves = a.n_tiles * a.n_frames;
     const uint32_t blocks = (waves + (WG_WAVES - 1u)) / WG_WAVES;
     hipLaunchKernelGGL(kernel, dim3(blocks), dim3(64u * WG_WAVES), 0, s, a);
+}
+// ... its shutter form: one workgroup of 2^ln waves per (output frame, tile); a.n_frames counts cameras
+template <uint32_t FMT, uint32_t SF>
+inline void launch_shutter_schedule(const MarchArgs& a, uint32_t ln, hipStream_t s) {
+    const uint32_t blocks = a.n_tiles * (a.n_frames >> ln), lds = shutter_lds_bytes<FMT>(ln);
+    if (lds > 64u * 1024u) {  // above the default limit of a launch's dynamic LDS: once per kernel
+        static const hipError_t raised = hipFuncSetAttribute(reinterpret_cast<const void*>(&march_tile_shutter_kernel<FMT, SF>),
+                                                              hipFuncAttributeMaxDynamicSharedMemorySize,
+                                                              (int)shutter_lds_bytes<FMT>(shutter::MAX_LOG2));
+        (void)raised;
+    }
+    hipLaunchKernelGGL((march_tile_shutter_kernel<FMT, SF>), dim3(blocks), dim3(64u << ln), lds, s, a, ln);
 }
 // ... and the adaptive render's work-list march: `waves` resident waves that pull (march_refine_kernel)
 template <uint32_t FMT, uint32_t SF>

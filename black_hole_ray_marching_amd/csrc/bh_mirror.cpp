@@ -7,6 +7,7 @@
 #include "bh_host.hpp"
 #include "bh_lens.hpp"
 #include "bh_refine.hpp"
+#include "bh_shutter.hpp"
 #include "bh_ss.hpp"
 
 extern "C" {
@@ -47,6 +48,83 @@ int bh_ss_resolve_host(const float* samples, uint32_t width, uint32_t height, ui
                 o[3] = 1.0f;
             }
         }
+    return BH_OK;
+}
+
+// The shutter kernel's resolve on the host: bh_shutter.hpp's mapping and tree, workgroup by workgroup.  Workgroup
+// g's wave w takes the dispatch slot the kernel's wave takes (wave_slot), decoded as march_slot decodes it (order
+// index slot / n_cameras, camera slot % n_cameras; the order here is the identity: any order visits every tile);
+// its 64 lanes hold the camera's samples of that tile of the virtual frame, through bh_ss.hpp's butterfly and
+// scale when ss > 1; then the writer lanes sum the n waves' values in tree order, scale and store.
+int bh_shutter_resolve_host(const float* samples, uint32_t n_frames, uint32_t n_sub, uint32_t width, uint32_t height,
+                            uint32_t ss, float* out) {
+    const uint32_t lk = bh::ss::log2_k(ss), ln = bh::shutter::log2_n(n_sub);
+    if (!samples || !out || lk > 3u || ln > bh::shutter::MAX_LOG2) return bad_arg(__func__, __LINE__);
+    if (n_frames == 0u || (uint64_t)n_frames * n_sub > BH_MAX_FRAMES) return bad_arg(__func__, __LINE__);
+    if (!frame_shape_ok(width, height, ss)) return bad_arg(__func__, __LINE__);
+    const uint32_t vw = width * ss, vh = height * ss, n_cams = n_frames << ln;
+    const uint32_t tiles_x = (vw + 7u) / 8u, tiles_y = (vh + 7u) / 8u, n_tiles = tiles_x * tiles_y;
+    const size_t vpx = (size_t)vw * vh, opx = (size_t)width * height;
+    std::vector<uint8_t> visits, stores;
+    std::vector<float> wave;  // [wave][channel][lane]
+    try {
+        visits.assign((size_t)n_cams * n_tiles, 0u);
+        stores.assign((size_t)n_frames * opx, 0u);
+        wave.resize((size_t)n_sub * 3u * 64u);
+    } catch (const std::bad_alloc&) {
+        return BH_ERR_OUT_OF_MEMORY;
+    }
+    bool outside = false;
+    for (uint32_t g = 0; g < n_tiles * n_frames; ++g) {
+        const uint32_t f = bh::shutter::group_frame(g, n_frames);
+        uint32_t tile = 0;
+        for (uint32_t w = 0; w < n_sub; ++w) {
+            const uint32_t slot = bh::shutter::wave_slot(g, w, n_frames, ln);
+            const uint32_t j = slot / n_cams, cam = slot - j * n_cams;
+            if (j >= n_tiles || cam >= n_cams || (w != 0u && j != tile)) { outside = true; continue; }
+            tile = j;
+            if (visits[(size_t)cam * n_tiles + j] != 255u) ++visits[(size_t)cam * n_tiles + j];
+            const uint32_t ty = j / tiles_x, tx = j - ty * tiles_x;
+            const float* S = samples + (size_t)cam * vpx * 4u;
+            float nv[64];
+            for (int ch = 0; ch < 3; ++ch) {
+                float* cur = &wave[((size_t)w * 3u + (size_t)ch) * 64u];
+                for (uint32_t lane = 0; lane < 64u; ++lane) {
+                    const uint32_t px = tx * 8u + (lane & 7u), py = ty * 8u + (lane >> 3);
+                    cur[lane] = px < vw && py < vh ? S[((size_t)py * vw + px) * 4u + (size_t)ch] : 0.0f;
+                }
+                if (lk == 0u) continue;
+                for (uint32_t i = 0; i < bh::ss::levels(lk); ++i) {
+                    const uint32_t mask = bh::ss::level_mask(i, lk);
+                    for (uint32_t lane = 0; lane < 64u; ++lane)
+                        nv[lane] = bh::ss::level_add(cur[lane], mask, [&](uint32_t m) { return cur[lane ^ m]; });
+                    std::memcpy(cur, nv, sizeof nv);
+                }
+                for (uint32_t lane = 0; lane < 64u; ++lane) cur[lane] = cur[lane] * bh::ss::scale(lk);
+            }
+        }
+        const uint32_t ty = tile / tiles_x, tx = tile - ty * tiles_x;
+        for (uint32_t lane = 0; lane < 64u; ++lane) {
+            const uint32_t px = tx * 8u + (lane & 7u), py = ty * 8u + (lane >> 3);
+            if (!(px < vw && py < vh && bh::ss::writer(lane, lk))) continue;
+            const size_t idx = bh::ss::out_index(px, py, lk, width);
+            if (idx >= opx) { outside = true; continue; }
+            if (stores[(size_t)f * opx + idx] != 255u) ++stores[(size_t)f * opx + idx];
+            float* o = out + ((size_t)f * opx + idx) * 4u;
+            for (int ch = 0; ch < 3; ++ch) {
+                const float s = bh::shutter::tree_sum(ln, [&](uint32_t t) { return wave[((size_t)t * 3u + (size_t)ch) * 64u + lane]; });
+                o[ch] = s * bh::shutter::scale(ln);
+            }
+            o[3] = 1.0f;
+        }
+    }
+    bool once = !outside;
+    for (uint8_t v : visits) once = once && v == 1u;
+    for (uint8_t v : stores) once = once && v == 1u;
+    if (!once) {
+        bh_set_last_error("bh_shutter_resolve_host: a (frame, tile, camera) not visited exactly once, or a store outside the frame");
+        return BH_ERR_INTERNAL;
+    }
     return BH_OK;
 }
 

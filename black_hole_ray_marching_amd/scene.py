@@ -237,6 +237,19 @@ def ss_resolve_host(samples: np.ndarray, ss: int) -> np.ndarray:
     return out
 
 
+def shutter_resolve_host(samples: np.ndarray, n_sub: int, ss: int = 1) -> np.ndarray:
+    """bh_shutter_resolve_host (host only): the shutter kernel's mapping and tree over fp32 RGBA sample frames
+    (n_frames * n_sub, ss*H, ss*W, 4), camera after camera -> the (n_frames, H, W, 4) resolve."""
+    s = np.ascontiguousarray(samples, np.float32)
+    k, n = _ss_arg(ss), _ss_arg(n_sub)
+    if s.ndim != 4 or s.shape[3] != 4 or k == 0 or n == 0 or s.shape[0] % n or s.shape[1] % k or s.shape[2] % k:
+        raise BhError(_abi.BH_ERR_INVALID_ARG, "shutter_resolve_host: samples must be (n_frames*n_sub, ss*H, ss*W, 4)")
+    out = np.empty((s.shape[0] // n, s.shape[1] // k, s.shape[2] // k, 4), np.float32)
+    check(load().bh_shutter_resolve_host(s.ctypes.data, out.shape[0], n, out.shape[2], out.shape[1], k,
+                                         out.ctypes.data), "bh_shutter_resolve_host")
+    return out
+
+
 def lens_shade_host(lens: np.ndarray, sky: np.ndarray, ss: int = 1):
     """bh_lens_shade_host (host only): what the lens shade kernel runs, on the CPU.  `lens`: (ss*H, ss*W, 2)
     float32 records (u, v); `sky`: (h, w, 4) uint8 RGBA8 sRGB -> (col, blackout_col), fp32 (H, W, 4)."""
@@ -512,6 +525,35 @@ class Scene:
             return FrameBatch(self, descs, keep, _ss_arg(ss))
         a = _adaptive_desc(ss, adaptive, tile_mask, refined_tiles, n, descs[0].width, descs[0].height)
         return FrameBatch(self, descs, keep, _ss_arg(ss), a)
+
+    def render_shutter(self, output, blackout_output=None, *, cameras, fmt: int = BH_OUT_RGBA32F, ss: int = 1,
+                       stream=None, schedule: int = 0, math: int | None = None, width: int | None = None,
+                       height: int | None = None) -> None:
+        """bh_render_shutter: one frame that averages the frames of `cameras` (n in {1, 2, 4, 8, 16}
+        CameraUniforms: the sub-frame cameras of its exposure) in linear fp32 before the output encode; `ss` as
+        render's.  Uses the scene's uniforms, not its camera."""
+        self.render_frames_shutter([output], None if blackout_output is None else [blackout_output], cameras=[cameras],
+                                   fmt=fmt, ss=ss, stream=stream, schedule=schedule, math=math, width=width, height=height)
+
+    def render_frames_shutter(self, outputs, blackout_outputs=None, *, cameras, fmt: int = BH_OUT_RGBA32F, ss: int = 1,
+                              stream=None, schedule: int = 0, math: int | None = None, width: int | None = None,
+                              height: int | None = None) -> None:
+        """bh_render_frames_shutter: several shutter frames in one launch; `cameras` is a list of n-lists, one per
+        output frame, all of one length n, with len(outputs) * n at most BH_MAX_FRAMES."""
+        n = len(outputs)
+        if n < 1 or len(cameras) != n or not cameras[0] or any(len(g) != len(cameras[0]) for g in cameras):
+            raise BhError(_abi.BH_ERR_INVALID_ARG, "render_frames_shutter: one list of n cameras per output frame")
+        n_sub = len(cameras[0])
+        if n * n_sub > _abi.BH_MAX_FRAMES:
+            raise BhError(_abi.BH_ERR_INVALID_ARG, f"render_frames_shutter: at most {_abi.BH_MAX_FRAMES} cameras per call, got {n * n_sub}")
+        bos = blackout_outputs if blackout_outputs is not None else [None] * n
+        if len(bos) != n:
+            raise BhError(_abi.BH_ERR_INVALID_ARG, "render_frames_shutter: per-frame lists must have one entry per frame")
+        descs = (_abi.bh_render_desc * n)(*[self._desc(outputs[i], bos[i], fmt, None, None, math, BH_LAYOUT_ROWMAJOR,
+                                                       0, 1, width, height, schedule, None) for i in range(n)])
+        cams = (_abi.bh_camera_uniform * (n * n_sub))(*[c.c for g in cameras for c in g])
+        check(self.lib.bh_render_frames_shutter(self._ctx, n, n_sub, cams, C.byref(self.uniforms.to_c()), descs,
+                                                _ss_arg(ss), _stream_handle(stream)), "bh_render_frames_shutter")
 
     def render_lens(self, lens, *, width: int | None = None, height: int | None = None, schedule: int = 0,
                     stream=None) -> None:

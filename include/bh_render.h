@@ -311,6 +311,47 @@ int bh_render_frames_ss(bh_ctx* ctx, uint32_t n_frames, const bh_camera_uniform*
  * pixels) -> the fp32 RGBA resolve, width x height, alpha 1.  BH_ERR_INVALID_ARG as above. */
 int bh_ss_resolve_host(const float* samples_rgba, uint32_t width, uint32_t height, uint32_t ss, float* out_rgba);
 
+/* Shutter render: every output frame integrates over a shutter interval -- it takes n_sub in {1, 2, 4, 8, 16}
+ * camera uniforms (the sub-frame cameras of its exposure) and is the average of the n_sub frames bh_render would
+ * produce for them, resolved inside the march kernel in linear fp32 before the one output encode (not in the
+ * reference, which renders one instantaneous camera per frame).  Composes with ss.
+ *   bh_render_shutter: cameras[n_sub], one desc.  bh_render_frames_shutter: n_frames output frames in one
+ *     launch, frame f uses cameras[f * n_sub + t], t = 0 .. n_sub - 1, and descs[f].
+ *   Samples: for time sample t, col_t and bo_t are the linear fp32 values before any encode -- with ss = 1 the
+ *     values bh_render computes for that camera, with ss = k in {2, 4, 8} the values bh_render_ss computes
+ *     (the k x k tree and the multiply by 1 / k^2 included).  The blackout test runs per ray sample, as it does
+ *     there, never on an average.
+ *   Resolve, per channel r, g, b and per target, in fp32, no FMA: a pairwise tree over t (level 1 adds t and
+ *     t^1, level 2 the pair sums t and t^2, and so on), then one multiply by 1 / n_sub (exact).  Alpha is 1.
+ *   Encode: the output format's existing one, applied to the resolved value.  out_blackout == NULL: that
+ *     target is neither resolved nor written.
+ * n_sub = 1 is bh_render_frames / bh_render_frames_ss exactly (the call is passed on).  BH_ERR_INVALID_ARG:
+ * n_sub outside {1, 2, 4, 8, 16}; n_frames * n_sub above BH_MAX_FRAMES; the ss and size limits of bh_render_ss.
+ * With n_sub > 1 one workgroup of n_sub waves marches a tile once per camera and resolves it, so
+ * BH_ERR_UNSUPPORTED, with a sentence in bh_last_error() that starts with "bh_render_shutter", for everything
+ * bh_render_ss refuses: a layout other than BH_LAYOUT_ROWMAJOR, shard_count != 1, a partition, a base schedule
+ * other than BH_SCHED_TILE, any dbg_* pointer.  The BH_SCHED_FLAG_* flags are allowed.  A refused call leaves
+ * the outputs untouched.
+ * Order state, repeated-frame skip and graph contract are those of bh_render_frames(_ss) of the same
+ * n_frames * n_sub cameras: the key is the (virtual) geometry on the stream, shared with plain renders of it --
+ * the dispatch order it holds is the same order of the same tiles whichever kernel walks it, learned from
+ * camera 0 of frame 0 only (each tile counted once), and a call whose camera 0 repeats the last launch's skips
+ * the order build as a plain render does.  More than 32 cameras in a call go through the pinned ring and device
+ * table of bh_render_frames and are refused on a capturing stream.  The first call of a key allocates and is
+ * refused under capture; later calls allocate nothing. */
+int bh_render_shutter(bh_ctx* ctx, uint32_t n_sub, const bh_camera_uniform* cameras, const bh_uniforms* uniforms,
+                      const bh_render_desc* desc, uint32_t ss, void* hip_stream);
+int bh_render_frames_shutter(bh_ctx* ctx, uint32_t n_frames, uint32_t n_sub, const bh_camera_uniform* cameras,
+                             const bh_uniforms* uniforms, const bh_render_desc* descs, uint32_t ss, void* hip_stream);
+/* Host only (no device needed): the shutter kernel's own mapping and tree (csrc/bh_shutter.hpp: workgroup ->
+ * frame and tile, wave -> camera, the time tree) with bh_ss_resolve_host's lane code for ss > 1, run workgroup
+ * by workgroup over n_frames * n_sub fp32 RGBA sample frames (camera after camera, each ss*height rows of
+ * ss*width pixels) -> n_frames fp32 RGBA frames, width x height, alpha 1.  BH_ERR_INVALID_ARG as above;
+ * BH_ERR_INTERNAL if any (frame, tile, camera) is visited other than exactly once or a store index falls
+ * outside the frame. */
+int bh_shutter_resolve_host(const float* samples_rgba, uint32_t n_frames, uint32_t n_sub, uint32_t width,
+                            uint32_t height, uint32_t ss, float* out_rgba);
+
 /* Adaptive supersampling: every pixel gets the plain one-ray value, and every 8x8 output tile that shows an
  * edge is marched again with ss x ss rays per pixel and overwritten with the supersampled value.
  * Normative definition.  For one frame of size W x H, format F, ss = k in {2, 4, 8} and threshold T, let

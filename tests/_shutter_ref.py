@@ -1,0 +1,94 @@
+"""Reference of the shutter render (bh_render_shutter) for tests/test_shutter_host.py and
+tests/test_gpu_shutter.py: the CPU oracle's fp32 frame of every sub-frame camera (the virtual frame kW x kH for
+ss = k, resolved by tests/_ss_ref.py's numpy tree), averaged by a numpy restatement of the normative time tree
+(include/bh_render.h), then encoded as the output format stores it.  Never the GPU's own output.
+
+Every oracle frame is rendered once per process and shared (read-only arrays)."""
+import functools
+
+import numpy as np
+
+import black_hole_ray_marching_amd as bh
+import oracle
+from tests._cases import CAMERAS, camera_uniform, uniforms
+from tests._ss_ref import CAP, FLAGS, SIZES, expected_bytes, resolve_np, sky_ss  # noqa: F401  (shared with the tests)
+
+NS = [2, 4, 8, 16]
+MIXED = ["D", "E", "H", "F2", "B", "C", "G", "F"]  # unrelated views, all four fates; cycled for n = 16
+
+
+def mixed(n: int, W: int, H: int, first: int = 0):
+    """The first n of MIXED (from `first` on, cyclically): n CameraUniforms."""
+    return tuple(camera_uniform(MIXED[(first + t) % len(MIXED)], W, H) for t in range(n))
+
+
+def sweep(n: int, W: int, H: int):
+    """Neighbouring views, the real use: camera t is what a controller with W and ArrowLeft held reaches from
+    camera D after dt = 0.05 * t / n (t = 0: camera D itself)."""
+    pos, target = CAMERAS["D"][:2]
+    out = []
+    for t in range(n):
+        ctrl = bh.CameraController()
+        ctrl.process_key("W", True)
+        ctrl.process_key("ArrowLeft", True)
+        cam, _ = ctrl.update_camera(bh.Camera.look_at(pos, target, W, H), 0.05 * t / n)
+        cu = bh.CameraUniform()
+        cu.update(cam)
+        out.append(cu)
+    return tuple(out)
+
+
+CAMERA_SETS = {"mixed": mixed, "sweep": sweep}
+
+
+@functools.lru_cache(maxsize=None)
+def _oracle_virtual(cam_bytes: bytes, W: int, H: int, k: int):
+    col, bo, _, fate = oracle.render_rows(cam_bytes, bytes(uniforms().to_c()), sky_ss(), k * W, k * H, CAP, FLAGS)
+    assert not np.isnan(col).any() and not np.isnan(bo).any(), "the oracle frame holds a NaN"
+    for x in (col, bo, fate):
+        x.setflags(write=False)
+    return col, bo, fate
+
+
+def oracle_virtual(cam, W: int, H: int, k: int):
+    """The oracle's (col, blackout_col, fate) of the virtual frame kW x kH for CameraUniform `cam`."""
+    return _oracle_virtual(cam.to_bytes(), W, H, k)
+
+
+def samples(cams, W: int, H: int, k: int):
+    """(col, blackout_col) samples of every camera before the time resolve, fp32 (n, H, W, 4): the oracle's frame
+    (ss = 1) or its k x k resolve."""
+    col = np.stack([resolve_np(oracle_virtual(c, W, H, k)[0], k) for c in cams])
+    bo = np.stack([resolve_np(oracle_virtual(c, W, H, k)[1], k) for c in cams])
+    return col, bo
+
+
+def time_tree_np(v: np.ndarray) -> np.ndarray:
+    """(n, H, W, 4) fp32 samples -> (H, W, 4): per channel the pairwise tree over the first axis, one multiply
+    by 1 / n; alpha 1."""
+    v = np.asarray(v, np.float32)[..., :3]
+    n = v.shape[0]
+    while v.shape[0] > 1:
+        v = v[0::2] + v[1::2]
+    v = v[0] * np.float32(1 / n)
+    assert v.dtype == np.float32
+    return np.concatenate([v, np.ones(v.shape[:2] + (1,), np.float32)], -1)
+
+
+def running_sum_np(v: np.ndarray) -> np.ndarray:
+    """The same average summed t = 0, 1, 2, ...: what the tree must differ from somewhere (n >= 4)."""
+    v = np.asarray(v, np.float32)[..., :3]
+    s = v[0]
+    for t in range(1, v.shape[0]):
+        s = s + v[t]
+    s = s * np.float32(1 / v.shape[0])
+    return np.concatenate([s, np.ones(s.shape[:2] + (1,), np.float32)], -1)
+
+
+def reference(cams, W: int, H: int, k: int = 1):
+    """(col, blackout_col) fp32 (H, W, 4): the normative result for the cameras `cams` of one output frame."""
+    col, bo = samples(cams, W, H, k)
+    rc, rb = time_tree_np(col), time_tree_np(bo)
+    rc.setflags(write=False)
+    rb.setflags(write=False)
+    return rc, rb

@@ -7,9 +7,13 @@ driven by CameraController with a key script, PNG frames out.
 Script: comma-separated KEY:first-last frame ranges (keys held down), reference key names (W A S D
 Space F ArrowUp/Down/Left/Right P O).
 
+    python tools/render_path.py --shutter 8 --ss 2 --frames 4
+Every frame integrated over a shutter interval: 8 sub-frame cameras per frame, averaged before the encode.
+
     python tools/render_path.py --sky-frames DIR --out frames/sky
 A moving sky behind a still camera instead: one frame per image in DIR, the view marched once into a lens map."""
 import argparse
+import dataclasses
 import json
 import sys
 import time
@@ -42,7 +46,14 @@ p.add_argument("--sky-frames", default=None, metavar="DIR",
                help="a moving sky behind a still camera: one output frame per image file in DIR (sorted by name), "
                     "the default camera marched once into a lens map (bh_render_lens) and shaded with each image "
                     "(bh_shade_lens); --script, --frames and --dt are not used")
+p.add_argument("--shutter", type=int, choices=[1, 2, 4, 8, 16], default=1, metavar="N",
+               help="N sub-frame cameras per frame, averaged in linear fp32 before the sRGB encode (bh_render_shutter): "
+                    "camera t of a frame is where a copy of the controller takes the frame's camera in dt * S * t / N")
+p.add_argument("--shutter-frac", type=float, default=0.5, metavar="S",
+               help="with --shutter: the part of a frame's dt the shutter stays open (default 0.5)")
 args = p.parse_args()
+if args.shutter > 1 and (args.adaptive is not None or args.sky_frames):
+    sys.exit("render_path: --shutter does not combine with --adaptive or --sky-frames (no adaptive or lens shutter)")
 if args.adaptive is not None and args.ss == 1:
     p.error("--adaptive needs --ss 2, 4 or 8")
 if args.sky_frames and args.adaptive is not None:
@@ -63,6 +74,22 @@ col = torch.empty((H, W, 4), dtype=torch.uint8, device="cuda")
 bo = torch.empty_like(col)
 surf = torch.empty_like(col)
 log = []
+
+
+def shutter_cameras(frame_cam):
+    """The N sub-frame cameras of a frame: a copy of the controller's state moves a copy of the frame's camera
+    by dt * S * t / N (t = 0: the frame's own camera); the path itself is untouched."""
+    out = []
+    for t in range(args.shutter):
+        c2 = bh.CameraController()
+        c2.c = type(ctrl.c).from_buffer_copy(ctrl.c)
+        sub, _ = c2.update_camera(dataclasses.replace(frame_cam), args.dt * args.shutter_frac * t / args.shutter)
+        cu = bh.CameraUniform()
+        cu.update(sub)
+        out.append(cu)
+    return out
+
+
 t0 = time.perf_counter()
 if args.sky_frames:
     images = sorted(q for q in Path(args.sky_frames).iterdir() if q.is_file())
@@ -87,7 +114,10 @@ for f in range(0 if args.sky_frames else args.frames):
         ctrl.process_key(k, a <= f <= b)
     cam, moved = ctrl.update_camera(cam, args.dt)
     scene.update(cam)
-    scene.render(col, bo, fmt=bh.BH_OUT_BGRA8_SRGB, ss=args.ss, adaptive=args.adaptive)
+    if args.shutter > 1:
+        scene.render_shutter(col, bo, cameras=shutter_cameras(cam), fmt=bh.BH_OUT_BGRA8_SRGB, ss=args.ss)
+    else:
+        scene.render(col, bo, fmt=bh.BH_OUT_BGRA8_SRGB, ss=args.ss, adaptive=args.adaptive)
     scene.bloom(col, bo, surf)
     if not args.no_png:
         write_png(out_dir / f"frame_{f:04d}.png", surf.cpu().numpy())
@@ -95,5 +125,5 @@ for f in range(0 if args.sky_frames else args.frames):
 torch.cuda.synchronize()
 dt = time.perf_counter() - t0
 (out_dir / "path.json").write_text(json.dumps(log, indent=0))
-print(json.dumps({"frames": args.frames, "width": W, "height": H, "ss": args.ss, "adaptive": args.adaptive, "seconds": round(dt, 3),
+print(json.dumps({"frames": args.frames, "width": W, "height": H, "ss": args.ss, "adaptive": args.adaptive, "shutter": args.shutter, "seconds": round(dt, 3),
                   "frames_per_s_incl_png": round(args.frames / dt, 2), "out": str(out_dir)}))
