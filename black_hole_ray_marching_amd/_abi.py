@@ -136,6 +136,13 @@ SIGNATURES = {
     "bh_shade_lens": (C.c_int, [C.c_void_p, C.POINTER(bh_shade_desc), C.c_void_p]),
     "bh_lens_shade_host": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint32,
                                      C.c_uint32, C.c_void_p, C.c_void_p]),
+    "bh_sky_create_mips": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(C.c_void_p)]),
+    "bh_sky_levels": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint32)]),
+    "bh_sky_read_level": (C.c_int, [C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.c_void_p]),
+    "bh_shade_lens_mip": (C.c_int, [C.c_void_p, C.POINTER(bh_shade_desc), C.c_void_p]),
+    "bh_sky_mips_host": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p]),
+    "bh_lens_shade_mip_host": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint32,
+                                         C.c_uint32, C.c_void_p, C.c_void_p]),
     "bh_shard_tile_count": (C.c_int64, [C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32]),
     "bh_tiles_unpack": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32,
                                   C.c_uint64, C.c_uint32, C.c_void_p]),

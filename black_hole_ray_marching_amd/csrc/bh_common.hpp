@@ -136,6 +136,22 @@ struct LensShadeArgs {
     uint32_t sky_w, sky_h;
 };
 
+// One bh_shade_lens_mip launch (bh_lens_mip.hip): LensShadeArgs' fields and the sky's chain -- the levels >= 1,
+// 8 bytes per texel, level l at chain + level_off[l] texels (lens::mip_offsets).
+struct LensMipArgs {
+    const bh_lens_px* lens;
+    const uint32_t* sky;
+    const void* chain;
+    const float* srgb_lut;
+    const float* srgb_enc;
+    void* out_col;
+    void* out_blackout;        // or null
+    uint32_t width, height;    // the OUTPUT frame
+    uint32_t sky_w, sky_h;
+    uint32_t n_levels;
+    uint32_t level_off[16];
+};
+
 constexpr uint32_t REFINE_HEADS = 8, REFINE_HEAD_STRIDE = 32, REFINE_HEAD0 = 32;  // 128-byte lines
 constexpr uint32_t REFINE_CTR_WORDS = REFINE_HEAD0 + REFINE_HEADS * REFINE_HEAD_STRIDE;
 

@@ -15,6 +15,7 @@
 
 #include "bh_host.hpp"
 #include "bh_srgb.hpp"
+#include "bh_lens.hpp"
 #include "bh_refine.hpp"
 #include "bh_shutter.hpp"
 #include "bh_ss.hpp"
@@ -246,6 +247,7 @@ int bh_destroy(bh_ctx* c) {
     for (auto& t : c->frame_tables) free_frame_table(t);
     for (bh_sky* k : c->skies) {
         (void)hipFree(k->texels);
+        if (k->chain) (void)hipFree(k->chain);
         delete k;
     }
     delete c;
@@ -804,8 +806,9 @@ int bh_render_lens(bh_ctx* c, const bh_camera_uniform* cam, const bh_uniforms* U
     return march_in_order(c, &L, cam, U, stream);
 }
 
-int bh_sky_create(bh_ctx* c, const uint8_t* rgba8, uint32_t w, uint32_t h, bh_sky** out) {
-    if (!c || !rgba8 || !out || w == 0 || h == 0 || w > 32768u || h > 32768u) return bad_arg(__func__, __LINE__);
+// bh_sky_create and bh_sky_create_mips: the texels, and with `mips` the chain built from them (a synchronous call)
+static int sky_create(bh_ctx* c, const uint8_t* rgba8, uint32_t w, uint32_t h, bool mips, bh_sky** out, const char* fn) {
+    if (!c || !rgba8 || !out || w == 0 || h == 0 || w > 32768u || h > 32768u) return bad_arg(fn, __LINE__);
     *out = nullptr;
     DeviceScope dev(c->device);
     if (dev.err != hipSuccess) return hip_fail(dev.err, "hipSetDevice");
@@ -817,14 +820,51 @@ int bh_sky_create(bh_ctx* c, const uint8_t* rgba8, uint32_t w, uint32_t h, bh_sk
     const size_t bytes = (size_t)w * h * 4u;
     hipError_t e = hipMalloc(&k->texels, bytes);
     if (e == hipSuccess) e = hipMemcpy(k->texels, rgba8, bytes, hipMemcpyHostToDevice);
+    if (e == hipSuccess && mips) {
+        uint32_t off[bh::lens::MIP_MAX_LEVELS];
+        const size_t texels = bh::lens::mip_offsets(w, h, off);
+        e = hipMalloc(&k->chain, (texels ? texels : 1u) * sizeof(bh::lens::Half4));  // a 1x1 sky has no level >= 1
+        if (e == hipSuccess) e = (hipError_t)bh_launch_sky_mips(k->texels, w, h, c->lut, k->chain, nullptr);
+        if (e == hipSuccess) e = hipStreamSynchronize(nullptr);
+        k->n_levels = bh::lens::mip_levels(w, h);
+    }
     if (e != hipSuccess) {
         if (k->texels) (void)hipFree(k->texels);
+        if (k->chain) (void)hipFree(k->chain);
         delete k;
-        return alloc_fail(e, "bh_sky_create");
+        return alloc_fail(e, fn);
     }
     c->skies.push_back(k);
     *out = k;
     return BH_OK;
+}
+
+int bh_sky_create(bh_ctx* c, const uint8_t* rgba8, uint32_t w, uint32_t h, bh_sky** out) {
+    return sky_create(c, rgba8, w, h, false, out, __func__);
+}
+
+int bh_sky_create_mips(bh_ctx* c, const uint8_t* rgba8, uint32_t w, uint32_t h, bh_sky** out) {
+    return sky_create(c, rgba8, w, h, true, out, __func__);
+}
+
+int bh_sky_levels(const bh_sky* k, uint32_t* out) {
+    if (!k || !out) return bad_arg(__func__, __LINE__);
+    *out = k->n_levels;
+    return BH_OK;
+}
+
+int bh_sky_read_level(const bh_sky* k, uint32_t level, uint32_t* out_w, uint32_t* out_h, void* host_out) {
+    if (!k || !out_w || !out_h || level < 1u || level >= k->n_levels) return bad_arg(__func__, __LINE__);
+    uint32_t off[bh::lens::MIP_MAX_LEVELS];
+    bh::lens::mip_offsets(k->w, k->h, off);
+    *out_w = bh::lens::mip_side(k->w, level);
+    *out_h = bh::lens::mip_side(k->h, level);
+    if (!host_out) return BH_OK;
+    DeviceScope dev(k->ctx->device);
+    if (dev.err != hipSuccess) return hip_fail(dev.err, "hipSetDevice");
+    const hipError_t e = hipMemcpy(host_out, static_cast<const bh::lens::Half4*>(k->chain) + off[level],
+                                   (size_t)*out_w * *out_h * sizeof(bh::lens::Half4), hipMemcpyDeviceToHost);
+    return e == hipSuccess ? BH_OK : hip_fail(e, "hipMemcpy(sky level)");
 }
 
 int bh_sky_destroy(bh_sky* k) {
@@ -833,16 +873,21 @@ int bh_sky_destroy(bh_sky* k) {
     DeviceScope dev(c->device);
     c->skies.erase(std::remove(c->skies.begin(), c->skies.end(), k), c->skies.end());
     (void)hipFree(k->texels);
+    if (k->chain) (void)hipFree(k->chain);
     delete k;
     return BH_OK;
 }
 
+// what bh_shade_lens and bh_shade_lens_mip refuse alike
+static bool shade_desc_ok(const bh_ctx* c, const bh_shade_desc* d) {
+    if (!c || !d || !d->lens || !d->out_col || (reinterpret_cast<uintptr_t>(d->lens) & 7u)) return false;
+    if (bh::ss::log2_k(d->ss) > 3u || !frame_shape_ok(d->width, d->height, d->ss) || d->format > BH_OUT_BGRA8_SRGB) return false;
+    return !d->sky || d->sky->ctx == c;
+}
+
 // Validation and one kernel launch: no allocation, no synchronisation, no state (capturable from the first call).
 int bh_shade_lens(bh_ctx* c, const bh_shade_desc* d, void* stream) {
-    if (!c || !d || !d->lens || !d->out_col || (reinterpret_cast<uintptr_t>(d->lens) & 7u)) return bad_arg(__func__, __LINE__);
-    if (bh::ss::log2_k(d->ss) > 3u || !frame_shape_ok(d->width, d->height, d->ss) || d->format > BH_OUT_BGRA8_SRGB)
-        return bad_arg(__func__, __LINE__);
-    if (d->sky && d->sky->ctx != c) return bad_arg(__func__, __LINE__);
+    if (!shade_desc_ok(c, d)) return bad_arg(__func__, __LINE__);
     bh::LensShadeArgs a;
     a.lens = d->lens;
     a.sky = d->sky ? d->sky->texels : c->sky;
@@ -858,6 +903,35 @@ int bh_shade_lens(bh_ctx* c, const bh_shade_desc* d, void* stream) {
     if (dev.err != hipSuccess) return hip_fail(dev.err, "hipSetDevice");
     const int e = bh_launch_lens_shade(a, d->ss, d->format, reinterpret_cast<hipStream_t>(stream));
     if (e != 0) return hip_fail((hipError_t)e, "lens shade kernel launch");
+    return BH_OK;
+}
+
+// The same contract; the chain and its offsets travel in the launch's arguments.
+int bh_shade_lens_mip(bh_ctx* c, const bh_shade_desc* d, void* stream) {
+    if (!shade_desc_ok(c, d) || !d->sky || d->sky->n_levels == 0u) return bad_arg(__func__, __LINE__);
+    if (d->ss == 8u) {
+        g_last_error = "bh_shade_lens_mip: ss = 8 is not built: the plain shade is at its register limit there, and "
+                       "the filter is what replaces a large ss.";
+        return BH_ERR_UNSUPPORTED;
+    }
+    bh::LensMipArgs a;
+    a.lens = d->lens;
+    a.sky = d->sky->texels;
+    a.chain = d->sky->chain;
+    a.sky_w = d->sky->w;
+    a.sky_h = d->sky->h;
+    a.n_levels = d->sky->n_levels;
+    bh::lens::mip_offsets(a.sky_w, a.sky_h, a.level_off);
+    a.srgb_lut = c->lut;
+    a.srgb_enc = c->enc;
+    a.out_col = d->out_col;
+    a.out_blackout = d->out_blackout;
+    a.width = d->width;
+    a.height = d->height;
+    DeviceScope dev(c->device);
+    if (dev.err != hipSuccess) return hip_fail(dev.err, "hipSetDevice");
+    const int e = bh_launch_lens_shade_mip(a, d->ss, d->format, reinterpret_cast<hipStream_t>(stream));
+    if (e != 0) return hip_fail((hipError_t)e, "filtered lens shade kernel launch");
     return BH_OK;
 }
 

@@ -123,6 +123,9 @@ struct bh_sky {
     bh_ctx* ctx = nullptr;
     uint32_t* texels = nullptr;
     uint32_t w = 0, h = 0;
+    // bh_sky_create_mips: the levels >= 1 (csrc/bh_lens.hpp, mip_offsets), n_levels != 0; both unset otherwise
+    void* chain = nullptr;
+    uint32_t n_levels = 0;
 };
 
 // A weighted tile partition (include/bh_render.h, bh_partition_create).
@@ -205,6 +208,10 @@ BH_INTERNAL int bh_launch_refine_fast(const bh::MarchArgs& a, const bh::RefineAr
 BH_INTERNAL int bh_launch_refine_detect(const bh::MarchArgs& a, const bh::RefineArgs& r, hipStream_t s);
 // the lens shade (bh_lens.hip): ss in {1, 2, 4, 8}, format a bh_out_format
 BH_INTERNAL int bh_launch_lens_shade(const bh::LensShadeArgs& a, uint32_t ss, uint32_t format, hipStream_t s);
+// the filtered lens shade and the chain it reads (bh_lens_mip.hip): ss in {1, 2, 4}; the chain's kernels on `s`
+BH_INTERNAL int bh_launch_lens_shade_mip(const bh::LensMipArgs& a, uint32_t ss, uint32_t format, hipStream_t s);
+BH_INTERNAL int bh_launch_sky_mips(const uint32_t* sky, uint32_t w0, uint32_t h0, const float* srgb_lut, void* chain,
+                hipStream_t s);
 BH_INTERNAL int bh_march_blocks_per_cu_exact(void);
 BH_INTERNAL int bh_march_blocks_per_cu_fast(void);
 BH_INTERNAL int bh_launch_build_order(const uint8_t* cost, uint32_t n_tiles, uint32_t block, uint32_t centre,

@@ -7,6 +7,7 @@
 #include <math.h>
 #include <stddef.h>
 #include <stdint.h>
+#include <string.h>
 
 #include "../../include/bh_render.h"
 
@@ -126,6 +127,239 @@ BH_LENS_HD Acc shade_pixel(const bh_lens_px* lens, uint32_t width, uint32_t x, u
                            const float* lut) {
     const size_t vw = (size_t)width * K;
     Acc a = sum_y<K, K, BO>(lens + (size_t)y * K * vw + (size_t)x * K, vw, s, lut);
+    if constexpr (K > 1) {
+        constexpr float scale = 1.0f / (float)(K * K);
+        a.col = {a.col.r * scale, a.col.g * scale, a.col.b * scale};
+        if constexpr (BO) a.bo = {a.bo.r * scale, a.bo.g * scale, a.bo.b * scale};
+    }
+    return a;
+}
+
+// ---- the filtered shade (include/bh_render.h, "Filtered lens shades"): a mip chain of the sky, the level of a
+// record taken from its neighbours in the lens.  bh_lens_mip.hip runs these per texel and per output pixel,
+// bh_sky_mips_host and bh_lens_shade_mip_host (bh_mirror.cpp) the same functions in loops.
+constexpr uint32_t MIP_MAX_LEVELS = 16;  // a side is at most 32768 = 2^15
+
+BH_LENS_HD uint32_t mip_levels(uint32_t w0, uint32_t h0) {
+    uint32_t m = w0 > h0 ? w0 : h0, n = 1;
+    while (m >>= 1) ++n;
+    return n;
+}
+BH_LENS_HD uint32_t mip_side(uint32_t s0, uint32_t l) { return (s0 >> l) != 0u ? s0 >> l : 1u; }
+// off[l], l in 1..n-1: the first texel of level l in the chain's storage (levels 1.. back to back, 8 bytes per
+// texel); off[0] = 0 is not used.  Returns the chain's texels: under 2^30 / 3 + 2^16.
+BH_LENS_HD uint32_t mip_offsets(uint32_t w0, uint32_t h0, uint32_t off[MIP_MAX_LEVELS]) {
+    uint32_t at = 0;
+    const uint32_t n = mip_levels(w0, h0);
+    for (uint32_t l = 0; l < MIP_MAX_LEVELS; ++l) {
+        off[l] = l >= 1u && l < n ? at : 0u;
+        if (l >= 1u && l < n) at += mip_side(w0, l) * mip_side(h0, l);
+    }
+    return at;
+}
+
+// A texel of a level >= 1: four halves r, g, b, 1.0 as two little-endian words (r | g << 16, b | a << 16).  The
+// device converts with its instructions; the host spells both conversions out on the bits, so the mirrors need
+// no half-float support from the host compiler's runtime.
+struct Half4 { uint32_t lo, hi; };
+BH_LENS_HD float half_to_f32(uint32_t h) {  // exact
+#if defined(__HIP_DEVICE_COMPILE__)
+    const uint16_t b = (uint16_t)h;
+    return (float)*reinterpret_cast<const _Float16*>(&b);
+#else
+    const uint32_t e = (h >> 10) & 31u, m = h & 1023u;
+    const float s = (h & 0x8000u) ? -1.0f : 1.0f;
+    if (e == 0u) return s * ((float)m * 0x1p-24f);
+    if (e == 31u) return m ? NAN : s * INFINITY;
+    return s * ldexpf((float)(m | 1024u), (int)e - 25);
+#endif
+}
+BH_LENS_HD uint32_t f32_to_half(float f) {  // round to nearest even
+#if defined(__HIP_DEVICE_COMPILE__)
+    const _Float16 h = (_Float16)f;
+    return *reinterpret_cast<const uint16_t*>(&h);
+#else
+    uint32_t x;
+    memcpy(&x, &f, 4);
+    const uint32_t sign = (x >> 16) & 0x8000u, ex = (x >> 23) & 255u;
+    uint32_t man = x & 0x7fffffu;
+    if (ex == 255u) return sign | 0x7c00u | (man ? 0x200u : 0u);
+    const int32_t e = (int32_t)ex - 127 + 15;
+    if (e >= 31) return sign | 0x7c00u;
+    if (e <= 0) {  // a subnormal half, or zero: man * 2^(e - 14) in units of 2^-24
+        if (e < -10) return sign;
+        man |= 0x800000u;
+        const uint32_t shift = (uint32_t)(14 - e), q = man >> shift, rem = man & ((1u << shift) - 1u), half = 1u << (shift - 1u);
+        return sign | (q + ((rem > half || (rem == half && (q & 1u))) ? 1u : 0u));
+    }
+    const uint32_t q = ((uint32_t)e << 10) | (man >> 13), rem = man & 0x1fffu;
+    return sign | (q + ((rem > 0x1000u || (rem == 0x1000u && (q & 1u))) ? 1u : 0u));  // a carry into the exponent is the rounding
+#endif
+}
+BH_LENS_HD Rgb widen(Half4 t) { return {half_to_f32(t.lo & 0xffffu), half_to_f32(t.lo >> 16), half_to_f32(t.hi & 0xffffu)}; }
+
+// 8-byte load and store of a texel of a level >= 1
+BH_LENS_HD Half4 load_half4(const Half4* p) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    const uint2 t = *reinterpret_cast<const uint2*>(p);
+    return {t.x, t.y};
+#else
+    return *p;
+#endif
+}
+BH_LENS_HD void store_half4(Half4* p, Half4 t) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    *reinterpret_cast<uint2*>(p) = make_uint2(t.lo, t.hi);
+#else
+    *p = t;
+#endif
+}
+
+// A texel of level l from its four sources a b / c d of level l - 1 (the normative average, alpha 1.0).
+BH_LENS_HD Half4 mip_texel(Rgb a, Rgb b, Rgb c, Rgb d) {
+    const float r = ((a.r + b.r) + (c.r + d.r)) * 0.25f, g = ((a.g + b.g) + (c.g + d.g)) * 0.25f;
+    const float bl = ((a.b + b.b) + (c.b + d.b)) * 0.25f;
+    return {f32_to_half(r) | f32_to_half(g) << 16, f32_to_half(bl) | 0x3c00u << 16};
+}
+// Texel (i, j) of level 1 from level 0 (w x h), and of a level l >= 2 from level l - 1 (w x h): the second
+// source of an axis clamps to the last texel, so a side that has reached 1 (or an odd side's last texel) holds.
+BH_LENS_HD Half4 mip_down0(const SkyView& s, const float* lut, uint32_t i, uint32_t j) {
+    const int32_t wm = (int32_t)s.w - 1, hm = (int32_t)s.h - 1;
+    const int32_t x0 = clampi((int32_t)(2u * i), 0, wm), x1 = clampi((int32_t)(2u * i + 1u), 0, wm);
+    const int32_t y0 = clampi((int32_t)(2u * j), 0, hm), y1 = clampi((int32_t)(2u * j + 1u), 0, hm);
+    const uint32_t a = texel(s, x0, y0), b = texel(s, x1, y0), c = texel(s, x0, y1), d = texel(s, x1, y1);
+    return mip_texel(decode(lut, a), decode(lut, b), decode(lut, c), decode(lut, d));
+}
+BH_LENS_HD Half4 mip_down(const Half4* src, uint32_t w, uint32_t h, uint32_t i, uint32_t j) {
+    const uint32_t x0 = 2u * i < w - 1u ? 2u * i : w - 1u, x1 = 2u * i + 1u < w - 1u ? 2u * i + 1u : w - 1u;
+    const uint32_t y0 = 2u * j < h - 1u ? 2u * j : h - 1u, y1 = 2u * j + 1u < h - 1u ? 2u * j + 1u : h - 1u;
+    const Half4 a = load_half4(src + y0 * w + x0), b = load_half4(src + y0 * w + x1);
+    const Half4 c = load_half4(src + y1 * w + x0), d = load_half4(src + y1 * w + x1);
+    return mip_texel(widen(a), widen(b), widen(c), widen(d));
+}
+
+// A sky with its chain: level 0 as SkyView, the levels >= 1 at chain + off[l].
+struct MipView {
+    SkyView s;
+    const Half4* chain;
+    const uint32_t* off;  // MIP_MAX_LEVELS entries (mip_offsets)
+    uint32_t n_levels;
+};
+
+// sample()'s arithmetic on level l >= 1: its sides, its half texels widened, no table.  The coordinates are a
+// valid record's (no NaN: an invalid record never comes here).
+BH_LENS_HD Rgb sample_mip(const MipView& m, uint32_t l, float u, float v) {
+    const uint32_t w = mip_side(m.s.w, l), h = mip_side(m.s.h, l);
+    const Half4* lev = m.chain + m.off[l];
+    float tx = u * (float)w - 0.5f;
+    float ty = v * (float)h - 0.5f;
+    tx = fminf(fmaxf(tx, -1.0f), (float)w);
+    ty = fminf(fmaxf(ty, -1.0f), (float)h);
+    const float fx0 = floorf(tx), fy0 = floorf(ty);
+    const float fa = tx - fx0, fb = ty - fy0;
+    int32_t x0 = (int32_t)fx0, y0 = (int32_t)fy0;
+    const int32_t wm = (int32_t)w - 1, hm = (int32_t)h - 1;
+    const int32_t x1 = clampi(x0 + 1, 0, wm), y1 = clampi(y0 + 1, 0, hm);
+    x0 = clampi(x0, 0, wm);
+    y0 = clampi(y0, 0, hm);
+    const Half4 w00 = load_half4(lev + (uint32_t)y0 * w + (uint32_t)x0), w10 = load_half4(lev + (uint32_t)y0 * w + (uint32_t)x1);
+    const Half4 w01 = load_half4(lev + (uint32_t)y1 * w + (uint32_t)x0), w11 = load_half4(lev + (uint32_t)y1 * w + (uint32_t)x1);
+    const Rgb t00 = widen(w00), t10 = widen(w10), t01 = widen(w01), t11 = widen(w11);
+    const float ia = 1.0f - fa, ib = 1.0f - fb;
+    const Rgb top = {t00.r * ia + t10.r * fa, t00.g * ia + t10.g * fa, t00.b * ia + t10.b * fa};
+    const Rgb bot = {t01.r * ia + t11.r * fa, t01.g * ia + t11.g * fa, t01.b * ia + t11.b * fa};
+    return {top.r * ib + bot.r * fb, top.g * ib + bot.g * fb, top.b * ib + bot.b * fb};
+}
+
+BH_LENS_HD bool valid_px(bh_lens_px r) { return r.u >= 0.0f && r.v == r.v; }
+// F of one axis: the squared footprint, in level-0 texels, between a valid centre c and its neighbour n
+BH_LENS_HD float footprint(bh_lens_px c, bh_lens_px n, float w0, float h0) {
+    if (!valid_px(n)) return 0.0f;
+    float du = fabsf(n.u - c.u);
+    if (du > 0.5f) du = 1.0f - du;  // the seam
+    const float dv = fabsf(n.v - c.v);
+    const float su = du * w0, sv = dv * h0;
+    return su * su + sv * sv;
+}
+BH_LENS_HD int32_t float_bits(float f) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    return __float_as_int(f);
+#else
+    int32_t i;
+    memcpy(&i, &f, 4);
+    return i;
+#endif
+}
+
+// col of the record c from its neighbours xn and yn: the level from the footprint, two levels blended.  An axis
+// without a neighbour passes an invalid record: F = 0 either way.
+BH_LENS_HD Rgb shade_mip_rec(bh_lens_px c, bh_lens_px xn, bh_lens_px yn, const MipView& m, const float* lut) {
+    if (!valid_px(c) || m.n_levels == 1u) return shade(c.u, c.v, m.s, lut);
+    const float w0 = (float)m.s.w, h0 = (float)m.s.h;
+    const float rho2 = fmaxf(footprint(c, xn, w0, h0), footprint(c, yn, w0, h0));
+    const int32_t q = float_bits(rho2) - 0x3f800000;  // log2(rho2), 9.23 fixed point
+    if (q <= 0) return shade(c.u, c.v, m.s, lut);
+    const uint32_t L = (uint32_t)(q >> 24);
+    Rgb col;
+    if (L >= m.n_levels - 1u) {
+        col = sample_mip(m, m.n_levels - 1u, c.u, c.v);
+    } else {
+        const float f = (float)(q & 0xffffff) * 0x1p-24f, g = 1.0f - f;
+        const Rgb lo = L == 0u ? sample(m.s, lut, c.u, c.v) : sample_mip(m, L, c.u, c.v);
+        const Rgb hi = sample_mip(m, L + 1u, c.u, c.v);
+        col = {lo.r * g + hi.r * f, lo.g * g + hi.g * f, lo.b * g + hi.b * f};
+    }
+    col.g = col.g * sqrtf(col.g);
+    col.b = col.b * sqrtf(col.b);
+    return col;
+}
+// Record (vx, vy) of a lens of vw x vh records and its neighbours, three loads.  Every index stays inside
+// vw x vh: a last column or row looks backwards, a side of 1 has no neighbour.
+BH_LENS_HD Rgb shade_mip(const bh_lens_px* lens, uint32_t vw, uint32_t vh, uint32_t vx, uint32_t vy, const MipView& m,
+                         const float* lut) {
+    const size_t at = (size_t)vy * vw + vx;
+    const bh_lens_px none{BH_LENS_BLACKOUT, 0.0f};
+    const bh_lens_px c = load_px(lens + at);
+    const bh_lens_px xn = vw > 1u ? load_px(vx + 1u < vw ? lens + at + 1 : lens + at - 1) : none;
+    const bh_lens_px yn = vh > 1u ? load_px(vy + 1u < vh ? lens + at + vw : lens + at - vw) : none;
+    return shade_mip_rec(c, xn, yn, m, lut);
+}
+
+// sum_x, sum_y and shade_pixel over shade_mip: the same trees, the records addressed by their place in the
+// virtual frame, since a record's neighbour is the virtual grid's, not the output pixel's.
+template <int N, int K, bool BO>
+BH_LENS_HD Acc sum_x_mip(const bh_lens_px* lens, uint32_t vw, uint32_t vh, uint32_t vx, uint32_t vy, const MipView& m,
+                         const float* lut) {
+    if constexpr (N == 1) {
+        Acc a{shade_mip(lens, vw, vh, vx, vy, m, lut), {0.0f, 0.0f, 0.0f}};
+        if constexpr (BO) a.bo = blackout(a.col);
+        return a;
+    } else {
+        const Acc lo = sum_x_mip<N / 2, K, BO>(lens, vw, vh, vx, vy, m, lut);
+        const Acc hi = sum_x_mip<N / 2, K, BO>(lens, vw, vh, vx + N / 2, vy, m, lut);
+        const Acc r = add<BO>(lo, hi);
+#if defined(__HIP_DEVICE_COMPILE__)
+        // K = 4: two records, up to four bilinear samples, in flight at a time (what sum_x does at K = 8)
+        if constexpr (K == 4 && N == 2) __builtin_amdgcn_sched_barrier(0);
+#endif
+        return r;
+    }
+}
+template <int N, int K, bool BO>
+BH_LENS_HD Acc sum_y_mip(const bh_lens_px* lens, uint32_t vw, uint32_t vh, uint32_t vx, uint32_t vy, const MipView& m,
+                         const float* lut) {
+    if constexpr (N == 1) {
+        return sum_x_mip<K, K, BO>(lens, vw, vh, vx, vy, m, lut);
+    } else {
+        const Acc lo = sum_y_mip<N / 2, K, BO>(lens, vw, vh, vx, vy, m, lut);
+        const Acc hi = sum_y_mip<N / 2, K, BO>(lens, vw, vh, vx, vy + N / 2, m, lut);
+        return add<BO>(lo, hi);
+    }
+}
+template <int K, bool BO>
+BH_LENS_HD Acc shade_pixel_mip(const bh_lens_px* lens, uint32_t width, uint32_t height, uint32_t x, uint32_t y,
+                               const MipView& m, const float* lut) {
+    Acc a = sum_y_mip<K, K, BO>(lens, width * K, height * K, x * K, y * K, m, lut);
     if constexpr (K > 1) {
         constexpr float scale = 1.0f / (float)(K * K);
         a.col = {a.col.r * scale, a.col.g * scale, a.col.b * scale};

@@ -250,9 +250,10 @@ def shutter_resolve_host(samples: np.ndarray, n_sub: int, ss: int = 1) -> np.nda
     return out
 
 
-def lens_shade_host(lens: np.ndarray, sky: np.ndarray, ss: int = 1):
+def lens_shade_host(lens: np.ndarray, sky: np.ndarray, ss: int = 1, mip: bool = False):
     """bh_lens_shade_host (host only): what the lens shade kernel runs, on the CPU.  `lens`: (ss*H, ss*W, 2)
-    float32 records (u, v); `sky`: (h, w, 4) uint8 RGBA8 sRGB -> (col, blackout_col), fp32 (H, W, 4)."""
+    float32 records (u, v); `sky`: (h, w, 4) uint8 RGBA8 sRGB -> (col, blackout_col), fp32 (H, W, 4).
+    mip=True: bh_lens_shade_mip_host, the filtered shade over the sky's mip chain (ss 1, 2 or 4)."""
     ln = np.ascontiguousarray(lens, np.float32)
     s = np.ascontiguousarray(sky, np.uint8)
     k = _ss_arg(ss)
@@ -262,9 +263,22 @@ def lens_shade_host(lens: np.ndarray, sky: np.ndarray, ss: int = 1):
         raise BhError(_abi.BH_ERR_INVALID_ARG, "lens_shade_host: the lens sides must be multiples of ss")
     h, w = ln.shape[0] // k, ln.shape[1] // k
     col, bo = np.empty((h, w, 4), np.float32), np.empty((h, w, 4), np.float32)
-    check(load().bh_lens_shade_host(ln.ctypes.data, w, h, k, s.ctypes.data, s.shape[1], s.shape[0], col.ctypes.data,
-                                    bo.ctypes.data), "bh_lens_shade_host")
+    name = "bh_lens_shade_mip_host" if mip else "bh_lens_shade_host"
+    check(getattr(load(), name)(ln.ctypes.data, w, h, k, s.ctypes.data, s.shape[1], s.shape[0], col.ctypes.data,
+                                bo.ctypes.data), name)
     return col, bo
+
+
+def sky_mips_host(sky: np.ndarray, level: int) -> np.ndarray:
+    """bh_sky_mips_host (host only): level `level` >= 1 of the mip chain of `sky` ((h, w, 4) uint8 RGBA8 sRGB), by
+    the chain kernels' own functions -> float16 (h_l, w_l, 4)."""
+    s = np.ascontiguousarray(sky, np.uint8)
+    if s.ndim != 3 or s.shape[2] != 4:
+        raise BhError(_abi.BH_ERR_INVALID_ARG, "sky_mips_host: sky must be (h, w, 4)")
+    lv = _ss_arg(level)
+    out = np.empty((max(1, s.shape[0] >> min(lv, 31)), max(1, s.shape[1] >> min(lv, 31)), 4), np.float16)
+    check(load().bh_sky_mips_host(s.ctypes.data, s.shape[1], s.shape[0], lv, out.ctypes.data), "bh_sky_mips_host")
+    return out
 
 
 def _adaptive_desc(ss, adaptive, tile_mask, refined_tiles, n_frames: int, width: int, height: int):
@@ -571,10 +585,12 @@ class Scene:
                                       C.byref(d), _ptr(lens), _stream_handle(stream)), "bh_render_lens")
 
     def shade(self, lens, output, blackout_output=None, *, fmt: int = BH_OUT_RGBA32F, sky: "Sky | None" = None,
-              ss: int = 1, width: int | None = None, height: int | None = None, stream=None) -> None:
+              ss: int = 1, width: int | None = None, height: int | None = None, stream=None, mip: bool = False) -> None:
         """bh_shade_lens: `lens` (render_lens of ss*width x ss*height) and a sky -> the bytes render() -- with
         ss > 1, render(ss=ss) -- writes for that view with that sky.  `sky`: a Sky of this scene, or None for the
-        scene's own.  Asynchronous on `stream`; allocates nothing (capturable from the first call)."""
+        scene's own.  Asynchronous on `stream`; allocates nothing (capturable from the first call).
+        mip=True: bh_shade_lens_mip, the sky filtered through its mip chain, the level taken from the lens; `sky`
+        must be a Sky(..., mips=True), ss 1, 2 or 4."""
         k = _ss_arg(ss)
         d = _abi.bh_shade_desc()
         d.width, d.height, d.ss, d.format = width or self.width, height or self.height, k, fmt
@@ -586,7 +602,8 @@ class Scene:
         _check_size(blackout_output, need, "blackout_output", "shade")
         d.lens, d.sky = _ptr(lens), None if sky is None else sky.handle
         d.out_col, d.out_blackout = _ptr(output), _ptr(blackout_output)
-        check(self.lib.bh_shade_lens(self._ctx, C.byref(d), _stream_handle(stream)), "bh_shade_lens")
+        name = "bh_shade_lens_mip" if mip else "bh_shade_lens"
+        check(getattr(self.lib, name)(self._ctx, C.byref(d), _stream_handle(stream)), name)
 
     def set_clock_probe(self, acc, stride: int = 256) -> None:
         """bh_set_clock_probe: arm (acc = a zeroed device buffer of 128 u64) or disarm (acc = None) the
@@ -619,17 +636,35 @@ class Scene:
 
 class Sky:
     """bh_sky (include/bh_render.h): a sky beside the scene's own, for Scene.shade(sky=...).  `array`: (h, w, 4)
-    uint8 RGBA8 sRGB texels (synthetic_sky, load_sky).  It belongs to `scene`; Scene.close() closes it."""
+    uint8 RGBA8 sRGB texels (synthetic_sky, load_sky).  It belongs to `scene`; Scene.close() closes it.
+    mips=True: bh_sky_create_mips, the sky with its mip chain, for Scene.shade(mip=True)."""
 
-    def __init__(self, scene: "Scene", array: np.ndarray) -> None:
+    def __init__(self, scene: "Scene", array: np.ndarray, mips: bool = False) -> None:
         a = np.ascontiguousarray(array, dtype=np.uint8)
         if a.ndim != 3 or a.shape[2] != 4:
             raise ValueError("sky must be (H, W, 4) uint8 RGBA (Rgba8UnormSrgb texels)")
         self.scene, self.width, self.height = scene, a.shape[1], a.shape[0]
         h = C.c_void_p()
-        check(scene.lib.bh_sky_create(scene._ctx, a.ctypes.data, a.shape[1], a.shape[0], C.byref(h)), "bh_sky_create")
+        name = "bh_sky_create_mips" if mips else "bh_sky_create"
+        check(getattr(scene.lib, name)(scene._ctx, a.ctypes.data, a.shape[1], a.shape[0], C.byref(h)), name)
         self.handle = h.value
         scene._skies.append(self)
+
+    @property
+    def levels(self) -> int:
+        """bh_sky_levels: the levels of the mip chain, level 0 included; 0 for a sky without one."""
+        n = C.c_uint32()
+        check(self.scene.lib.bh_sky_levels(self.handle, C.byref(n)), "bh_sky_levels")
+        return n.value
+
+    def level(self, l: int) -> np.ndarray:
+        """bh_sky_read_level: level l >= 1 of the chain, copied from the device -> float16 (h_l, w_l, 4)."""
+        w, h = C.c_uint32(), C.c_uint32()
+        lv = _ss_arg(l)
+        check(self.scene.lib.bh_sky_read_level(self.handle, lv, C.byref(w), C.byref(h), None), "bh_sky_read_level")
+        out = np.empty((h.value, w.value, 4), np.float16)
+        check(self.scene.lib.bh_sky_read_level(self.handle, lv, C.byref(w), C.byref(h), out.ctypes.data), "bh_sky_read_level")
+        return out
 
     def close(self) -> None:
         """Free the device texels (after the shades that read them have completed).  A no-op when already
@@ -839,7 +874,7 @@ def tiles_unpack_rgbm_partition(packed, out_col, out_blackout, partition: "Parti
           "bh_tiles_unpack_rgbm_partition")
 
 
-__all__ = ["Camera", "Sky", "lens_shade_host", "ss_resolve_host", "refine_mask_host", "refine_cover_host", "Partition", "Presenter", "partition_map", "tiles_unpack_rgbm_partition", "CameraController", "CameraUniform", "Uniforms", "Scene", "synthetic_sky", "shard_tile_count", "tiles_unpack",
+__all__ = ["Camera", "Sky", "lens_shade_host", "sky_mips_host", "ss_resolve_host", "refine_mask_host", "refine_cover_host", "Partition", "Presenter", "partition_map", "tiles_unpack_rgbm_partition", "CameraController", "CameraUniform", "Uniforms", "Scene", "synthetic_sky", "shard_tile_count", "tiles_unpack",
            "tiles_unpack_rgb", "tiles_unpack_rgbm", "tile_bytes", "BH_LAYOUT_TILES_RGBM", "BH_LAYOUT_TILES_RGBM14",
            "BH_UNPACK_RGBM14",
            "srgb_encode_table", "load_sky", "bloom_plan_failures", "BH_OUT_BGRA8_SRGB",

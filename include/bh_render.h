@@ -463,6 +463,57 @@ int bh_lens_shade_host(const bh_lens_px* lens, uint32_t width, uint32_t height, 
                        const uint8_t* sky_rgba8, uint32_t sky_w, uint32_t sky_h,
                        float* out_col_rgba, float* out_blackout_rgba_or_NULL);
 
+/* Filtered lens shades: a mip chain of the sky, the level of each record taken from the lens (not in the
+ * reference, whose one tap is textureSampleLevel(..., 0.0)).  bh_shade_lens takes one bilinear tap of level 0
+ * per record, which aliases once neighbouring records land more than a texel apart: a sky finer than the frame,
+ * and around the shadow rim whatever the sky.  A lens holds what a texture unit would use -- every record's
+ * (u, v) beside its neighbours' -- so the footprint is a difference of two records.  Normative:
+ * The chain of a sky of w0 x h0 texels.  Level 0 is the sky's RGBA8-sRGB texels.  Level l >= 1 is
+ *   w_l x h_l = max(1, w_(l-1) >> 1) x max(1, h_(l-1) >> 1); n_levels = 1 + floor(log2(max(w0, h0))).  Texel
+ *   (i, j) of level l, channels r, g, b: the sources are level l-1 at x0 = min(2i, w_(l-1) - 1),
+ *   x1 = min(2i + 1, w_(l-1) - 1), y0 and y1 likewise, read as fp32 linear values (level 0 through the 256-entry
+ *   sRGB decode table, levels >= 1 the stored half widened, which is exact); the value is
+ *   RNE_f16(((a + b) + (c + d)) * 0.25f), a = T(x0, y0), b = T(x1, y0), c = T(x0, y1), d = T(x1, y1), in fp32
+ *   without FMA.  Alpha is stored as 1.0.  A level is 4 halves per texel (r, g, b, a), row-major; the chain
+ *   costs about 2/3 of level 0's bytes.
+ * The level of a record (x, y) of a lens grid of Wv x Hv records (with ss, the virtual frame).  A record is
+ *   valid iff u >= 0 && v == v (a sky ray, no NaN).  An invalid centre record is shaded as bh_shade_lens shades
+ *   it and nothing else (the sentinels, NaN -> texel (0, 0)).  The neighbour on axis x is x + 1 if x + 1 < Wv,
+ *   else x - 1, none if Wv == 1; the same on y.  Per axis, if the neighbour exists and is valid:
+ *     du = |u_n - u|, if du > 0.5f then du = 1.0f - du (the seam; the sampler itself still does not wrap),
+ *     dv = |v_n - v|, su = du * (float)w0, sv = dv * (float)h0, F = su * su + sv * sv; otherwise F = 0.
+ *   rho2 = fmaxf(F_x, F_y).  q = (int32)bits(rho2) - 0x3f800000: log2(rho2) in 9.23 fixed point, the mantissa
+ *   read as the fraction (no transcendentals).  If q <= 0 or n_levels == 1 the record is shaded as bh_shade_lens
+ *   shades it, bit for bit.  Otherwise L = q >> 24, f = (float)(q & 0xffffff) * 0x1p-24f (exact), and
+ *     if L >= n_levels - 1: c = sample_l(n_levels - 1); otherwise per channel c = cL * (1.0f - f) + cH * f with
+ *     cL = sample_l(L), cH = sample_l(L + 1) (two multiplies and one add, no FMA, for f == 0 too);
+ *     then g, b <- c * sqrtf(c).
+ *   sample_l(0) is the bilinear sample of bh_shade_lens; sample_l(l >= 1) is the same arithmetic with (w_l, h_l)
+ *   and the half texels widened, without the table.  The blackout test, the ss tree, the 1 / k^2 multiply and
+ *   the encode are exactly bh_shade_lens's.
+ * Not built: the filter inside bh_render and its ss / shutter / adaptive / presenter forms, anisotropic
+ * footprints, a chain for the context's own sky, ss = 8, fast math, tiled or sharded layouts. */
+/* bh_sky_create with the chain built on the device before the call returns.  Such a sky is usable wherever a
+ * bh_sky is; bh_shade_lens reads its level 0 only. */
+int bh_sky_create_mips(bh_ctx* ctx, const uint8_t* rgba8_srgb, uint32_t w, uint32_t h, bh_sky** out);
+/* n_levels of a sky of bh_sky_create_mips, 0 for a sky of bh_sky_create. */
+int bh_sky_levels(const bh_sky* sky, uint32_t* out_levels);
+/* For tests: the sides of level `level` (1 .. n_levels - 1) and, with a non-NULL host_out, a synchronous copy of
+ * its w * h * 4 halves.  BH_ERR_INVALID_ARG for a sky without a chain or a level outside that range. */
+int bh_sky_read_level(const bh_sky* sky, uint32_t level, uint32_t* out_w, uint32_t* out_h, void* host_out_or_NULL);
+/* bh_shade_lens with the filter above; the same contract (asynchronous, allocates nothing, keeps no state,
+ * capturable from its first call).  BH_ERR_INVALID_ARG for everything bh_shade_lens refuses, and for a NULL sky
+ * or a sky without a chain.  ss == 8 is BH_ERR_UNSUPPORTED with a sentence in bh_last_error(): filtering is what
+ * replaces a large ss. */
+int bh_shade_lens_mip(bh_ctx* ctx, const bh_shade_desc* desc, void* hip_stream);
+/* Host only: level `level` (1 .. n_levels - 1) of the chain of a sky, w_l * h_l * 4 halves, by the functions
+ * the chain kernels run (csrc/bh_lens.hpp). */
+int bh_sky_mips_host(const uint8_t* sky_rgba8, uint32_t sky_w, uint32_t sky_h, uint32_t level, uint16_t* out_halves);
+/* Host only: bh_lens_shade_host for bh_shade_lens_mip (ss in {1, 2, 4}). */
+int bh_lens_shade_mip_host(const bh_lens_px* lens, uint32_t width, uint32_t height, uint32_t ss,
+                           const uint8_t* sky_rgba8, uint32_t sky_w, uint32_t sky_h,
+                           float* out_col_rgba, float* out_blackout_rgba_or_NULL);
+
 /* Bloom::render (src/bloom.rs:53-71): the reference's Kawase bloom + remix chain over the scene's two
  * targets, on BGRA8-sRGB images (bh_render with BH_OUT_BGRA8_SRGB): `col` (full_image_input),
  * `blackout` (blackout_input) -> `out` (the surface), all width x height (1..65536 each, as bh_render),

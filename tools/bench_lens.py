@@ -9,7 +9,13 @@
           moves as many bytes (half of them read, half written).  frac_of_copy = the shade's compulsory bytes per
           second over the copy's.  The shade kernel carries no clock probe; `march_clock_mhz` is the clock the
           probe saw during this case's render_lens windows.
-    python tools/bench_lens.py [--cases 4096x2048:512,1920x1080:256] [--frames 20] [--rounds 5] [--out FILE]"""
+  --mip   instead of the above: (a) Scene.shade(mip=True) against (b) Scene.shade of the same lens and sky, RGBA16F,
+          both targets, at every ss of --ss that the filter has, windows alternating; once per sky of --mip-skies
+          (4096x2048: mostly the plain path, so a - b is the cost of the footprint; 16384x8192: minified).  Beside
+          them the chain build (bh_sky_create_mips less bh_sky_create of the same texels, wall clock, upload included
+          in both) and the clock the probe saw during the case's render_lens windows.
+    python tools/bench_lens.py [--cases 4096x2048:512,1920x1080:256] [--frames 20] [--rounds 5] [--out FILE]
+    python tools/bench_lens.py --mip --cases 1920x1080:256,4096x2048:512 --ss 1,2"""
 import argparse
 import json
 import statistics
@@ -27,6 +33,8 @@ p.add_argument("--ss", default="1,2,4", help="comma list of ss for the shade leg
 p.add_argument("--frames", type=int, default=20, help="launches per timed window")
 p.add_argument("--rounds", type=int, default=5)
 p.add_argument("--out", default=None, help="also append the JSON rows to this file")
+p.add_argument("--mip", action="store_true", help="measure the filtered shade against the plain one")
+p.add_argument("--mip-skies", default="4096x2048,16384x8192", help="with --mip: comma list of synthetic sky sizes")
 args = p.parse_args()
 if not torch.cuda.is_available():
     sys.exit("bench_lens: no GPU (there is no CPU timing path)")
@@ -63,6 +71,74 @@ def spread(ts):
     return round((max(ts) - min(ts)) / statistics.median(ts), 4)
 
 
+def write_out():
+    if args.out:
+        Path(args.out).parent.mkdir(parents=True, exist_ok=True)
+        with open(args.out, "a") as f:
+            for r in rows:
+                f.write(json.dumps(r) + "\n")
+
+
+def bench_mip():
+    import time
+    skies = {}
+    for name in args.mip_skies.split(","):
+        skies[name] = bh.synthetic_sky(*(int(v) for v in name.split("x")), seed=11)
+    for case in args.cases.split(","):
+        size, cap = case.split(":")
+        W, H = (int(v) for v in size.split("x"))
+        scene = bh.Scene(W, H, sky=sky, max_iters=int(cap), math=bh.BH_MATH_EXACT)
+        s = torch.cuda.Stream()
+        acc = torch.zeros(128, dtype=torch.int64, device="cuda")
+        for name, texels in skies.items():
+            walls = {}
+            for mips in (False, True, False, True):  # the second pair is the one reported (allocator warm)
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                k_sky = bh.Sky(scene, texels, mips=mips)
+                walls[mips] = (time.perf_counter() - t0) * 1e3
+                if mips:
+                    mip_sky = k_sky
+                else:
+                    k_sky.close()
+            emit({"what": "chain", "sky": name, "levels": mip_sky.levels, "create_ms": round(walls[False], 3),
+                  "create_mips_ms": round(walls[True], 3), "chain_ms": round(walls[True] - walls[False], 3)})
+            for k in (int(v) for v in args.ss.split(",") if int(v) in (1, 2, 4)):
+                vlens = torch.empty((k * H, k * W, 2), dtype=torch.float32, device="cuda")
+                clocks = []
+                for _ in range(3):
+                    clocks.append(window(lambda st: scene.render_lens(vlens, width=k * W, height=k * H, stream=st), s, scene, acc)[1])
+                col, bo = (torch.empty((H, W, 4), dtype=torch.float16, device="cuda") for _ in range(2))
+
+                def leg_a(st):
+                    scene.shade(vlens, col, bo, fmt=bh.BH_OUT_RGBA16F, sky=mip_sky, ss=k, stream=st, mip=True)
+
+                def leg_b(st):
+                    scene.shade(vlens, col, bo, fmt=bh.BH_OUT_RGBA16F, sky=mip_sky, ss=k, stream=st)
+
+                for _ in range(3):
+                    leg_a(s)
+                    leg_b(s)
+                torch.cuda.synchronize()
+                ta, tb = [], []
+                for _ in range(args.rounds):
+                    ta.append(window(leg_a, s)[0])
+                    tb.append(window(leg_b, s)[0])
+                ma, mb = statistics.median(ta), statistics.median(tb)
+                emit({"what": "shade_mip", "width": W, "height": H, "ss": k, "format": "rgba16f", "targets": 2, "sky": name,
+                      "camera": "A", "view_max_iters": int(cap), "frames": args.frames, "rounds": args.rounds,
+                      "a_mip_ms": [round(t, 5) for t in ta], "b_plain_ms": [round(t, 5) for t in tb],
+                      "a_median_ms": round(ma, 5), "b_median_ms": round(mb, 5), "a_over_b": round(ma / mb, 4),
+                      "spread_a": spread(ta), "spread_b": spread(tb), "march_clock_mhz": statistics.median(clocks)})
+                del vlens, col, bo
+            mip_sky.close()
+        scene.close()
+
+
+if args.mip:
+    bench_mip()
+    write_out()
+    sys.exit(0)
 for case in args.cases.split(","):
     size, cap = case.split(":")
     W, H = (int(v) for v in size.split("x"))
@@ -142,8 +218,4 @@ for case in args.cases.split(","):
             del col, bo, src, dst
         del vlens
     scene.close()
-if args.out:
-    Path(args.out).parent.mkdir(parents=True, exist_ok=True)
-    with open(args.out, "a") as f:
-        for r in rows:
-            f.write(json.dumps(r) + "\n")
+write_out()

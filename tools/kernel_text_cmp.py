@@ -52,9 +52,9 @@ with tempfile.TemporaryDirectory() as t:
     to, tn = Path(t) / "old", Path(t) / "new"
     to.mkdir()
     tn.mkdir()
-    for o in sorted(Path(args.old).glob("*.o")):
-        n = Path(args.new) / o.name
-        ko, kn = kernels(o, to), kernels(n, tn) if n.exists() else {}
+    for unit in sorted({f.name for d in (args.old, args.new) for f in Path(d).glob("*.o")}):  # a new unit has new kernels only
+        o, n = Path(args.old) / unit, Path(args.new) / unit
+        ko, kn = kernels(o, to) if o.exists() else {}, kernels(n, tn) if n.exists() else {}
         for name, h in sorted(ko.items()):
             if args.match not in name:
                 continue

@@ -11,7 +11,10 @@ Space F ArrowUp/Down/Left/Right P O).
 Every frame integrated over a shutter interval: 8 sub-frame cameras per frame, averaged before the encode.
 
     python tools/render_path.py --sky-frames DIR --out frames/sky
-A moving sky behind a still camera instead: one frame per image in DIR, the view marched once into a lens map."""
+A moving sky behind a still camera instead: one frame per image in DIR, the view marched once into a lens map.
+
+    python tools/render_path.py --sky-filter mip --sky stars_16k.jpg --width 1920 --height 1080
+The sky filtered through its mip chain: per frame a lens render and a filtered shade (bh_shade_lens_mip)."""
 import argparse
 import dataclasses
 import json
@@ -20,12 +23,6 @@ import time
 from pathlib import Path
 
 import numpy as np
-
-sys.path.insert(0, str(Path(__file__).resolve().parent.parent))
-import torch  # noqa: E402
-
-import black_hole_ray_marching_amd as bh  # noqa: E402
-from black_hole_ray_marching_amd.png import write_png  # noqa: E402
 
 p = argparse.ArgumentParser()
 p.add_argument("--width", type=int, default=1024)
@@ -51,13 +48,27 @@ p.add_argument("--shutter", type=int, choices=[1, 2, 4, 8, 16], default=1, metav
                     "camera t of a frame is where a copy of the controller takes the frame's camera in dt * S * t / N")
 p.add_argument("--shutter-frac", type=float, default=0.5, metavar="S",
                help="with --shutter: the part of a frame's dt the shutter stays open (default 0.5)")
+p.add_argument("--sky-filter", choices=["none", "mip"], default="none",
+               help="mip: every frame is a lens render (bh_render_lens) shaded through the sky's mip chain, the level "
+                    "taken from the lens (bh_shade_lens_mip); with --ss 1, 2 or 4 and with --sky-frames")
 args = p.parse_args()
+mip = args.sky_filter == "mip"
+if mip and (args.shutter > 1 or args.adaptive is not None):
+    sys.exit("render_path: --sky-filter mip does not combine with --shutter or --adaptive (the filter is a lens shade)")
+if mip and args.ss == 8:
+    sys.exit("render_path: --sky-filter mip takes --ss 1, 2 or 4 (bh_shade_lens_mip has no ss = 8)")
 if args.shutter > 1 and (args.adaptive is not None or args.sky_frames):
     sys.exit("render_path: --shutter does not combine with --adaptive or --sky-frames (no adaptive or lens shutter)")
 if args.adaptive is not None and args.ss == 1:
     p.error("--adaptive needs --ss 2, 4 or 8")
 if args.sky_frames and args.adaptive is not None:
     p.error("--sky-frames shades a lens map: there is no adaptive lens")
+# the arguments are good: now the imports that take seconds
+sys.path.insert(0, str(Path(__file__).resolve().parent.parent))
+import torch  # noqa: E402
+
+import black_hole_ray_marching_amd as bh  # noqa: E402
+from black_hole_ray_marching_amd.png import write_png  # noqa: E402
 W, H = args.width, args.height
 keys = []
 for item in filter(None, args.script.split(",")):
@@ -100,8 +111,8 @@ if args.sky_frames:
     lens = torch.empty((k * H, k * W, 2), dtype=torch.float32, device="cuda")
     scene.render_lens(lens, width=k * W, height=k * H)  # the only march of the run
     for f, path in enumerate(images):
-        frame_sky = bh.Sky(scene, bh.load_sky(path))
-        scene.shade(lens, col, bo, fmt=bh.BH_OUT_BGRA8_SRGB, sky=frame_sky, ss=k)
+        frame_sky = bh.Sky(scene, bh.load_sky(path), mips=mip)
+        scene.shade(lens, col, bo, fmt=bh.BH_OUT_BGRA8_SRGB, sky=frame_sky, ss=k, mip=mip)
         scene.bloom(col, bo, surf)
         if not args.no_png:
             write_png(out_dir / f"frame_{f:04d}.png", surf.cpu().numpy())
@@ -109,12 +120,18 @@ if args.sky_frames:
         frame_sky.close()
         log.append({"frame": f, "sky": path.name, "pos": cam.pos, "dir": cam.dir, "moved": False})
     args.frames = len(images)
+if mip and not args.sky_frames:  # the path's own sky with its chain, and the lens every frame marches into
+    path_sky = bh.Sky(scene, sky, mips=True)
+    path_lens = torch.empty((args.ss * H, args.ss * W, 2), dtype=torch.float32, device="cuda")
 for f in range(0 if args.sky_frames else args.frames):
     for k, a, b in keys:
         ctrl.process_key(k, a <= f <= b)
     cam, moved = ctrl.update_camera(cam, args.dt)
     scene.update(cam)
-    if args.shutter > 1:
+    if mip:
+        scene.render_lens(path_lens, width=args.ss * W, height=args.ss * H)
+        scene.shade(path_lens, col, bo, fmt=bh.BH_OUT_BGRA8_SRGB, sky=path_sky, ss=args.ss, mip=True)
+    elif args.shutter > 1:
         scene.render_shutter(col, bo, cameras=shutter_cameras(cam), fmt=bh.BH_OUT_BGRA8_SRGB, ss=args.ss)
     else:
         scene.render(col, bo, fmt=bh.BH_OUT_BGRA8_SRGB, ss=args.ss, adaptive=args.adaptive)
@@ -125,5 +142,5 @@ for f in range(0 if args.sky_frames else args.frames):
 torch.cuda.synchronize()
 dt = time.perf_counter() - t0
 (out_dir / "path.json").write_text(json.dumps(log, indent=0))
-print(json.dumps({"frames": args.frames, "width": W, "height": H, "ss": args.ss, "adaptive": args.adaptive, "shutter": args.shutter, "seconds": round(dt, 3),
+print(json.dumps({"frames": args.frames, "width": W, "height": H, "ss": args.ss, "adaptive": args.adaptive, "shutter": args.shutter, "sky_filter": args.sky_filter, "seconds": round(dt, 3),
                   "frames_per_s_incl_png": round(args.frames / dt, 2), "out": str(out_dir)}))
