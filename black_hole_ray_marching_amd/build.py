@@ -55,10 +55,8 @@ TU_FLAGS = {
     "bh_march_refine_lat.hip": ["-ffp-contract=off", "-fhip-fp32-correctly-rounded-divide-sqrt", "-fno-slp-vectorize",
                                 "-mllvm", "-disable-machine-licm"],
     "bh_tiles.hip": [],
-    # the lens shade: the march kernels' shading arithmetic, one rounding per op (bh_lens.hpp)
+    # the lens shades and the sky chain: the march kernels' shading arithmetic, one rounding per op (bh_lens.hpp)
     "bh_lens.hip": ["-ffp-contract=off", "-fhip-fp32-correctly-rounded-divide-sqrt", "-fno-slp-vectorize"],
-    # the filtered lens shade and its sky chain: bh_lens.hip's contract (the same header's arithmetic)
-    "bh_lens_mip.hip": ["-ffp-contract=off", "-fhip-fp32-correctly-rounded-divide-sqrt", "-fno-slp-vectorize"],
     # post-RA scheduling off: fused bloom chain 0.556 -> 0.548 ms (A/B r01; pre-RA off too: 0.561)
     # no SLP vectorisation: packed-FP32 forms of the filter's adjacent channel ops cost more than the
     # scalar ops on gfx950 (a v_pk op issues slower than two scalar ones, plus the shuffles and hazard

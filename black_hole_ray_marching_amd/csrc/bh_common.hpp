@@ -10,6 +10,19 @@
 
 namespace bh {
 
+// A launch's run-time word as a compile-time constant: what every launcher's ladder hands to its kernel choice.
+template <uint32_t V>
+struct Const { static constexpr uint32_t value = V; };
+// f(FMT) with the launch's output format (validated by the entry points) as a compile-time constant
+template <class F>
+__attribute__((visibility("hidden"))) inline int with_format(uint32_t format, F&& f) {
+    switch (format) {
+        case BH_OUT_RGBA32F: return f(Const<BH_OUT_RGBA32F>{});
+        case BH_OUT_RGBA16F: return f(Const<BH_OUT_RGBA16F>{});
+        default: return f(Const<BH_OUT_BGRA8_SRGB>{});
+    }
+}
+
 // Frames whose arguments travel inline in the kernel argument; a bh_render_frames call of more
 // (up to BH_MAX_FRAMES) stages them in a device table (bh_host.hpp, FrameTable).
 constexpr uint32_t BH_INLINE_FRAMES = 32;
@@ -136,18 +149,10 @@ struct LensShadeArgs {
     uint32_t sky_w, sky_h;
 };
 
-// One bh_shade_lens_mip launch (bh_lens_mip.hip): LensShadeArgs' fields and the sky's chain -- the levels >= 1,
-// 8 bytes per texel, level l at chain + level_off[l] texels (lens::mip_offsets).
-struct LensMipArgs {
-    const bh_lens_px* lens;
-    const uint32_t* sky;
+// One bh_shade_lens_mip launch (bh_lens.hip): the same and the sky's chain -- the levels >= 1, 8 bytes per
+// texel, level l at chain + level_off[l] texels (lens::mip_offsets).
+struct LensMipArgs : LensShadeArgs {
     const void* chain;
-    const float* srgb_lut;
-    const float* srgb_enc;
-    void* out_col;
-    void* out_blackout;        // or null
-    uint32_t width, height;    // the OUTPUT frame
-    uint32_t sky_w, sky_h;
     uint32_t n_levels;
     uint32_t level_off[16];
 };

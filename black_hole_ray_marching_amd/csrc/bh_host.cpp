@@ -885,20 +885,25 @@ static bool shade_desc_ok(const bh_ctx* c, const bh_shade_desc* d) {
     return !d->sky || d->sky->ctx == c;
 }
 
+// the arguments both shades share; sky: the desc's, or (bh_shade_lens only) the ctx's own
+static void fill_shade_args(const bh_ctx* c, const bh_shade_desc* d, bh::LensShadeArgs* a) {
+    a->lens = d->lens;
+    a->sky = d->sky ? d->sky->texels : c->sky;
+    a->sky_w = d->sky ? d->sky->w : c->sky_w;
+    a->sky_h = d->sky ? d->sky->h : c->sky_h;
+    a->srgb_lut = c->lut;
+    a->srgb_enc = c->enc;
+    a->out_col = d->out_col;
+    a->out_blackout = d->out_blackout;
+    a->width = d->width;
+    a->height = d->height;
+}
+
 // Validation and one kernel launch: no allocation, no synchronisation, no state (capturable from the first call).
 int bh_shade_lens(bh_ctx* c, const bh_shade_desc* d, void* stream) {
     if (!shade_desc_ok(c, d)) return bad_arg(__func__, __LINE__);
     bh::LensShadeArgs a;
-    a.lens = d->lens;
-    a.sky = d->sky ? d->sky->texels : c->sky;
-    a.sky_w = d->sky ? d->sky->w : c->sky_w;
-    a.sky_h = d->sky ? d->sky->h : c->sky_h;
-    a.srgb_lut = c->lut;
-    a.srgb_enc = c->enc;
-    a.out_col = d->out_col;
-    a.out_blackout = d->out_blackout;
-    a.width = d->width;
-    a.height = d->height;
+    fill_shade_args(c, d, &a);
     DeviceScope dev(c->device);
     if (dev.err != hipSuccess) return hip_fail(dev.err, "hipSetDevice");
     const int e = bh_launch_lens_shade(a, d->ss, d->format, reinterpret_cast<hipStream_t>(stream));
@@ -915,19 +920,10 @@ int bh_shade_lens_mip(bh_ctx* c, const bh_shade_desc* d, void* stream) {
         return BH_ERR_UNSUPPORTED;
     }
     bh::LensMipArgs a;
-    a.lens = d->lens;
-    a.sky = d->sky->texels;
+    fill_shade_args(c, d, &a);
     a.chain = d->sky->chain;
-    a.sky_w = d->sky->w;
-    a.sky_h = d->sky->h;
     a.n_levels = d->sky->n_levels;
     bh::lens::mip_offsets(a.sky_w, a.sky_h, a.level_off);
-    a.srgb_lut = c->lut;
-    a.srgb_enc = c->enc;
-    a.out_col = d->out_col;
-    a.out_blackout = d->out_blackout;
-    a.width = d->width;
-    a.height = d->height;
     DeviceScope dev(c->device);
     if (dev.err != hipSuccess) return hip_fail(dev.err, "hipSetDevice");
     const int e = bh_launch_lens_shade_mip(a, d->ss, d->format, reinterpret_cast<hipStream_t>(stream));

@@ -208,7 +208,7 @@ BH_INTERNAL int bh_launch_refine_fast(const bh::MarchArgs& a, const bh::RefineAr
 BH_INTERNAL int bh_launch_refine_detect(const bh::MarchArgs& a, const bh::RefineArgs& r, hipStream_t s);
 // the lens shade (bh_lens.hip): ss in {1, 2, 4, 8}, format a bh_out_format
 BH_INTERNAL int bh_launch_lens_shade(const bh::LensShadeArgs& a, uint32_t ss, uint32_t format, hipStream_t s);
-// the filtered lens shade and the chain it reads (bh_lens_mip.hip): ss in {1, 2, 4}; the chain's kernels on `s`
+// the filtered lens shade and the chain it reads (bh_lens.hip): ss in {1, 2, 4}; the chain's kernels on `s`
 BH_INTERNAL int bh_launch_lens_shade_mip(const bh::LensMipArgs& a, uint32_t ss, uint32_t format, hipStream_t s);
 BH_INTERNAL int bh_launch_sky_mips(const uint32_t* sky, uint32_t w0, uint32_t h0, const float* srgb_lut, void* chain,
                 hipStream_t s);

@@ -11,11 +11,15 @@
 
 #include "../../include/bh_render.h"
 
+// BH_LENS_FI: the cursor form of the resolve tree, its cursors and the pixel entry points, inlined whatever their
+// size -- left to the inliner, the filtered shade's K = 4 tree becomes a called function of 87 KB.
 #ifndef BH_LENS_HD
 #if defined(__HIPCC__) || defined(__CUDACC__)
 #define BH_LENS_HD __host__ __device__ inline
+#define BH_LENS_FI __host__ __device__ __attribute__((always_inline)) inline
 #else
 #define BH_LENS_HD inline
+#define BH_LENS_FI inline
 #endif
 #endif
 
@@ -30,28 +34,34 @@ BH_LENS_HD Rgb decode(const float* lut, uint32_t t) { return {lut[t & 0xffu], lu
 // a sky holds at most 2^30 texels (bh_create, bh_sky_create): a 32-bit element index
 BH_LENS_HD uint32_t texel(const SkyView& s, int32_t x, int32_t y) { return s.texels[(uint32_t)y * s.w + (uint32_t)x]; }
 
-// textureSampleLevel on Rgba8UnormSrgb, mag Linear, clamp to edge: sample_sky's arithmetic (bh_march_shade.hpp),
-// op for op.  A NaN coordinate takes texel (0, 0).
-BH_LENS_HD Rgb sample(const SkyView& s, const float* lut, float u, float v) {
-    if (u != u || v != v) return decode(lut, texel(s, 0, 0));
-    float tx = u * (float)s.w - 0.5f;
-    float ty = v * (float)s.h - 0.5f;
-    tx = fminf(fmaxf(tx, -1.0f), (float)s.w);
-    ty = fminf(fmaxf(ty, -1.0f), (float)s.h);
+// textureSampleLevel on Rgba8UnormSrgb, mag Linear, clamp to edge, of a w x h level: sample_sky's arithmetic
+// (bh_march_shade.hpp), op for op.  load(x, y) fetches a texel, widen(t) makes it an Rgb.
+template <class Load, class Widen>
+BH_LENS_HD Rgb bilinear(uint32_t w, uint32_t h, float u, float v, Load load, Widen widen) {
+    float tx = u * (float)w - 0.5f;
+    float ty = v * (float)h - 0.5f;
+    tx = fminf(fmaxf(tx, -1.0f), (float)w);
+    ty = fminf(fmaxf(ty, -1.0f), (float)h);
     const float fx0 = floorf(tx), fy0 = floorf(ty);
     const float fa = tx - fx0, fb = ty - fy0;
     int32_t x0 = (int32_t)fx0, y0 = (int32_t)fy0;
-    const int32_t wm = (int32_t)s.w - 1, hm = (int32_t)s.h - 1;
+    const int32_t wm = (int32_t)w - 1, hm = (int32_t)h - 1;
     const int32_t x1 = clampi(x0 + 1, 0, wm), y1 = clampi(y0 + 1, 0, hm);
     x0 = clampi(x0, 0, wm);
     y0 = clampi(y0, 0, hm);
-    const uint32_t w00 = texel(s, x0, y0), w10 = texel(s, x1, y0);  // the four gathers first: one wait
-    const uint32_t w01 = texel(s, x0, y1), w11 = texel(s, x1, y1);
-    const Rgb t00 = decode(lut, w00), t10 = decode(lut, w10), t01 = decode(lut, w01), t11 = decode(lut, w11);
+    const auto w00 = load(x0, y0), w10 = load(x1, y0);  // the four gathers first: one wait
+    const auto w01 = load(x0, y1), w11 = load(x1, y1);
+    const Rgb t00 = widen(w00), t10 = widen(w10), t01 = widen(w01), t11 = widen(w11);
     const float ia = 1.0f - fa, ib = 1.0f - fb;
     const Rgb top = {t00.r * ia + t10.r * fa, t00.g * ia + t10.g * fa, t00.b * ia + t10.b * fa};
     const Rgb bot = {t01.r * ia + t11.r * fa, t01.g * ia + t11.g * fa, t01.b * ia + t11.b * fa};
     return {top.r * ib + bot.r * fb, top.g * ib + bot.g * fb, top.b * ib + bot.b * fb};
+}
+// Level 0: packed texels decoded through the table.  A NaN coordinate takes texel (0, 0).
+BH_LENS_HD Rgb sample(const SkyView& s, const float* lut, float u, float v) {
+    if (u != u || v != v) return decode(lut, texel(s, 0, 0));
+    return bilinear(s.w, s.h, u, v, [&](int32_t x, int32_t y) { return texel(s, x, y); },
+                    [&](uint32_t t) { return decode(lut, t); });
 }
 
 // col of one record
@@ -92,6 +102,48 @@ BH_LENS_HD Acc add(const Acc& p, const Acc& q) {
 // neighbouring records of one lens row -- level 1 adds neighbours, level 2 the pair sums, ... -- and the same
 // tree over N rows' results; the sums the xor butterfly of bh_ss.hpp leaves in every lane of a group (fp32 add
 // is commutative bit for bit).  Each record is shaded on its own, the blackout test per sample.
+// A record is named by a cursor C: c.col() shades it, c.right(n) and c.down(n) name the record n columns or
+// rows on, and C::barrier_at<K>() is the N at which sum_x holds the scheduler (0: nowhere).  The filtered shade's
+// records (MipLens::Cursor) go through this form, the plain shade's through the pointer form below.
+template <int N, int K, bool BO, class C>
+BH_LENS_FI Acc sum_x(const C& c) {
+    if constexpr (N == 1) {
+        Acc a{c.col(), {0.0f, 0.0f, 0.0f}};
+        if constexpr (BO) a.bo = blackout(a.col);
+        return a;
+    } else {
+        const Acc lo = sum_x<N / 2, K, BO>(c), hi = sum_x<N / 2, K, BO>(c.right(N / 2));
+        const Acc r = add<BO>(lo, hi);
+#if defined(__HIP_DEVICE_COMPILE__)
+        if constexpr (N == C::template barrier_at<K>()) __builtin_amdgcn_sched_barrier(0);
+#endif
+        return r;
+    }
+}
+template <int N, int K, bool BO, class C>
+BH_LENS_FI Acc sum_y(const C& c) {
+    if constexpr (N == 1) {
+        return sum_x<K, K, BO>(c);
+    } else {
+        const Acc lo = sum_y<N / 2, K, BO>(c), hi = sum_y<N / 2, K, BO>(c.down(N / 2));
+        return add<BO>(lo, hi);
+    }
+}
+// The tree's result as the pixel: one multiply by 1 / K^2 (a power of two: exact)
+template <int K, bool BO>
+BH_LENS_HD Acc scaled(Acc a) {
+    if constexpr (K > 1) {
+        constexpr float scale = 1.0f / (float)(K * K);
+        a.col = {a.col.r * scale, a.col.g * scale, a.col.b * scale};
+        if constexpr (BO) a.bo = {a.bo.r * scale, a.bo.g * scale, a.bo.b * scale};
+    }
+    return a;
+}
+
+// The plain shade's tree: the same two recursions with a record named by its pointer and the rows vw records
+// apart.  It is kept beside the cursor form: over a pointer cursor the K = 2, 4 and 8 kernels came out with other
+// instruction order and measured 0.1 to 1.0 % slower at K = 8 in two sessions; this form
+// gives the machine code they had.
 template <int N, int K, bool BO>
 BH_LENS_HD Acc sum_x(const bh_lens_px* p, const SkyView& s, const float* lut) {
     if constexpr (N == 1) {
@@ -120,23 +172,26 @@ BH_LENS_HD Acc sum_y(const bh_lens_px* row, size_t vw, const SkyView& s, const f
     }
 }
 
-// Output pixel (x, y) of a width-pixel-wide frame from the lens of its virtual frame (K * width records per
-// row): its K x K records resolved as above, then one multiply by 1 / K^2 (a power of two: exact).
-template <int K, bool BO>
-BH_LENS_HD Acc shade_pixel(const bh_lens_px* lens, uint32_t width, uint32_t x, uint32_t y, const SkyView& s,
-                           const float* lut) {
-    const size_t vw = (size_t)width * K;
-    Acc a = sum_y<K, K, BO>(lens + (size_t)y * K * vw + (size_t)x * K, vw, s, lut);
-    if constexpr (K > 1) {
-        constexpr float scale = 1.0f / (float)(K * K);
-        a.col = {a.col.r * scale, a.col.g * scale, a.col.b * scale};
-        if constexpr (BO) a.bo = {a.bo.r * scale, a.bo.g * scale, a.bo.b * scale};
+// The plain shade's lens: the records of a width-pixel-wide output frame's virtual frame (K * width per row),
+// each shaded from its own two words.  pixel<K, BO>(x, y): output pixel (x, y) from its K x K records.
+struct PlainLens {
+    const bh_lens_px* lens;
+    uint32_t width;
+    SkyView s;
+    const float* lut;
+    template <int K, bool BO>
+    BH_LENS_FI Acc pixel(uint32_t x, uint32_t y) const {
+        const size_t vw = (size_t)width * K;
+        return scaled<K, BO>(sum_y<K, K, BO>(lens + (size_t)y * K * vw + (size_t)x * K, vw, s, lut));
     }
-    return a;
-}
+};
+
+// Output pixel (x, y) from a lens L (PlainLens, MipLens)
+template <int K, bool BO, class L>
+BH_LENS_FI Acc shade_pixel(const L& lens, uint32_t x, uint32_t y) { return lens.template pixel<K, BO>(x, y); }
 
 // ---- the filtered shade (include/bh_render.h, "Filtered lens shades"): a mip chain of the sky, the level of a
-// record taken from its neighbours in the lens.  bh_lens_mip.hip runs these per texel and per output pixel,
+// record taken from its neighbours in the lens.  bh_lens.hip runs these per texel and per output pixel,
 // bh_sky_mips_host and bh_lens_shade_mip_host (bh_mirror.cpp) the same functions in loops.
 constexpr uint32_t MIP_MAX_LEVELS = 16;  // a side is at most 32768 = 2^15
 
@@ -246,29 +301,13 @@ struct MipView {
     uint32_t n_levels;
 };
 
-// sample()'s arithmetic on level l >= 1: its sides, its half texels widened, no table.  The coordinates are a
-// valid record's (no NaN: an invalid record never comes here).
+// sample() on level l >= 1: its sides, its half texels widened, no table.  The coordinates are a valid
+// record's (no NaN: an invalid record never comes here).
 BH_LENS_HD Rgb sample_mip(const MipView& m, uint32_t l, float u, float v) {
     const uint32_t w = mip_side(m.s.w, l), h = mip_side(m.s.h, l);
     const Half4* lev = m.chain + m.off[l];
-    float tx = u * (float)w - 0.5f;
-    float ty = v * (float)h - 0.5f;
-    tx = fminf(fmaxf(tx, -1.0f), (float)w);
-    ty = fminf(fmaxf(ty, -1.0f), (float)h);
-    const float fx0 = floorf(tx), fy0 = floorf(ty);
-    const float fa = tx - fx0, fb = ty - fy0;
-    int32_t x0 = (int32_t)fx0, y0 = (int32_t)fy0;
-    const int32_t wm = (int32_t)w - 1, hm = (int32_t)h - 1;
-    const int32_t x1 = clampi(x0 + 1, 0, wm), y1 = clampi(y0 + 1, 0, hm);
-    x0 = clampi(x0, 0, wm);
-    y0 = clampi(y0, 0, hm);
-    const Half4 w00 = load_half4(lev + (uint32_t)y0 * w + (uint32_t)x0), w10 = load_half4(lev + (uint32_t)y0 * w + (uint32_t)x1);
-    const Half4 w01 = load_half4(lev + (uint32_t)y1 * w + (uint32_t)x0), w11 = load_half4(lev + (uint32_t)y1 * w + (uint32_t)x1);
-    const Rgb t00 = widen(w00), t10 = widen(w10), t01 = widen(w01), t11 = widen(w11);
-    const float ia = 1.0f - fa, ib = 1.0f - fb;
-    const Rgb top = {t00.r * ia + t10.r * fa, t00.g * ia + t10.g * fa, t00.b * ia + t10.b * fa};
-    const Rgb bot = {t01.r * ia + t11.r * fa, t01.g * ia + t11.g * fa, t01.b * ia + t11.b * fa};
-    return {top.r * ib + bot.r * fb, top.g * ib + bot.g * fb, top.b * ib + bot.b * fb};
+    return bilinear(w, h, u, v, [&](int32_t x, int32_t y) { return load_half4(lev + (uint32_t)y * w + (uint32_t)x); },
+                    [](Half4 t) { return widen(t); });
 }
 
 BH_LENS_HD bool valid_px(bh_lens_px r) { return r.u >= 0.0f && r.v == r.v; }
@@ -325,48 +364,28 @@ BH_LENS_HD Rgb shade_mip(const bh_lens_px* lens, uint32_t vw, uint32_t vh, uint3
     return shade_mip_rec(c, xn, yn, m, lut);
 }
 
-// sum_x, sum_y and shade_pixel over shade_mip: the same trees, the records addressed by their place in the
-// virtual frame, since a record's neighbour is the virtual grid's, not the output pixel's.
-template <int N, int K, bool BO>
-BH_LENS_HD Acc sum_x_mip(const bh_lens_px* lens, uint32_t vw, uint32_t vh, uint32_t vx, uint32_t vy, const MipView& m,
-                         const float* lut) {
-    if constexpr (N == 1) {
-        Acc a{shade_mip(lens, vw, vh, vx, vy, m, lut), {0.0f, 0.0f, 0.0f}};
-        if constexpr (BO) a.bo = blackout(a.col);
-        return a;
-    } else {
-        const Acc lo = sum_x_mip<N / 2, K, BO>(lens, vw, vh, vx, vy, m, lut);
-        const Acc hi = sum_x_mip<N / 2, K, BO>(lens, vw, vh, vx + N / 2, vy, m, lut);
-        const Acc r = add<BO>(lo, hi);
-#if defined(__HIP_DEVICE_COMPILE__)
-        // K = 4: two records, up to four bilinear samples, in flight at a time (what sum_x does at K = 8)
-        if constexpr (K == 4 && N == 2) __builtin_amdgcn_sched_barrier(0);
-#endif
-        return r;
+// The filtered shade's lens: the same records, each named by its place in the virtual frame (K * width x
+// K * height), since a record's neighbour is the virtual grid's, not the output pixel's.
+struct MipLens {
+    const bh_lens_px* lens;
+    uint32_t width, height;
+    MipView m;
+    const float* lut;
+    struct Cursor {
+        const MipLens& f;
+        uint32_t vw, vh, vx, vy;
+        BH_LENS_FI Rgb col() const { return shade_mip(f.lens, vw, vh, vx, vy, f.m, f.lut); }
+        BH_LENS_FI Cursor right(int n) const { return {f, vw, vh, vx + n, vy}; }
+        BH_LENS_FI Cursor down(int n) const { return {f, vw, vh, vx, vy + n}; }
+        // K = 4: two records, up to four bilinear samples, in flight at a time (what the plain tree does at K = 8)
+        template <int K>
+        static constexpr int barrier_at() { return K == 4 ? 2 : 0; }
+    };
+    template <int K, bool BO>
+    BH_LENS_FI Acc pixel(uint32_t x, uint32_t y) const {
+        return scaled<K, BO>(sum_y<K, K, BO>(Cursor{*this, width * K, height * K, x * K, y * K}));
     }
-}
-template <int N, int K, bool BO>
-BH_LENS_HD Acc sum_y_mip(const bh_lens_px* lens, uint32_t vw, uint32_t vh, uint32_t vx, uint32_t vy, const MipView& m,
-                         const float* lut) {
-    if constexpr (N == 1) {
-        return sum_x_mip<K, K, BO>(lens, vw, vh, vx, vy, m, lut);
-    } else {
-        const Acc lo = sum_y_mip<N / 2, K, BO>(lens, vw, vh, vx, vy, m, lut);
-        const Acc hi = sum_y_mip<N / 2, K, BO>(lens, vw, vh, vx, vy + N / 2, m, lut);
-        return add<BO>(lo, hi);
-    }
-}
-template <int K, bool BO>
-BH_LENS_HD Acc shade_pixel_mip(const bh_lens_px* lens, uint32_t width, uint32_t height, uint32_t x, uint32_t y,
-                               const MipView& m, const float* lut) {
-    Acc a = sum_y_mip<K, K, BO>(lens, width * K, height * K, x * K, y * K, m, lut);
-    if constexpr (K > 1) {
-        constexpr float scale = 1.0f / (float)(K * K);
-        a.col = {a.col.r * scale, a.col.g * scale, a.col.b * scale};
-        if constexpr (BO) a.bo = {a.bo.r * scale, a.bo.g * scale, a.bo.b * scale};
-    }
-    return a;
-}
+};
 
 }  // namespace lens
 }  // namespace bh

@@ -43,25 +43,14 @@ namespace BH_NS {
 // A launcher is a template, so a unit holds the kernels of the launchers it calls and no others; hidden, like
 // the entry points that call them.
 // f(SF) with the launch's scene flags as a compile-time constant where the build folds them: the reference's
-// scene always; no surfaces (BASELINE config 1: the sdf folds to +inf) with FOLD_NONE, which the exact builds
+// scene always (Const and with_format: bh_common.hpp); no surfaces (BASELINE config 1: the sdf folds to +inf) with FOLD_NONE, which the exact builds
 // set and the fast build does not; otherwise SF_DYN, the kernels that read the flags.
-template <uint32_t V>
-struct Const { static constexpr uint32_t value = V; };
 template <bool FOLD_NONE, class F>
 __attribute__((visibility("hidden"))) inline void with_scene_fold(uint32_t flags, F&& f) {
     if (flags == BH_SCENE_DEFAULT) return f(Const<BH_SCENE_DEFAULT>{});
     if constexpr (FOLD_NONE)
         if (flags == 0u) return f(Const<0u>{});
     f(Const<SF_DYN>{});
-}
-// f(FMT) with the launch's output format as a compile-time constant
-template <class F>
-__attribute__((visibility("hidden"))) inline int with_format(uint32_t format, F&& f) {
-    switch (format) {
-        case BH_OUT_RGBA32F: return f(Const<BH_OUT_RGBA32F>{});
-        case BH_OUT_RGBA16F: return f(Const<BH_OUT_RGBA16F>{});
-        default: return f(Const<BH_OUT_BGRA8_SRGB>{});
-    }
 }
 // The march over every tile under `schedule` (a bh_schedule without its flags); counters, grid: the persistent
 // schedule's.  Returns a hipError_t.

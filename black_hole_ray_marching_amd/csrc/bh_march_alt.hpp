@@ -38,7 +38,7 @@ template <uint32_t FMT>
 __global__ void __launch_bounds__(256) march_persistent_kernel(MarchArgs a, uint32_t* __restrict__ counters) {
     __shared__ float lut[lds_tables<FMT>()];
     __shared__ WaveQueues queues[4];
-    load_tables<FMT>(a, lut);
+    load_srgb_tables<FMT, 256u>(a, lut);
     __syncthreads();  // the only workgroup barrier: waves run independently afterwards
 
     const uint32_t lane = threadIdx.x & 63u;
@@ -148,7 +148,7 @@ __global__ void __launch_bounds__(256) march_persistent_kernel(MarchArgs a, uint
 template <uint32_t FMT>
 __global__ void __launch_bounds__(256) march_pair_kernel(MarchArgs a) {
     __shared__ float lut[lds_tables<FMT>()];
-    load_tables<FMT>(a, lut);
+    load_srgb_tables<FMT, 256u>(a, lut);
     __syncthreads();
     const uint32_t lane = threadIdx.x & 63u;
     const uint32_t pair = blockIdx.x * 4u + (threadIdx.x >> 6);

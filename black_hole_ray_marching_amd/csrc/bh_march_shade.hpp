@@ -1,7 +1,7 @@
 // bh_march_shade.hpp -- from a finished ray to its texel: the sky sample (texel_u32, decode, sample_sky), the sky
-// coordinates and colour of a ray (sky_uv, shade, lens_record), the workgroup's LDS tables (load_tables), the
-// output encoders (store_px, store_px_planar, store_rgbm14) and the pixel store (write_pixel, out_index).
-// Needs bh_march_ops.hpp and bh_srgb.hpp (the BGRA8 encoder).
+// coordinates and colour of a ray (sky_uv, shade, lens_record), the output encoders (store_px, store_px_planar,
+// store_rgbm14) and the pixel store (write_pixel, out_index).
+// Needs bh_march_ops.hpp and bh_srgb.hpp (the BGRA8 encoder, the row-major store, the workgroup's LDS tables).
 #pragma once
 #include <hip/hip_fp16.h>
 
@@ -107,39 +107,9 @@ __device__ __forceinline__ float2 lens_record(uint32_t fate, v3 rd) {
 }
 #endif
 
-// Output texel store; the format is a template parameter (one kernel instantiation per format keeps
-// the BGRA8 encoder out of the other formats' code: it measured 1.8 % on the RGBA16F kernel).
+// Output texel store of a row-major target (bh_srgb.hpp, store_rgb)
 template <uint32_t FMT>
-__device__ __forceinline__ void store_px(void* base, size_t idx, v3 c, const float* enc) {
-    if constexpr (FMT == BH_OUT_RGBA32F) {
-        reinterpret_cast<float4*>(base)[idx] = make_float4(c.x, c.y, c.z, 1.0f);
-    } else if constexpr (FMT == BH_OUT_RGBA16F) {
-        __half2 lo = __floats2half2_rn(c.x, c.y);
-        __half2 hi = __floats2half2_rn(c.z, 1.0f);
-        uint2 w;
-        w.x = *reinterpret_cast<uint32_t*>(&lo);
-        w.y = *reinterpret_cast<uint32_t*>(&hi);
-        reinterpret_cast<uint2*>(base)[idx] = w;
-    } else {
-        static_assert(FMT == BH_OUT_BGRA8_SRGB, "output format");
-        reinterpret_cast<uint32_t*>(base)[idx] = srgb_bgra8(c.x, c.y, c.z, enc);
-    }
-}
-
-// LDS tables of a workgroup: [0, 256) the sRGB decode of sky texels, then for BGRA8 output the
-// encoder's 257 thresholds.  NT = the workgroup's threads (a divisor or multiple of 256).
-template <uint32_t FMT>
-constexpr int lds_tables() { return FMT == BH_OUT_BGRA8_SRGB ? 256 + SRGB_TABLE : 256; }
-template <uint32_t FMT, uint32_t NT = 256>
-__device__ __forceinline__ void load_tables(const MarchArgs& a, float* tab) {
-#pragma unroll
-    for (uint32_t i = threadIdx.x; i < 256u; i += NT) {
-        tab[i] = a.srgb_lut[i];
-        if constexpr (FMT == BH_OUT_BGRA8_SRGB) tab[256 + i] = a.srgb_enc[i];
-    }
-    if constexpr (FMT == BH_OUT_BGRA8_SRGB)
-        if (threadIdx.x == 0) tab[256 + 256] = a.srgb_enc[256];
-}
+__device__ __forceinline__ void store_px(void* base, size_t idx, v3 c, const float* enc) { store_rgb<FMT>(base, idx, c.x, c.y, c.z, enc); }
 
 // BH_LAYOUT_TILES_RGB(M) store: pixel idx = tile * 64 + lane goes to three channel planes of its tile
 // (alpha, always 1, is dropped; the unpack restores it).  Each plane store of a wave is one

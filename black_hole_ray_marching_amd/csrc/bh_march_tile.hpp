@@ -194,7 +194,7 @@ __device__ __forceinline__ void march_tile_wave(const MarchArgs& A, const float*
 template <uint32_t FMT, uint32_t SF>
 __global__ void __launch_bounds__(64 * WG_WAVES) march_tile_kernel(MarchArgs A) {
     __shared__ float lut[lds_tables<FMT>()];
-    load_tables<FMT, 64u * WG_WAVES>(A, lut);
+    load_srgb_tables<FMT, 64u * WG_WAVES>(A, lut);
     __syncthreads();
     const uint32_t slot = __builtin_amdgcn_readfirstlane(blockIdx.x * WG_WAVES + (threadIdx.x >> 6));
     if (slot >= A.n_tiles * A.n_frames) return;  // wave-uniform
@@ -212,7 +212,7 @@ __global__ void __launch_bounds__(64 * WG_WAVES) march_tile_kernel(MarchArgs A) 
 template <uint32_t FMT, uint32_t SF>
 __global__ void __launch_bounds__(64 * WG_WAVES) march_tile_ss_kernel(MarchArgs A) {
     __shared__ float lut[lds_tables<FMT>()];
-    load_tables<FMT, 64u * WG_WAVES>(A, lut);
+    load_srgb_tables<FMT, 64u * WG_WAVES>(A, lut);
     __syncthreads();
     march_tile_wave<FMT, SF, true>(A, lut);
 }
@@ -237,6 +237,8 @@ template <uint32_t FMT, uint32_t SF>
 __global__ void __launch_bounds__(64u << shutter::MAX_LOG2) __attribute__((amdgpu_waves_per_eu(8)))
 march_tile_shutter_kernel(MarchArgs A, uint32_t ln) {
     float* lut = reinterpret_cast<float*>(shutter_hist_lds() + (1u << ln));
+    // the tables by a loop of its own: load_srgb_tables' stride is a compile-time constant, this workgroup's size
+    // is not, and its form of the loop gives these kernels other machine code than the one they were measured with
     const uint32_t nt = 64u << ln;
     for (uint32_t i = threadIdx.x; i < (uint32_t)lds_tables<FMT>(); i += nt)
         lut[i] = i < 256u ? A.srgb_lut[i] : A.srgb_enc[i - 256u];
@@ -300,7 +302,7 @@ __global__ void __launch_bounds__(64 * WG_WAVES) march_refine_kernel(MarchArgs A
         min(__hip_atomic_load(R.ctr + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT), R.capacity - n_front));
     const uint32_t total = (n_front + n_back) << (2u * lk);  // <= 0xFFFF0000 (bh_host.cpp)
     if (total == 0u) return;  // nothing refined (the same for every wave of the launch): no table, no pull
-    load_tables<FMT, 64u * WG_WAVES>(A, lut);
+    load_srgb_tables<FMT, 64u * WG_WAVES>(A, lut);
     __syncthreads();
     const uint32_t nh = R.n_heads ? R.n_heads : 1u;
     uint32_t q = (blockIdx.x * WG_WAVES + (threadIdx.x >> 6)) % nh, tried = 0u;

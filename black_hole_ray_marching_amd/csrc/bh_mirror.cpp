@@ -128,14 +128,13 @@ int bh_shutter_resolve_host(const float* samples, uint32_t n_frames, uint32_t n_
     return BH_OK;
 }
 
-// The shade kernel's per-pixel function (bh_lens.hpp, shade_pixel) in a loop over the output frame.
-extern "C++" template <int K>
-static void lens_shade_rows(const bh_lens_px* lens, uint32_t width, uint32_t height, const bh::lens::SkyView& s,
-                            const float* lut, float* out_col, float* out_bo) {
+// The shade kernels' per-pixel function (bh_lens.hpp, shade_pixel) in a loop over the output frame, for the
+// plain shade's lens or the filtered one's.
+extern "C++" template <int K, class L>
+static void lens_shade_rows(const L& lens, uint32_t width, uint32_t height, float* out_col, float* out_bo) {
     for (uint32_t y = 0; y < height; ++y)
         for (uint32_t x = 0; x < width; ++x) {
-            const bh::lens::Acc p = out_bo ? bh::lens::shade_pixel<K, true>(lens, width, x, y, s, lut)
-                                           : bh::lens::shade_pixel<K, false>(lens, width, x, y, s, lut);
+            const bh::lens::Acc p = out_bo ? bh::lens::shade_pixel<K, true>(lens, x, y) : bh::lens::shade_pixel<K, false>(lens, x, y);
             const bh::lens::Rgb col = p.col, bo = p.bo;
             const size_t o = ((size_t)y * width + x) * 4u;
             out_col[o] = col.r; out_col[o + 1] = col.g; out_col[o + 2] = col.b; out_col[o + 3] = 1.0f;
@@ -143,25 +142,37 @@ static void lens_shade_rows(const bh_lens_px* lens, uint32_t width, uint32_t hei
         }
 }
 
+// A sky as the device holds it: the decode table, and the packed little-endian words the kernels read (the
+// caller's bytes may be unaligned).  False: out of memory.
+struct HostSky {
+    float lut[256];
+    std::vector<uint32_t> texels;
+    bh::lens::SkyView view;
+};
+static bool host_sky(const uint8_t* sky, uint32_t sky_w, uint32_t sky_h, HostSky* k) {
+    srgb_lut(k->lut);
+    try {
+        k->texels.resize((size_t)sky_w * sky_h);
+    } catch (const std::bad_alloc&) {
+        return false;
+    }
+    std::memcpy(k->texels.data(), sky, k->texels.size() * 4u);
+    k->view = {k->texels.data(), sky_w, sky_h};
+    return true;
+}
+
 int bh_lens_shade_host(const bh_lens_px* lens, uint32_t width, uint32_t height, uint32_t ss, const uint8_t* sky,
                        uint32_t sky_w, uint32_t sky_h, float* out_col, float* out_bo) {
     if (!lens || !sky || !out_col || bh::ss::log2_k(ss) > 3u || !frame_shape_ok(width, height, ss)) return bad_arg(__func__, __LINE__);
     if (sky_w == 0 || sky_h == 0 || sky_w > 32768u || sky_h > 32768u) return bad_arg(__func__, __LINE__);
-    float lut[256];
-    srgb_lut(lut);
-    std::vector<uint32_t> texels;  // the packed little-endian words the device reads (the bytes may be unaligned)
-    try {
-        texels.resize((size_t)sky_w * sky_h);
-    } catch (const std::bad_alloc&) {
-        return BH_ERR_OUT_OF_MEMORY;
-    }
-    std::memcpy(texels.data(), sky, texels.size() * 4u);
-    const bh::lens::SkyView s{texels.data(), sky_w, sky_h};
+    HostSky k;
+    if (!host_sky(sky, sky_w, sky_h, &k)) return BH_ERR_OUT_OF_MEMORY;
+    const bh::lens::PlainLens l{lens, width, k.view, k.lut};
     switch (ss) {
-        case 1u: lens_shade_rows<1>(lens, width, height, s, lut, out_col, out_bo); break;
-        case 2u: lens_shade_rows<2>(lens, width, height, s, lut, out_col, out_bo); break;
-        case 4u: lens_shade_rows<4>(lens, width, height, s, lut, out_col, out_bo); break;
-        default: lens_shade_rows<8>(lens, width, height, s, lut, out_col, out_bo); break;
+        case 1u: lens_shade_rows<1>(l, width, height, out_col, out_bo); break;
+        case 2u: lens_shade_rows<2>(l, width, height, out_col, out_bo); break;
+        case 4u: lens_shade_rows<4>(l, width, height, out_col, out_bo); break;
+        default: lens_shade_rows<8>(l, width, height, out_col, out_bo); break;
     }
     return BH_OK;
 }
@@ -182,38 +193,20 @@ static void build_chain(const bh::lens::SkyView& s, const float* lut, uint32_t u
 int bh_sky_mips_host(const uint8_t* sky, uint32_t sky_w, uint32_t sky_h, uint32_t level, uint16_t* out_halves) {
     if (!sky || !out_halves || sky_w == 0 || sky_h == 0 || sky_w > 32768u || sky_h > 32768u) return bad_arg(__func__, __LINE__);
     if (level < 1u || level >= bh::lens::mip_levels(sky_w, sky_h)) return bad_arg(__func__, __LINE__);
-    float lut[256];
-    srgb_lut(lut);
     uint32_t off[bh::lens::MIP_MAX_LEVELS];
     bh::lens::mip_offsets(sky_w, sky_h, off);
     const size_t n_out = (size_t)bh::lens::mip_side(sky_w, level) * bh::lens::mip_side(sky_h, level);
-    std::vector<uint32_t> texels;
+    HostSky k;
     std::vector<bh::lens::Half4> chain;
     try {
-        texels.resize((size_t)sky_w * sky_h);
         chain.resize(off[level] + n_out);
     } catch (const std::bad_alloc&) {
         return BH_ERR_OUT_OF_MEMORY;
     }
-    std::memcpy(texels.data(), sky, texels.size() * 4u);
-    build_chain({texels.data(), sky_w, sky_h}, lut, level, off, chain.data());
+    if (!host_sky(sky, sky_w, sky_h, &k)) return BH_ERR_OUT_OF_MEMORY;
+    build_chain(k.view, k.lut, level, off, chain.data());
     std::memcpy(out_halves, chain.data() + off[level], n_out * sizeof(bh::lens::Half4));
     return BH_OK;
-}
-
-// The filtered shade kernel's per-pixel function (bh_lens.hpp, shade_pixel_mip) in a loop over the output frame.
-extern "C++" template <int K>
-static void lens_shade_mip_rows(const bh_lens_px* lens, uint32_t width, uint32_t height, const bh::lens::MipView& m,
-                                const float* lut, float* out_col, float* out_bo) {
-    for (uint32_t y = 0; y < height; ++y)
-        for (uint32_t x = 0; x < width; ++x) {
-            const bh::lens::Acc p = out_bo ? bh::lens::shade_pixel_mip<K, true>(lens, width, height, x, y, m, lut)
-                                           : bh::lens::shade_pixel_mip<K, false>(lens, width, height, x, y, m, lut);
-            const bh::lens::Rgb col = p.col, bo = p.bo;
-            const size_t o = ((size_t)y * width + x) * 4u;
-            out_col[o] = col.r; out_col[o + 1] = col.g; out_col[o + 2] = col.b; out_col[o + 3] = 1.0f;
-            if (out_bo) { out_bo[o] = bo.r; out_bo[o + 1] = bo.g; out_bo[o + 2] = bo.b; out_bo[o + 3] = 1.0f; }
-        }
 }
 
 int bh_lens_shade_mip_host(const bh_lens_px* lens, uint32_t width, uint32_t height, uint32_t ss, const uint8_t* sky,
@@ -224,27 +217,23 @@ int bh_lens_shade_mip_host(const bh_lens_px* lens, uint32_t width, uint32_t heig
         bh_set_last_error("bh_lens_shade_mip_host: ss = 8 is not built (bh_shade_lens_mip).");
         return BH_ERR_UNSUPPORTED;
     }
-    float lut[256];
-    srgb_lut(lut);
     uint32_t off[bh::lens::MIP_MAX_LEVELS];
     const size_t n_chain = bh::lens::mip_offsets(sky_w, sky_h, off);
     const uint32_t n_levels = bh::lens::mip_levels(sky_w, sky_h);
-    std::vector<uint32_t> texels;
+    HostSky k;
     std::vector<bh::lens::Half4> chain;
     try {
-        texels.resize((size_t)sky_w * sky_h);
         chain.resize(n_chain);
     } catch (const std::bad_alloc&) {
         return BH_ERR_OUT_OF_MEMORY;
     }
-    std::memcpy(texels.data(), sky, texels.size() * 4u);
-    const bh::lens::SkyView s{texels.data(), sky_w, sky_h};
-    build_chain(s, lut, n_levels - 1u, off, chain.data());
-    const bh::lens::MipView m{s, chain.data(), off, n_levels};
+    if (!host_sky(sky, sky_w, sky_h, &k)) return BH_ERR_OUT_OF_MEMORY;
+    build_chain(k.view, k.lut, n_levels - 1u, off, chain.data());
+    const bh::lens::MipLens l{lens, width, height, {k.view, chain.data(), off, n_levels}, k.lut};
     switch (ss) {
-        case 1u: lens_shade_mip_rows<1>(lens, width, height, m, lut, out_col, out_bo); break;
-        case 2u: lens_shade_mip_rows<2>(lens, width, height, m, lut, out_col, out_bo); break;
-        default: lens_shade_mip_rows<4>(lens, width, height, m, lut, out_col, out_bo); break;
+        case 1u: lens_shade_rows<1>(l, width, height, out_col, out_bo); break;
+        case 2u: lens_shade_rows<2>(l, width, height, out_col, out_bo); break;
+        default: lens_shade_rows<4>(l, width, height, out_col, out_bo); break;
     }
     return BH_OK;
 }

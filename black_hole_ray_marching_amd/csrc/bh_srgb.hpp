@@ -8,8 +8,11 @@
 // the answer, and the two neighbouring thresholds fix it: exact for every float (checked
 // exhaustively on the device, bh_selftest_crmath op 4).
 #pragma once
+#include <hip/hip_fp16.h>
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+
+#include "../../include/bh_render.h"
 
 namespace bh {
 
@@ -62,6 +65,48 @@ __device__ __forceinline__ uint32_t srgb_encode_code(float x, const uint32_t* E)
 // BGRA8 texel (byte 0 = B) of linear rgb, alpha 1.
 __device__ __forceinline__ uint32_t srgb_bgra8(float r, float g, float b, const float* T) {
     return srgb_encode(b, T) | (srgb_encode(g, T) << 8) | (srgb_encode(r, T) << 16) | 0xFF000000u;
+}
+
+// Output texel store of every row-major target (the march's, the lens shades'); the format is a template
+// parameter (one kernel instantiation per format keeps the BGRA8 encoder out of the other formats' code: it
+// measured 1.8 % on the RGBA16F march kernel).  Vector stores only.
+template <uint32_t FMT>
+__device__ __forceinline__ void store_rgb(void* base, size_t idx, float r, float g, float b, const float* enc) {
+    if constexpr (FMT == BH_OUT_RGBA32F) {
+        reinterpret_cast<float4*>(base)[idx] = make_float4(r, g, b, 1.0f);
+    } else if constexpr (FMT == BH_OUT_RGBA16F) {
+        __half2 lo = __floats2half2_rn(r, g);
+        __half2 hi = __floats2half2_rn(b, 1.0f);
+        uint2 w;
+        w.x = *reinterpret_cast<uint32_t*>(&lo);
+        w.y = *reinterpret_cast<uint32_t*>(&hi);
+        reinterpret_cast<uint2*>(base)[idx] = w;
+    } else {
+        static_assert(FMT == BH_OUT_BGRA8_SRGB, "output format");
+        reinterpret_cast<uint32_t*>(base)[idx] = srgb_bgra8(r, g, b, enc);
+    }
+}
+
+// LDS tables of a workgroup of NT threads (a divisor or multiple of 256): tab[0, 256) the sRGB decode of sky
+// texels, then for BGRA8 output the encoder's 257 thresholds (not read otherwise).  The caller's barrier follows.
+// `a` is a launch's arguments, or any struct with their two table pointers srgb_lut and srgb_enc.  (The march
+// kernels call this directly, with their MarchArgs: called through a wrapper of their own, the pair and
+// persistent kernels came out with the pointer's load one instruction earlier or later than measured.)
+struct SrgbTables { const float* srgb_lut; const float* srgb_enc; };
+template <uint32_t FMT>
+constexpr int lds_tables() { return FMT == BH_OUT_BGRA8_SRGB ? 256 + SRGB_TABLE : 256; }
+// ONE_EACH: the workgroup is exactly 256 threads, one entry of each table per thread, no loop and no guard (the lens
+// kernels: at ss 1 the guarded loop, which waits for its load inside the guard, measured 1 to 3 % of the launch).
+template <uint32_t FMT, uint32_t NT, bool ONE_EACH = false, class Args>
+__device__ __forceinline__ void load_srgb_tables(const Args& a, float* tab) {
+    static_assert(!ONE_EACH || NT == 256u, "one entry per thread");
+#pragma unroll
+    for (uint32_t i = threadIdx.x; ONE_EACH ? i == threadIdx.x : i < 256u; i += NT) {
+        tab[i] = a.srgb_lut[i];
+        if constexpr (FMT == BH_OUT_BGRA8_SRGB) tab[256 + i] = a.srgb_enc[i];
+    }
+    if constexpr (FMT == BH_OUT_BGRA8_SRGB)
+        if (threadIdx.x == 0) tab[256 + 256] = a.srgb_enc[256];
 }
 
 }  // namespace bh

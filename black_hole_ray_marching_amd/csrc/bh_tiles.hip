@@ -248,12 +248,10 @@ extern "C" __attribute__((visibility("hidden"))) int bh_launch_refine_detect(con
     const uint64_t waves = (uint64_t)r.tiles_x * r.tiles_y * r.n_frames;
     if (waves == 0 || waves > 0xFFFF0000ull) return (int)hipErrorInvalidValue;
     const dim3 grid((uint32_t)((waves + bh::DETECT_WAVES - 1u) / bh::DETECT_WAVES)), block(64u * bh::DETECT_WAVES);
-    switch (a.format) {
-        case BH_OUT_RGBA32F: hipLaunchKernelGGL(bh::refine_detect_kernel<BH_OUT_RGBA32F>, grid, block, 0, s, a, r); break;
-        case BH_OUT_RGBA16F: hipLaunchKernelGGL(bh::refine_detect_kernel<BH_OUT_RGBA16F>, grid, block, 0, s, a, r); break;
-        default: hipLaunchKernelGGL(bh::refine_detect_kernel<BH_OUT_BGRA8_SRGB>, grid, block, 0, s, a, r); break;
-    }
-    return (int)hipGetLastError();
+    return bh::with_format(a.format, [&](auto fmt) {
+        hipLaunchKernelGGL(bh::refine_detect_kernel<decltype(fmt)::value>, grid, block, 0, s, a, r);
+        return (int)hipGetLastError();
+    });
 }
 
 extern "C" __attribute__((visibility("hidden"))) int bh_launch_build_order(const uint8_t* cost, uint32_t n,

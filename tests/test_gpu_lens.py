@@ -159,8 +159,8 @@ def test_shade_ss(torch_cuda, scene, cam, W, H, k):
         col, bo = shade(torch, scene, lens, W, H, fmt, "96x40", ss=k)
         assert_frame(col, expected_bytes(fmt, wc), f"fmt {fmt} col")
         assert_frame(bo, expected_bytes(fmt, wb), f"fmt {fmt} blackout_col")
-    col, bo = shade(torch, scene, lens, W, H, F32, "96x40", blackout=False, ss=k)
-    assert_frame(col, expected_bytes(F32, wc), "col alone")
+        col, bo = shade(torch, scene, lens, W, H, fmt, "96x40", blackout=False, ss=k)  # the kernels' other arm
+        assert_frame(col, expected_bytes(fmt, wc), f"fmt {fmt} col alone")
     wc, wb = frame(cam, W, H, "ctx", k)
     col, bo = shade(torch, scene, lens, W, H, F32, ss=k)
     assert_frame(col, expected_bytes(F32, wc), "scene sky col")

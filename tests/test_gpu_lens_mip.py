@@ -180,7 +180,7 @@ def test_end_to_end_ss(torch_cuda, scene, cam):
     end_to_end(torch_cuda, scene, cam, 13, 7, 2)
 
 
-@pytest.mark.parametrize("k", [1, 2])
+@pytest.mark.parametrize("k", [1, 2, 4])
 @pytest.mark.parametrize("fmt", [bh.BH_OUT_RGBA16F, bh.BH_OUT_BGRA8_SRGB])
 def test_formats_and_col_alone(torch_cuda, scene, fmt, k):
     torch = torch_cuda

@@ -5,7 +5,8 @@ machine code byte for byte as it was (tools/text_hash.sh hashes the whole .text,
 changes).
     python tools/kernel_text_cmp.py OLD_BUILD_DIR NEW_BUILD_DIR [--match march_]
 Prints one line per kernel of the old build: same / DIFFERENT / MISSING, then the kernels only the new build
-has; exit status 1 if any kernel differs or is missing."""
+has; a function of a unit that the new build no longer has is matched by name in its other units ("moved to");
+exit status 1 if any kernel differs or is missing."""
 import argparse
 import hashlib
 import subprocess
@@ -52,16 +53,22 @@ with tempfile.TemporaryDirectory() as t:
     to, tn = Path(t) / "old", Path(t) / "new"
     to.mkdir()
     tn.mkdir()
-    for unit in sorted({f.name for d in (args.old, args.new) for f in Path(d).glob("*.o")}):  # a new unit has new kernels only
-        o, n = Path(args.old) / unit, Path(args.new) / unit
-        ko, kn = kernels(o, to) if o.exists() else {}, kernels(n, tn) if n.exists() else {}
-        for name, h in sorted(ko.items()):
+    units = sorted({f.name for d in (args.old, args.new) for f in Path(d).glob("*.o")})  # a new unit has new kernels only
+    old = {u: kernels(Path(args.old) / u, to) if (Path(args.old) / u).exists() else {} for u in units}
+    new = {u: kernels(Path(args.new) / u, tn) if (Path(args.new) / u).exists() else {} for u in units}
+    # a unit the new build no longer has: its functions are looked up by name in the new build's other units
+    gone = [u for u in units if not (Path(args.new) / u).exists()]
+    moved = {name: u for u in units for name in new[u] if any(name in old[g] for g in gone) and name not in old[u]}
+    for unit in units:
+        stem = Path(unit).stem
+        for name, h in sorted(old[unit].items()):
             if args.match not in name:
                 continue
-            state = "MISSING" if name not in kn else "same" if kn[name] == h else "DIFFERENT"
+            at = moved[name] if unit in gone and name in moved else unit
+            state = "MISSING" if name not in new[at] else "same" if new[at][name] == h else "DIFFERENT"
             bad += state != "same"
-            print(f"{state:9} {o.stem:20} {h} {name}")
-        for name in sorted(set(kn) - set(ko)):
+            print(f"{state:9} {stem:20} {h} {name}" + (f"  (moved to {Path(at).stem})" if at != unit else ""))
+        for name in sorted(set(new[unit]) - set(old[unit]) - set(moved)):
             if args.match in name:
-                print(f"{'new':9} {o.stem:20} {kn[name]} {name}")
+                print(f"{'new':9} {stem:20} {new[unit][name]} {name}")
 sys.exit(1 if bad else 0)
