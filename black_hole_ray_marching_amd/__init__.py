@@ -12,5 +12,6 @@ from ._abi import (BH_BLOOM_AUTO, BH_BLOOM_LITERAL, BH_FATE_BLACKOUT, BH_FATE_CA
 from .scene import (MAX_ITERATIONS, Camera, CameraController, CameraUniform, FrameBatch, Partition, Presenter, Scene, Sky, Uniforms, bloom_check, bloom_plan_failures, clock_mhz, lens_shade_host, load_sky, sky_mips_host,
                     partition_map, refine_cover_host, refine_mask_host, shard_tile_count, shutter_resolve_host, srgb_encode_table, ss_resolve_host, tiles_unpack_rgbm_partition,
                     synthetic_sky, tile_bytes, tiles_unpack, tiles_unpack_rgb, tiles_unpack_rgbm)
+from . import raymap
 
 __version__ = "0.5.0"

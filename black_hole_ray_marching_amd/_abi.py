@@ -143,6 +143,11 @@ SIGNATURES = {
     "bh_sky_mips_host": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p]),
     "bh_lens_shade_mip_host": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint32,
                                          C.c_uint32, C.c_void_p, C.c_void_p]),
+    "bh_render_rays": (C.c_int, [C.c_void_p, C.POINTER(C.c_float), C.POINTER(bh_uniforms), C.POINTER(bh_render_desc),
+                                 C.c_void_p, C.c_uint32, C.c_void_p]),
+    "bh_render_lens_rays": (C.c_int, [C.c_void_p, C.POINTER(C.c_float), C.POINTER(bh_uniforms),
+                                      C.POINTER(bh_render_desc), C.c_void_p, C.c_void_p, C.c_void_p]),
+    "bh_ray_map_pinhole_host": (C.c_int, [C.POINTER(bh_camera_uniform), C.c_uint32, C.c_uint32, C.c_void_p]),
     "bh_shard_tile_count": (C.c_int64, [C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32]),
     "bh_tiles_unpack": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32,
                                   C.c_uint64, C.c_uint32, C.c_void_p]),

@@ -189,6 +189,31 @@ int bh_camera_uniform_update(const bh_camera* cam, bh_camera_uniform* out) {
     return BH_OK;
 }
 
+// The ray map of bh_render's own projection: pixel_ray's interpolated vector d (bh_march_step.hpp) before its
+// normalisation, by the same fp32 operations in the same order -- the IEEE divisions by 2W and 2H (what the kernel's
+// division core returns), l1 = (1 - l0) - l2, (l0 c0 + l1 c1) + l2 c2.  This unit is built without contraction.
+int bh_ray_map_pinhole_host(const bh_camera_uniform* cam, uint32_t width, uint32_t height, float* out) {
+    if (!cam || !out || width == 0 || height == 0 || width > 65536u || height > 65536u) return bad_arg(__func__, __LINE__);
+    static const float st[3][2] = {{3.0f, 1.0f}, {-1.0f, 1.0f}, {-1.0f, -3.0f}};
+    for (int i = 0; i < 3; ++i)
+        if (cam->screen_tri[i][0] != st[i][0] || cam->screen_tri[i][1] != st[i][1]) {
+            bh_set_last_error("bh_ray_map_pinhole_host: non-default screen triangle");
+            return BH_ERR_UNSUPPORTED;
+        }
+    const float w2 = 2.0f * (float)width, h2 = 2.0f * (float)height;
+    for (uint32_t y = 0; y < height; ++y) {
+        const float l2 = ((float)y + 0.5f) / h2;
+        for (uint32_t x = 0; x < width; ++x) {
+            const float l0 = ((float)x + 0.5f) / w2;
+            const float l1 = (1.0f - l0) - l2;
+            float* d = out + ((size_t)y * width + x) * 3u;
+            for (int k = 0; k < 3; ++k)
+                d[k] = (l0 * cam->world_tri[0][k] + l1 * cam->world_tri[1][k]) + l2 * cam->world_tri[2][k];
+        }
+    }
+    return BH_OK;
+}
+
 static void sky_rows(uint8_t* out, uint32_t w, uint32_t h, uint64_t seed, uint32_t y0, uint32_t y1) {
     const int base = 6;  // nebula lattice cells around the equator at octave 0
     for (uint32_t y = y0; y < y1; ++y) {

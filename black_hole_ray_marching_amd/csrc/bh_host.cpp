@@ -341,10 +341,10 @@ static int stage_frame_table(bh_ctx* c, hipStream_t s, const bh::FrameArgs* fram
 // the ctx keeps more than BH_ORDER_STATES instead of evicting one.  A capturing stream cannot create a
 // state (the allocation and the reset are not capturable work): BH_ERR_UNSUPPORTED.
 static int order_state(bh_ctx* c, const bh_render_desc* d, uint64_t nt, hipStream_t s, bool capturing,
-                       bh_ctx::OrderState** out) {
+                       bh_ctx::OrderState** out, bool from_map = false) {
     const uint64_t pser = d->partition ? d->partition->serial : 0u;
     for (auto& o : c->orders)
-        if (o.matches(d, pser, nt, s)) {
+        if (o.matches(d, pser, nt, s, from_map)) {
             o.last_use = ++c->order_clock;
             if (capturing) {
                 if (!o.valid) {
@@ -366,6 +366,7 @@ static int order_state(bh_ctx* c, const bh_render_desc* d, uint64_t nt, hipStrea
     n.partition = pser;
     n.n_tiles = nt;
     n.stream = (void*)s;
+    n.ray_map = from_map;
     const size_t cw = bh::ORDER_WORDS * sizeof(uint32_t);
     hipError_t he;
     if ((he = hipMalloc(&n.tile_cost, nt)) != hipSuccess || (he = hipMalloc(&n.order, nt * sizeof(uint32_t))) != hipSuccess ||
@@ -409,8 +410,10 @@ static void frame_args(const bh_camera_uniform* cam, float rs, const bh_render_d
 
 // What a frame's per-tile costs (the march's step counts) depend on: the camera, the shader uniforms and the
 // launch shape -- FNV-1a over those fields' bits (padding and the unused bg_brightness left out).  The
-// outputs, their format and the sky do not change a step count.
-static uint64_t frame_cost_key(const bh_camera_uniform* cam, const bh_uniforms* U, const bh_render_desc* d) {
+// outputs, their format and the sky do not change a step count.  A ray-map launch's rays are its map's: the map's
+// address enters the key (its contents cannot: a map rewritten in place may meet a stale order, never other bytes).
+static uint64_t frame_cost_key(const bh_camera_uniform* cam, const bh_uniforms* U, const bh_render_desc* d,
+                               const float* ray_map = nullptr) {
     uint64_t h = 1469598103934665603ull;
     auto mix = [&](const void* p, size_t n) {
         const unsigned char* b = static_cast<const unsigned char*>(p);
@@ -426,6 +429,7 @@ static uint64_t frame_cost_key(const bh_camera_uniform* cam, const bh_uniforms* 
                            d->shard_count, d->schedule};
     mix(f, sizeof f);
     mix(&pser, sizeof pser);
+    if (ray_map) mix(&ray_map, sizeof ray_map);
     return h | 1u;  // never 0: 0 marks the fresh state's all-zero costs
 }
 
@@ -496,6 +500,7 @@ struct Launch {
     std::vector<bh::FrameArgs> table;  // more than BH_INLINE_FRAMES frames: staged in the stream's device table
     uint64_t n_tiles = 0;              // the shard's tiles
     uint32_t shutter_log2 = 0;         // bh_render_shutter: log2 of the cameras per output frame (a.n_frames counts cameras)
+    const float* ray_map = nullptr;    // bh_render_rays, bh_render_lens_rays: the device map the rays come from
 };
 
 // Every argument check of a launch; no HIP call.  Leaves the launch's desc and tile count in L.
@@ -603,7 +608,7 @@ static int learned_order(bh_ctx* c, Launch* L, const bh_camera_uniform* cam0, co
     if ((d->schedule & 0xFFu) != BH_SCHED_TILE || (d->schedule & BH_SCHED_FLAG_STATIC_ORDER)) return BH_OK;
     // temporal order of this (geometry, shard, stream): allocated at its first render only
     bh_ctx::OrderState* os = nullptr;
-    int st = order_state(c, d, L->n_tiles, s, stream_capturing(s), &os);
+    int st = order_state(c, d, L->n_tiles, s, stream_capturing(s), &os, L->ray_map != nullptr);
     if (st != BH_OK) return st;
     if (!os->valid) {
         // all costs 0 (one bucket, the uncounted last) and an empty histogram: consistent
@@ -623,7 +628,7 @@ static int learned_order(bh_ctx* c, Launch* L, const bh_camera_uniform* cam0, co
     // buffers behind them costs at most a stale order, never a disagreement.  BH_ORDER_ALWAYS (A/B):
     // build and write on every launch, as before round 5.
     static const bool always = std::getenv("BH_ORDER_ALWAYS") != nullptr;
-    const uint64_t key = frame_cost_key(cam0, U, d);
+    const uint64_t key = frame_cost_key(cam0, U, d, L->ray_map);
     const bool repeat = !always && os->order_key == os->cost_key && os->cost_key == key;
     if (!repeat) {
         int oe = bh_launch_build_order(os->tile_cost, a.n_tiles, a.order_block, a.order_centre, os->counters,
@@ -646,7 +651,9 @@ static int launch_march(bh_ctx* c, const Launch& L, bh_ctx::OrderState* os, hipS
     const uint32_t sched = d->schedule & 0xFFu;
     const bool issue = march_variant_issue_order(d, a.n_tiles, a.n_frames, c->cus);  // every camera's tiles
     int e;
-    if (const uint32_t ln = L.shutter_log2)
+    if (L.ray_map)  // exact math, tile schedule (render_rays)
+        e = issue ? bh_launch_rays_exact(a, L.ray_map, s) : bh_launch_rays_exact_lat(a, L.ray_map, s);
+    else if (const uint32_t ln = L.shutter_log2)
         e = d->math != BH_MATH_EXACT ? bh_launch_shutter_fast(a, ln, s)
             : issue                  ? bh_launch_shutter_exact(a, ln, s)
                                      : bh_launch_shutter_exact_lat(a, ln, s);
@@ -804,6 +811,57 @@ int bh_render_lens(bh_ctx* c, const bh_camera_uniform* cam, const bh_uniforms* U
     fill_args(c, 1u, cam, U, &ld, 1u, &L);
     L.a.lens = 1u;
     return march_in_order(c, &L, cam, U, stream);
+}
+
+// ---- ray maps (include/bh_render.h): the caller's direction per pixel, one origin per frame -----------------
+// bh_render_rays (out_lens null) and bh_render_lens_rays: the launch of bh_render / bh_render_ss / bh_render_lens of
+// this geometry from a camera that holds only the position -- the corner rays are not read by the ray-map kernels
+// -- with an order state and a repeated-frame key of its own (Launch::ray_map).
+static int render_rays(const char* fn, bh_ctx* c, const float* pos, const bh_uniforms* U, const bh_render_desc* d,
+                       const float* dirs, uint32_t ss, bh_lens_px* out_lens, void* stream) {
+    if (!c || !pos || !U || !d || !dirs || (reinterpret_cast<uintptr_t>(dirs) & 3u)) return bad_arg(fn, __LINE__);
+    if (bh::ss::log2_k(ss) > 3u) return bad_arg(fn, __LINE__);
+    if (!frame_shape_ok(d->width, d->height, ss)) return bad_arg(fn, __LINE__);
+    bh_render_desc one = *d;
+    if (ss == 1u) one.dbg_n_rk = nullptr, one.dbg_fate = nullptr, one.dbg_steps = nullptr;  // per ray: as bh_render
+    const char* why = d->math == BH_MATH_FAST ? "exact math (BH_MATH_EXACT): a ray map has no fast-math kernels"
+                      : out_lens && (d->out_col || d->out_blackout) ? "no out_col or out_blackout (it writes only the lens)"
+                                                                   : ss_needs(out_lens ? d : &one, 1u);
+    if (why) {
+        g_last_error = std::string(fn) + ": a ray-map render needs " + why + ".";
+        return BH_ERR_UNSUPPORTED;
+    }
+    bh_camera_uniform cam;
+    std::memset(&cam, 0, sizeof cam);
+    static const float st[3][2] = {{3.0f, 1.0f}, {-1.0f, 1.0f}, {-1.0f, -3.0f}};
+    for (int i = 0; i < 3; ++i) {
+        cam.pos[i] = pos[i];
+        cam.screen_tri[i][0] = st[i][0];
+        cam.screen_tri[i][1] = st[i][1];
+    }
+    bh_render_desc ld = *d;
+    if (out_lens) {  // as bh_render_lens: the lens in place of target 0, the format word not read
+        ld.format = BH_OUT_RGBA32F;
+        ld.out_col = out_lens;
+    }
+    Launch L;
+    const int e = check_launch(c, 1u, &cam, U, &ld, ss, &L);
+    if (e != BH_OK) return e;
+    fill_args(c, 1u, &cam, U, &ld, ss, &L);
+    L.a.lens = out_lens ? 1u : 0u;
+    L.ray_map = dirs;
+    return march_in_order(c, &L, &cam, U, stream);
+}
+
+int bh_render_rays(bh_ctx* c, const float pos[3], const bh_uniforms* U, const bh_render_desc* d, const float* dirs_dev,
+                   uint32_t ss, void* stream) {
+    return render_rays(__func__, c, pos, U, d, dirs_dev, ss, nullptr, stream);
+}
+
+int bh_render_lens_rays(bh_ctx* c, const float pos[3], const bh_uniforms* U, const bh_render_desc* d,
+                        const float* dirs_dev, bh_lens_px* out_lens, void* stream) {
+    if (!out_lens || (reinterpret_cast<uintptr_t>(out_lens) & 7u)) return bad_arg(__func__, __LINE__);
+    return render_rays(__func__, c, pos, U, d, dirs_dev, 1u, out_lens, stream);
 }
 
 // bh_sky_create and bh_sky_create_mips: the texels, and with `mips` the chain built from them (a synchronous call)

@@ -37,6 +37,7 @@ struct bh_ctx {
         uint64_t partition = 0;              // bh_partition::serial, 0 = none
         uint64_t n_tiles = 0;                // the buffers' size in tiles
         void* stream = nullptr;
+        bool ray_map = false;                // a ray-map launch's state (bh_render_rays): its tile costs are its own
         uint64_t last_use = 0;
         bool valid = false;                  // costs and histogram agree (false: start afresh)
         bool captured = false;               // used by a launch captured into a graph: never evicted
@@ -56,10 +57,13 @@ struct bh_ctx {
         uint32_t* refine_ctr = nullptr;
         uint8_t* refine_mask = nullptr;
         uint32_t refine_frames = 0;
-        // the state's key: the frame geometry and shard of `d`, a partition's serial (0: none), the tile count, the stream
-        bool matches(const bh_render_desc* d, uint64_t partition_serial, uint64_t tiles, const void* on_stream) const {
+        // the state's key: the frame geometry and shard of `d`, a partition's serial (0: none), the tile count, the
+        // stream, and whether the rays come from a map
+        bool matches(const bh_render_desc* d, uint64_t partition_serial, uint64_t tiles, const void* on_stream,
+                     bool from_map = false) const {
             return width == d->width && height == d->height && shard_index == d->shard_index &&
-                   shard_count == d->shard_count && partition == partition_serial && n_tiles == tiles && stream == on_stream;
+                   shard_count == d->shard_count && partition == partition_serial && n_tiles == tiles &&
+                   stream == on_stream && ray_map == from_map;
         }
         void free_buffers() {
             (void)hipFree(tile_cost); (void)hipFree(order); (void)hipFree(counters);
@@ -196,6 +200,9 @@ BH_INTERNAL int bh_launch_march_exact_lat(const bh::MarchArgs& a, uint32_t sched
                 hipStream_t s);
 BH_INTERNAL int bh_launch_march_fast(const bh::MarchArgs& a, uint32_t schedule, uint32_t* counters, uint32_t grid,
                 hipStream_t s);
+// the ray-map march (bh_march_rays.hip): one frame, tile schedule; a.lens / a.ss_log2 pick the form
+BH_INTERNAL int bh_launch_rays_exact(const bh::MarchArgs& a, const float* dirs, hipStream_t s);
+BH_INTERNAL int bh_launch_rays_exact_lat(const bh::MarchArgs& a, const float* dirs, hipStream_t s);
 // the shutter render's march: 2^ln cameras per output frame, a.n_frames cameras in all (ln in 1..4)
 BH_INTERNAL int bh_launch_shutter_exact(const bh::MarchArgs& a, uint32_t ln, hipStream_t s);
 BH_INTERNAL int bh_launch_shutter_exact_lat(const bh::MarchArgs& a, uint32_t ln, hipStream_t s);

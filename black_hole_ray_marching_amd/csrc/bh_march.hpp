@@ -3,7 +3,8 @@
 // Included by two source files, each after defining BH_FAST and BH_NS:
 //   bh_march_exact.hip  (BH_FAST 0; built -ffp-contract=off, correctly-rounded f32 div/sqrt):
 //       same op sequence as the normative arithmetic of oracle/bh_oracle.c -> bit-exact parity
-//       (bh_march_exact_lat.hip and bh_march_refine_lat.hip build the same file again);
+//       (bh_march_exact_lat.hip and bh_march_refine_lat.hip build the same file again; bh_march_rays.hip and
+//       bh_march_rays_lat.hip hold the ray-map kernels alone, with the same two sets of flags);
 //   bh_march_fast.hip   (BH_FAST 1; built -ffp-contract=fast, hardware rcp/rsq/sqrt):
 //       algebraically identical reformulation for throughput -> tolerance parity.
 //
@@ -80,6 +81,28 @@ __attribute__((visibility("hidden"))) inline int launch_march(const MarchArgs& a
         return (int)hipGetLastError();
     });
 }
+#if !BH_FAST
+// The ray-map march (bh_render_rays, bh_render_lens_rays; tile schedule, one frame): the lens, supersampled or plain
+// form by the same fields as launch_march, with the same folds.
+template <bool FOLD_NONE>
+__attribute__((visibility("hidden"))) inline int launch_rays(const MarchArgs& a, const float* dirs, hipStream_t s) {
+    if (!dirs || a.n_frames != 1u) return (int)hipErrorInvalidValue;
+    if (a.lens != 0u) {
+        with_scene_fold<FOLD_NONE>(a.scene_flags, [&](auto sf) {
+            launch_tile_rays_schedule(march_tile_rays_lens_kernel<decltype(sf)::value>, a, dirs, s);
+        });
+        return (int)hipGetLastError();
+    }
+    return with_format(a.format, [&](auto fmt) {
+        constexpr uint32_t FMT = decltype(fmt)::value;
+        with_scene_fold<FOLD_NONE>(a.scene_flags, [&](auto sf) {
+            if (a.ss_log2 != 0u) launch_tile_rays_schedule(march_tile_rays_kernel<FMT, decltype(sf)::value, true>, a, dirs, s);
+            else launch_tile_rays_schedule(march_tile_rays_kernel<FMT, decltype(sf)::value, false>, a, dirs, s);
+        });
+        return (int)hipGetLastError();
+    });
+}
+#endif
 // The shutter render's march (bh_render_shutter, n = 2^ln cameras per output frame; tile schedule): the same folds.
 template <bool FOLD_NONE>
 __attribute__((visibility("hidden"))) inline int launch_shutter(const MarchArgs& a, uint32_t ln, hipStream_t s) {

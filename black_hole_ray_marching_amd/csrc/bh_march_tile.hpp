@@ -41,14 +41,19 @@ __device__ __forceinline__ void select_outputs(MarchArgs& a, const FrameArgs& F)
 // SHUT (march_tile_shutter_kernel): a wave of a shutter workgroup -- the epilogue leaves the lane's samples in the
 // wave's LDS area (after the k x k butterfly when A.ss_log2 != 0) and stores nothing; *sl receives the lane's
 // pixel for the workgroup's resolve.  It stays as the caller set it (ok = false) when the tile is out of range.
+// RAYS (exact math, the march_tile_rays_*_kernel forms): the lane's direction is the caller's -- normalize_x of the 12
+// bytes of its pixel in the ray map `dirs` (bh_render_rays: row-major, the launch's width x height) -- instead of
+// pixel_ray's; c0..c2, rw2 and rh2 are not read.  A lane outside the frame loads nothing and takes (0, 0, 1).
 struct ShutterLane { uint32_t px, py; bool valid, ok; };
-template <uint32_t FMT, uint32_t SF, bool SS = false, bool ITEM = false, bool LENS = false, bool SHUT = false>
+template <uint32_t FMT, uint32_t SF, bool SS = false, bool ITEM = false, bool LENS = false, bool SHUT = false,
+          bool RAYS = false>
 __device__ __forceinline__ void march_slot(const MarchArgs& A, uint32_t slot, const float* lut,
                                            uint32_t lane, uint32_t item_tx = 0u, uint32_t item_ty = 0u,
-                                           ShutterLane* sl = nullptr) {
+                                           ShutterLane* sl = nullptr, const float* dirs = nullptr) {
     static_assert(SS || !ITEM, "work items are supersampled tiles");
     static_assert(!LENS || (!SS && !BH_FAST), "a lens is one record per ray, in exact math");
     static_assert(!SHUT || (!SS && !ITEM && !LENS), "a shutter wave takes its ss from the argument");
+    static_assert(!RAYS || (!BH_FAST && !ITEM && !SHUT), "a ray map feeds the exact plain, supersampled and lens forms");
     const uint32_t nf = A.n_frames;
     uint32_t fi = 0, j = slot;
     if constexpr (ITEM) {
@@ -83,6 +88,17 @@ __device__ __forceinline__ void march_slot(const MarchArgs& A, uint32_t slot, co
     const Frame f = make_frame(a);
     RayState st;
     st.ro = f.ro0;
+#if !BH_FAST
+    if constexpr (RAYS) {
+        // fs_main :362 with in.camera_to_vertex = the map's vector: any bit pattern, normalised as pixel_ray's is
+        v3 d = mk(0.0f, 0.0f, 1.0f);
+        if (valid) {
+            const float* p = dirs + ((size_t)py * a.width + px) * 3u;
+            d = mk(p[0], p[1], p[2]);
+        }
+        st.rd = normalize_x(d);
+    } else
+#endif
     st.rd = pixel_ray(a, valid ? px : 0u, valid ? py : 0u);
     st.s = ray_s(f, st.rd);
     st.travelled = 0.0f;
@@ -277,6 +293,32 @@ template <uint32_t SF>
 __global__ void __launch_bounds__(64 * WG_WAVES) march_tile_lens_kernel(MarchArgs A) {
     march_tile_wave<BH_OUT_RGBA32F, SF, false, true>(A, nullptr);
 }
+
+// The tile schedule's ray-map forms (bh_render_rays, bh_render_lens_rays): the plain, supersampled and lens kernels
+// with march_slot's RAYS switch -- the lane's direction from the caller's map, everything after it shared.  The map
+// is a second kernel argument of these kernels only (MarchArgs has no free word, and its layout is what the other
+// kernels were compiled against); it is read once per lane, before the loop.
+template <uint32_t FMT, uint32_t SF, bool SS, bool LENS>
+__device__ __forceinline__ void march_tile_rays_wave(const MarchArgs& A, const float* lut, const float* dirs) {
+    const uint32_t slot = __builtin_amdgcn_readfirstlane(blockIdx.x * WG_WAVES + (threadIdx.x >> 6));
+    if (slot >= A.n_tiles * A.n_frames) return;  // wave-uniform
+    const bool probe = A.clk && ((slot + (slot >> 8)) & A.clk_mask) == 0u;  // as march_tile_wave
+    ClockStart c0{0u, 0u};
+    if (probe) c0 = clock_start();
+    march_slot<FMT, SF, SS, false, LENS, false, true>(A, slot, lut, threadIdx.x & 63u, 0u, 0u, nullptr, dirs);
+    if (probe) clock_end(A.clk, c0);
+}
+template <uint32_t FMT, uint32_t SF, bool SS>
+__global__ void __launch_bounds__(64 * WG_WAVES) march_tile_rays_kernel(MarchArgs A, const float* dirs) {
+    __shared__ float lut[lds_tables<FMT>()];
+    load_srgb_tables<FMT, 64u * WG_WAVES>(A, lut);
+    __syncthreads();
+    march_tile_rays_wave<FMT, SF, SS, false>(A, lut, dirs);
+}
+template <uint32_t SF>
+__global__ void __launch_bounds__(64 * WG_WAVES) march_tile_rays_lens_kernel(MarchArgs A, const float* dirs) {
+    march_tile_rays_wave<BH_OUT_RGBA32F, SF, false, true>(A, nullptr, dirs);
+}
 #endif
 
 // The adaptive render's second pass (bh_render_adaptive; bh_refine.hpp): the supersampled march over a work
@@ -342,6 +384,13 @@ inline void launch_tile_schedule(K kernel, const MarchArgs& a, hipStream_t s) {
     const uint32_t waves = a.n_tiles * a.n_frames;
     const uint32_t blocks = (waves + (WG_WAVES - 1u)) / WG_WAVES;
     hipLaunchKernelGGL(kernel, dim3(blocks), dim3(64u * WG_WAVES), 0, s, a);
+}
+// ... its ray-map forms: the same grid, the map as the second argument
+template <class K>
+inline void launch_tile_rays_schedule(K kernel, const MarchArgs& a, const float* dirs, hipStream_t s) {
+    const uint32_t waves = a.n_tiles * a.n_frames;
+    const uint32_t blocks = (waves + (WG_WAVES - 1u)) / WG_WAVES;
+    hipLaunchKernelGGL(kernel, dim3(blocks), dim3(64u * WG_WAVES), 0, s, a, dirs);
 }
 // ... its shutter form: one workgroup of 2^ln waves per (output frame, tile); a.n_frames counts cameras
 template <uint32_t FMT, uint32_t SF>

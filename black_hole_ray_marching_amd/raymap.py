@@ -1,0 +1,139 @@
+"""Ray maps for Scene.render_rays / Scene.render_lens(dirs=...): host-side builders, numpy arrays (H, W, 3) float32.
+
+A ray map holds one direction per pixel (include/bh_render.h, "Ray maps"); the kernel normalises it, so a builder
+may return any positive multiple of the direction it means.  Upload a map with `torch.from_numpy(m).cuda()`.
+
+`pinhole` goes through the C helper and is defined to the bit: render_rays over it is render().  The other
+builders compute in float64 and round once to float32; they promise their formula (each docstring states it), not
+bits.  Conventions shared by them: pixel (x, y) has its centre at ((x + 0.5) / W, (y + 0.5) / H), y grows downwards;
+the view's frame is right-handed from `forward` and `up` as the scene's camera builds it -- f = forward / |forward|,
+r = normalize(cross(up, f)), u = cross(f, r) -- so +x on the image is r and +y on the image is -u.
+"""
+from __future__ import annotations
+
+import ctypes as C
+
+import numpy as np
+
+from . import _abi
+from ._abi import BhError, check, load
+
+FACES = ("+x", "-x", "+y", "-y", "+z", "-z")
+
+
+def _size(W, H) -> tuple[int, int]:
+    ok = all(isinstance(v, (int, np.integer)) and not isinstance(v, bool) and 1 <= int(v) <= 65536 for v in (W, H))
+    if not ok:
+        raise BhError(_abi.BH_ERR_INVALID_ARG, f"raymap: width and height must be integers in 1..65536, got {W!r} x {H!r}")
+    return int(W), int(H)
+
+
+def _angle(a, what: str, hi: float) -> float:
+    try:
+        v = float(a)
+    except (TypeError, ValueError):
+        v = float("nan")
+    if not 0.0 < v <= hi:
+        raise BhError(_abi.BH_ERR_INVALID_ARG, f"raymap: {what} must be an angle in (0, {hi:.6g}] radians, got {a!r}")
+    return v
+
+
+def basis(forward, up) -> tuple[np.ndarray, np.ndarray, np.ndarray]:
+    """(r, u, f) in float64 from a view direction and an up hint (neither zero nor parallel)."""
+    try:
+        f = np.asarray(forward, np.float64).reshape(3)
+        v = np.asarray(up, np.float64).reshape(3)
+    except (TypeError, ValueError):
+        raise BhError(_abi.BH_ERR_INVALID_ARG, "raymap: forward and up must be three numbers each")
+    nf = np.linalg.norm(f)
+    r = np.cross(v, f)
+    nr = np.linalg.norm(r)
+    if not (np.isfinite(nf) and nf > 0.0 and np.isfinite(nr) and nr > 1e-12 * nf * max(np.linalg.norm(v), 1e-300)):
+        raise BhError(_abi.BH_ERR_INVALID_ARG, "raymap: forward and up must be finite, non-zero and not parallel")
+    f = f / nf
+    r = r / nr
+    return r, np.cross(f, r), f
+
+
+def _centres(W: int, H: int) -> tuple[np.ndarray, np.ndarray]:
+    """The pixel centres as fractions of the image, sx (1, W) and sy (H, 1), float64."""
+    return ((np.arange(W, dtype=np.float64) + 0.5) / W)[None, :], ((np.arange(H, dtype=np.float64) + 0.5) / H)[:, None]
+
+
+def _compose(a, b, c, r, u, f) -> np.ndarray:
+    """a r + b u + c f per pixel, rounded once to float32."""
+    d = a[..., None] * r + b[..., None] * u + c[..., None] * f
+    return np.ascontiguousarray(d, dtype=np.float32)
+
+
+def pinhole(camera_uniform, W: int, H: int) -> np.ndarray:
+    """bh_ray_map_pinhole_host: the scene's own projection -- the unnormalised interpolated vector of
+    `camera_uniform`'s screen triangle at every pixel centre, in the kernel's fp32 operations.  render_rays over it,
+    from camera_uniform.pos, is render() bit for bit."""
+    W, H = _size(W, H)
+    out = np.empty((H, W, 3), np.float32)
+    cu = getattr(camera_uniform, "c", camera_uniform)
+    check(load().bh_ray_map_pinhole_host(C.byref(cu), W, H, out.ctypes.data), "bh_ray_map_pinhole_host")
+    return out
+
+
+def perspective(W: int, H: int, fovy: float, forward=(0.0, 0.0, 1.0), up=(0.0, 1.0, 0.0)) -> np.ndarray:
+    """A pinhole lens of vertical field of view `fovy` (radians, below pi), square pixels:
+    d = f + (2 sx - 1) t (W / H) r + (1 - 2 sy) t u,  t = tan(fovy / 2)."""
+    W, H = _size(W, H)
+    t = np.tan(0.5 * _angle(fovy, "fovy", np.nextafter(np.pi, 0.0)))
+    r, u, f = basis(forward, up)
+    sx, sy = _centres(W, H)
+    a = np.broadcast_to((2.0 * sx - 1.0) * (t * W / H), (H, W))
+    b = np.broadcast_to((1.0 - 2.0 * sy) * t, (H, W))
+    return _compose(a, b, np.ones((H, W)), r, u, f)
+
+
+def equirect(W: int, H: int, forward=(0.0, 0.0, 1.0), up=(0.0, 1.0, 0.0)) -> np.ndarray:
+    """The full sphere, longitude along x and latitude along y:
+    lon = (2 sx - 1) pi, lat = (0.5 - sy) pi,  d = cos(lat) sin(lon) r + sin(lat) u + cos(lat) cos(lon) f.
+    The image's centre looks along `forward`, its top row towards `up`."""
+    W, H = _size(W, H)
+    r, u, f = basis(forward, up)
+    sx, sy = _centres(W, H)
+    lon, lat = (2.0 * sx - 1.0) * np.pi, (0.5 - sy) * np.pi
+    return _compose(np.cos(lat) * np.sin(lon), np.broadcast_to(np.sin(lat), (H, W)), np.cos(lat) * np.cos(lon), r, u, f)
+
+
+def fisheye(W: int, H: int, fov: float, forward=(0.0, 0.0, 1.0), up=(0.0, 1.0, 0.0)) -> np.ndarray:
+    """An equidistant fisheye of full field of view `fov` (radians, up to 2 pi) across the image circle, the circle
+    inscribed in the image: with (X, Y) = ((2 sx - 1) W, (1 - 2 sy) H) / min(W, H) and rho = min(|(X, Y)|, 1),
+    theta = rho fov / 2,  d = sin(theta) (X r + Y u) / |(X, Y)| + cos(theta) f.
+    A pixel outside the circle holds the direction of the nearest rim point, so every pixel has a finite ray."""
+    W, H = _size(W, H)
+    half = 0.5 * _angle(fov, "fov", 2.0 * np.pi)
+    r, u, f = basis(forward, up)
+    sx, sy = _centres(W, H)
+    m = float(min(W, H))
+    X = np.broadcast_to((2.0 * sx - 1.0) * (W / m), (H, W))
+    Y = np.broadcast_to((1.0 - 2.0 * sy) * (H / m), (H, W))
+    rad = np.hypot(X, Y)
+    theta = np.minimum(rad, 1.0) * half
+    safe = np.where(rad > 0.0, rad, 1.0)
+    s = np.sin(theta)
+    return _compose(s * X / safe, s * Y / safe, np.cos(theta), r, u, f)
+
+
+def cube_face(N: int, face: str, forward=(0.0, 0.0, 1.0), up=(0.0, 1.0, 0.0)) -> np.ndarray:
+    """One N x N face of a cube map in the frame (r, u, f): face "+z" looks along f, "-z" against it, "+x" along r,
+    "+y" along u.  With a = 2 sx - 1 and b = 1 - 2 sy the direction is, in (r, u, f) coordinates,
+    +x: (1, b, -a)  -x: (-1, b, a)  +y: (a, 1, -b)  -y: (a, -1, b)  +z: (a, b, 1)  -z: (-a, b, -1)."""
+    N, _ = _size(N, N)
+    if face not in FACES:
+        raise BhError(_abi.BH_ERR_INVALID_ARG, f"raymap: face must be one of {FACES}, got {face!r}")
+    r, u, f = basis(forward, up)
+    sx, sy = _centres(N, N)
+    a = np.broadcast_to(2.0 * sx - 1.0, (N, N))
+    b = np.broadcast_to(1.0 - 2.0 * sy, (N, N))
+    one = np.ones((N, N))
+    x, y, z = {"+x": (one, b, -a), "-x": (-one, b, a), "+y": (a, one, -b), "-y": (a, -one, b),
+               "+z": (a, b, one), "-z": (-a, b, -one)}[face]
+    return _compose(x, y, z, r, u, f)
+
+
+__all__ = ["FACES", "basis", "pinhole", "perspective", "equirect", "fisheye", "cube_face"]

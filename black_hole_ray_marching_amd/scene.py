@@ -342,6 +342,37 @@ def _check_size(t, need: int, name: str, what: str = "render") -> None:
         raise BhError(_abi.BH_ERR_INVALID_ARG, f"{what}: {name} must be contiguous")
 
 
+def _check_dirs(dirs, height: int, width: int, what: str) -> None:
+    """A ray map as bh_render_rays takes it: a contiguous float32 device tensor of shape (height, width, 3) (raw
+    pointers are trusted)."""
+    if dirs is None:
+        raise BhError(_abi.BH_ERR_INVALID_ARG, f"{what}: dirs is required")
+    if isinstance(dirs, int):
+        return
+    if not hasattr(dirs, "data_ptr") or not hasattr(dirs, "is_cuda"):
+        raise BhError(_abi.BH_ERR_INVALID_ARG, f"{what}: dirs must be a device tensor (upload a raymap.* array first), "
+                                               f"got {type(dirs).__name__}")
+    if tuple(dirs.shape) != (height, width, 3):
+        raise BhError(_abi.BH_ERR_INVALID_ARG, f"{what}: dirs must be ({height}, {width}, 3), got {tuple(dirs.shape)}")
+    if dirs.element_size() != 4 or not dirs.dtype.is_floating_point:
+        raise BhError(_abi.BH_ERR_INVALID_ARG, f"{what}: dirs must be float32, got {dirs.dtype}")
+    if not dirs.is_contiguous():
+        raise BhError(_abi.BH_ERR_INVALID_ARG, f"{what}: dirs must be contiguous")
+    if not dirs.is_cuda:
+        raise BhError(_abi.BH_ERR_INVALID_ARG, f"{what}: dirs must be in device memory")
+
+
+def _pos_arg(pos, what: str):
+    """The origin of a ray-map render as the C ABI takes it: three floats."""
+    try:
+        p = [float(v) for v in pos]
+    except (TypeError, ValueError):
+        p = []
+    if len(p) != 3:
+        raise BhError(_abi.BH_ERR_INVALID_ARG, f"{what}: pos must be three floats, got {pos!r}")
+    return (C.c_float * 3)(*p)
+
+
 class FrameBatch:
     """A prepared bh_render_frames call (Scene.prepare_frames): its targets stay referenced, so the
     device pointers in its descriptors stay valid while the batch lives."""
@@ -569,11 +600,28 @@ class Scene:
         check(self.lib.bh_render_frames_shutter(self._ctx, n, n_sub, cams, C.byref(self.uniforms.to_c()), descs,
                                                 _ss_arg(ss), _stream_handle(stream)), "bh_render_frames_shutter")
 
+    def render_rays(self, dirs, output, blackout_output=None, *, pos=None, fmt: int = BH_OUT_RGBA32F, ss: int = 1,
+                    stream=None, schedule: int = 0, dbg_n_rk=None, dbg_fate=None, width: int | None = None,
+                    height: int | None = None) -> None:
+        """bh_render_rays: render() -- with ss = k > 1, render(ss=k) -- with the ray of every pixel taken from the
+        ray map `dirs`, a contiguous float32 device tensor (ss*height, ss*width, 3) of directions (any length: the
+        kernel normalises them; raymap.* builds some), all from the one origin `pos` (default: the scene camera's
+        position).  Any projection is a map.  Exact math, whatever the scene's math mode."""
+        k = _ss_arg(ss)
+        d = self._desc(output, blackout_output, fmt, dbg_n_rk, dbg_fate, BH_MATH_EXACT, BH_LAYOUT_ROWMAJOR, 0, 1,
+                       width, height, schedule, None)
+        _check_dirs(dirs, d.height * k, d.width * k, "render_rays")
+        p = _pos_arg(self.camera_uniform.pos if pos is None else pos, "render_rays")
+        check(self.lib.bh_render_rays(self._ctx, p, C.byref(self.uniforms.to_c()), C.byref(d), _ptr(dirs), k,
+                                      _stream_handle(stream)), "bh_render_rays")
+
     def render_lens(self, lens, *, width: int | None = None, height: int | None = None, schedule: int = 0,
-                    stream=None) -> None:
+                    stream=None, dirs=None, pos=None) -> None:
         """bh_render_lens: march this scene's camera once into `lens`, a device buffer of height x width records
         (u, v) of 8 bytes (e.g. a float32 tensor (H, W, 2)) -- the view, without any sky.  Exact math, whatever
-        the scene's math mode.  Shade it with shade(), as often and with as many skies as wanted."""
+        the scene's math mode.  Shade it with shade(), as often and with as many skies as wanted.
+        `dirs` (a ray map as render_rays takes it, (height, width, 3)): bh_render_lens_rays, the view of that map
+        from `pos` (default: the scene camera's position)."""
         d = _abi.bh_render_desc()
         d.width, d.height = width or self.width, height or self.height
         d.max_iters, d.scene_flags = self.max_iters, self.scene_flags
@@ -581,6 +629,14 @@ class Scene:
         if lens is None:
             raise BhError(_abi.BH_ERR_INVALID_ARG, "render_lens: lens is required")
         _check_size(lens, d.width * d.height * 8, "lens", "render_lens")
+        if dirs is not None:
+            _check_dirs(dirs, d.height, d.width, "render_lens")
+            p = _pos_arg(self.camera_uniform.pos if pos is None else pos, "render_lens")
+            check(self.lib.bh_render_lens_rays(self._ctx, p, C.byref(self.uniforms.to_c()), C.byref(d), _ptr(dirs),
+                                               _ptr(lens), _stream_handle(stream)), "bh_render_lens_rays")
+            return
+        if pos is not None:
+            raise BhError(_abi.BH_ERR_INVALID_ARG, "render_lens: pos belongs to a ray-map render (give dirs)")
         check(self.lib.bh_render_lens(self._ctx, C.byref(self.camera_uniform.c), C.byref(self.uniforms.to_c()),
                                       C.byref(d), _ptr(lens), _stream_handle(stream)), "bh_render_lens")
 

@@ -69,7 +69,7 @@ extern "C" {
 typedef enum {
     BH_OK = 0,
     BH_ERR_INVALID_ARG = -1,   /* NULL/zero/out-of-range argument */
-    BH_ERR_UNSUPPORTED = -2,   /* valid for the reference but not implemented (e.g. non-default screen triangle) */
+    BH_ERR_UNSUPPORTED = -2,   /* valid for the reference but not implemented (e.g. non-default screen triangle: another projection is a ray map, bh_render_rays) */
     BH_ERR_HIP = -3,           /* a HIP runtime call failed; see bh_last_error() */
     BH_ERR_NO_DEVICE = -4,     /* no HIP device / device index out of range */
     BH_ERR_OUT_OF_MEMORY = -5,
@@ -513,6 +513,45 @@ int bh_sky_mips_host(const uint8_t* sky_rgba8, uint32_t sky_w, uint32_t sky_h, u
 int bh_lens_shade_mip_host(const bh_lens_px* lens, uint32_t width, uint32_t height, uint32_t ss,
                            const uint8_t* sky_rgba8, uint32_t sky_w, uint32_t sky_h,
                            float* out_col_rgba, float* out_blackout_rgba_or_NULL);
+
+/* Ray maps: the caller's direction per pixel, any projection (not in the reference, whose rays are its pinhole's).
+ * A ray map (normative) is a device array of height x width x 3 fp32 values, row-major, 12 bytes per pixel, 4-byte
+ * aligned: dirs[(y * width + x) * 3 + c].  Pixel (x, y) of a ray-map render is fs_main
+ * (src/black_hole_maybe.wgsl:362-369) with in.camera_to_vertex = dirs[y][x] and camera.pos = pos: the kernel
+ * normalises the vector exactly as the exact-math path normalises the interpolated one -- d / sqrt(dot(d, d)), one
+ * rounding per op -- computes the ray's constant from it and marches; it does nothing else to the direction.  The
+ * map is an input like the sky's bytes: how the caller made it is outside parity.  A vector whose normalisation is
+ * not finite (the zero vector, an inf, a NaN) renders what the WGSL gives that normalised direction; a kernel reads
+ * the 12 bytes of its own pixel and nothing else of the map, whatever they hold.  One origin per frame: `pos`.
+ * Exact math only.  Not built for ray maps: several frames per call, shutter and adaptive renders, the tiled
+ * layouts, shards and partitions, fast math.
+ *
+ * bh_render_rays: bh_render (ss == 1; the dbg_* outputs are allowed) or bh_render_ss (ss = k in {2, 4, 8}: `dirs_dev`
+ * is the map of the virtual frame, k*height x k*width x 3, its samples resolved by bh_render_ss's normative tree and
+ * encoded once; dbg_* refused) with the map as the source of the directions.  Both targets (out_blackout may be
+ * NULL), the three formats.  bh_render_lens_rays: bh_render_lens likewise; its records feed bh_shade_lens and
+ * bh_shade_lens_mip as any lens does.
+ * BH_ERR_INVALID_ARG: a NULL or misaligned dirs_dev, a NULL pos, ss outside {1, 2, 4, 8}, the size limits of
+ * bh_render(_ss).  BH_ERR_UNSUPPORTED, with a sentence in bh_last_error() that starts with the function's name:
+ * math != BH_MATH_EXACT, a layout other than BH_LAYOUT_ROWMAJOR, shard_count != 1, a partition, a base schedule
+ * other than BH_SCHED_TILE (the BH_SCHED_FLAG_* flags are accepted; results never depend on them), and what
+ * bh_render_ss / bh_render_lens refuse of the outputs.  A refused call launches nothing and writes nothing.
+ * Graph contract: bh_render's -- the first call of a key allocates and is refused under capture, later calls are
+ * capturable.  The temporal order and the repeated-frame key of a ray-map launch are its own: keyed by geometry,
+ * stream and "ray map" (the map's address enters the repeated-frame key), so a bh_render of the same size on the
+ * same stream neither inherits the map's tile costs nor loses its own.  A map rewritten in place under the same
+ * address may meet a stale order: that costs time, never bytes. */
+int bh_render_rays(bh_ctx* ctx, const float pos[3], const bh_uniforms* uniforms, const bh_render_desc* desc,
+                   const float* dirs_dev, uint32_t ss, void* hip_stream);
+int bh_render_lens_rays(bh_ctx* ctx, const float pos[3], const bh_uniforms* uniforms, const bh_render_desc* desc,
+                        const float* dirs_dev, bh_lens_px* out_lens, void* hip_stream);
+/* Host only: the map of bh_render's own projection -- for every pixel the UNNORMALISED interpolated vector of the
+ * camera's screen triangle at the pixel centre, by the kernel's fp32 operations in its order (IEEE divisions by 2W
+ * and 2H, l1 = (1 - l0) - l2, (l0 c0 + l1 c1) + l2 c2) -- into out_dirs (height * width * 3 floats).
+ * bh_render_rays over it (uploaded, pos = camera->pos) is bh_render, bit for bit.  The starting point of any
+ * "pinhole plus distortion" map.  BH_ERR_INVALID_ARG: a NULL pointer, a side of 0 or above 65536;
+ * BH_ERR_UNSUPPORTED: a non-default screen triangle. */
+int bh_ray_map_pinhole_host(const bh_camera_uniform* camera, uint32_t width, uint32_t height, float* out_dirs);
 
 /* Bloom::render (src/bloom.rs:53-71): the reference's Kawase bloom + remix chain over the scene's two
  * targets, on BGRA8-sRGB images (bh_render with BH_OUT_BGRA8_SRGB): `col` (full_image_input),

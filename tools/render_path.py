@@ -14,7 +14,11 @@ Every frame integrated over a shutter interval: 8 sub-frame cameras per frame, a
 A moving sky behind a still camera instead: one frame per image in DIR, the view marched once into a lens map.
 
     python tools/render_path.py --sky-filter mip --sky stars_16k.jpg --width 1920 --height 1080
-The sky filtered through its mip chain: per frame a lens render and a filtered shade (bh_shade_lens_mip)."""
+The sky filtered through its mip chain: per frame a lens render and a filtered shade (bh_shade_lens_mip).
+
+    python tools/render_path.py --projection equirect --ss 2 --width 2048 --height 1024
+Another projection than the reference's pinhole: every frame marches a ray map (bh_render_rays) -- a 360-degree
+equirectangular frame, a fisheye:DEG dome frame, a perspective:DEG lens of another field of view."""
 import argparse
 import dataclasses
 import json
@@ -51,8 +55,27 @@ p.add_argument("--shutter-frac", type=float, default=0.5, metavar="S",
 p.add_argument("--sky-filter", choices=["none", "mip"], default="none",
                help="mip: every frame is a lens render (bh_render_lens) shaded through the sky's mip chain, the level "
                     "taken from the lens (bh_shade_lens_mip); with --ss 1, 2 or 4 and with --sky-frames")
+p.add_argument("--projection", default=None, metavar="{pinhole,equirect,fisheye:DEG,perspective:DEG}",
+               help="march a ray map instead of the camera's own rays (bh_render_rays): the map of the (ss x) frame "
+                    "is built once in the camera's frame and turned with the camera per frame; pinhole is the "
+                    "camera's own projection through the map (the same bytes); DEG: the full field of view of a "
+                    "fisheye (up to 360), the vertical one of a perspective lens (below 180)")
 args = p.parse_args()
 mip = args.sky_filter == "mip"
+proj, proj_deg = None, None
+if args.projection is not None:
+    proj, _, deg = args.projection.partition(":")
+    if proj not in ("pinhole", "equirect", "fisheye", "perspective") or bool(deg) != (proj in ("fisheye", "perspective")):
+        p.error("--projection is one of pinhole, equirect, fisheye:DEG, perspective:DEG")
+    try:
+        proj_deg = float(deg) if deg else None
+    except ValueError:
+        p.error(f"--projection {proj}:DEG needs a number of degrees, got {deg!r}")
+    if proj_deg is not None and not 0.0 < proj_deg <= (360.0 if proj == "fisheye" else 179.9):
+        p.error(f"--projection {proj}: DEG must lie in (0, {360 if proj == 'fisheye' else 179.9}]")
+    if args.shutter > 1 or args.adaptive is not None:
+        sys.exit("render_path: --projection does not combine with --shutter or --adaptive (ray maps are not built for "
+                 "shutter or adaptive renders)")
 if mip and (args.shutter > 1 or args.adaptive is not None):
     sys.exit("render_path: --sky-filter mip does not combine with --shutter or --adaptive (the filter is a lens shade)")
 if mip and args.ss == 8:
@@ -68,6 +91,7 @@ sys.path.insert(0, str(Path(__file__).resolve().parent.parent))
 import torch  # noqa: E402
 
 import black_hole_ray_marching_amd as bh  # noqa: E402
+from black_hole_ray_marching_amd import raymap  # noqa: E402
 from black_hole_ray_marching_amd.png import write_png  # noqa: E402
 W, H = args.width, args.height
 keys = []
@@ -101,6 +125,26 @@ def shutter_cameras(frame_cam):
     return out
 
 
+local_map = None
+if proj in ("equirect", "fisheye", "perspective"):  # once per frame size, in the camera's own frame (r, u, f)
+    kw, kh = args.ss * W, args.ss * H
+    m = (raymap.equirect(kw, kh) if proj == "equirect" else raymap.fisheye(kw, kh, np.radians(proj_deg))
+         if proj == "fisheye" else raymap.perspective(kw, kh, np.radians(proj_deg)))
+    local_map = torch.from_numpy(m).cuda()
+
+
+def ray_map(frame_cam):
+    """The frame's map in world space: the local map turned into the camera's frame (a product on the device), or
+    -- pinhole -- the camera's own map from the library's helper."""
+    if local_map is None:
+        cu = bh.CameraUniform()
+        cu.update(frame_cam)
+        return torch.from_numpy(raymap.pinhole(cu, args.ss * W, args.ss * H)).cuda()
+    r, u, f = raymap.basis(frame_cam.dir, frame_cam.up)
+    turn = torch.from_numpy(np.stack([r, u, f]).astype(np.float32)).cuda()
+    return (local_map.reshape(-1, 3) @ turn).reshape(local_map.shape).contiguous()
+
+
 t0 = time.perf_counter()
 if args.sky_frames:
     images = sorted(q for q in Path(args.sky_frames).iterdir() if q.is_file())
@@ -109,7 +153,7 @@ if args.sky_frames:
     k = args.ss
     scene.update(cam)
     lens = torch.empty((k * H, k * W, 2), dtype=torch.float32, device="cuda")
-    scene.render_lens(lens, width=k * W, height=k * H)  # the only march of the run
+    scene.render_lens(lens, width=k * W, height=k * H, dirs=ray_map(cam) if proj else None)  # the only march of the run
     for f, path in enumerate(images):
         frame_sky = bh.Sky(scene, bh.load_sky(path), mips=mip)
         scene.shade(lens, col, bo, fmt=bh.BH_OUT_BGRA8_SRGB, sky=frame_sky, ss=k, mip=mip)
@@ -129,8 +173,10 @@ for f in range(0 if args.sky_frames else args.frames):
     cam, moved = ctrl.update_camera(cam, args.dt)
     scene.update(cam)
     if mip:
-        scene.render_lens(path_lens, width=args.ss * W, height=args.ss * H)
+        scene.render_lens(path_lens, width=args.ss * W, height=args.ss * H, dirs=ray_map(cam) if proj else None)
         scene.shade(path_lens, col, bo, fmt=bh.BH_OUT_BGRA8_SRGB, sky=path_sky, ss=args.ss, mip=True)
+    elif proj:
+        scene.render_rays(ray_map(cam), col, bo, fmt=bh.BH_OUT_BGRA8_SRGB, ss=args.ss)
     elif args.shutter > 1:
         scene.render_shutter(col, bo, cameras=shutter_cameras(cam), fmt=bh.BH_OUT_BGRA8_SRGB, ss=args.ss)
     else:
@@ -142,5 +188,5 @@ for f in range(0 if args.sky_frames else args.frames):
 torch.cuda.synchronize()
 dt = time.perf_counter() - t0
 (out_dir / "path.json").write_text(json.dumps(log, indent=0))
-print(json.dumps({"frames": args.frames, "width": W, "height": H, "ss": args.ss, "adaptive": args.adaptive, "shutter": args.shutter, "sky_filter": args.sky_filter, "seconds": round(dt, 3),
+print(json.dumps({"frames": args.frames, "width": W, "height": H, "ss": args.ss, "adaptive": args.adaptive, "shutter": args.shutter, "sky_filter": args.sky_filter, "projection": args.projection, "seconds": round(dt, 3),
                   "frames_per_s_incl_png": round(args.frames / dt, 2), "out": str(out_dir)}))
