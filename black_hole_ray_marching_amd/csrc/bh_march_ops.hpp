@@ -67,6 +67,13 @@ constexpr float ONE_PI = 3.14159265359f;  // :83
 //          XOps<false> plain IEEE ops (the guard's fallback);  both = the oracle's arithmetic;
 //   fast:  FOps        hardware rsq / sqrt, FMA contraction.
 
+// sdf (:119-123) from its two terms: a disabled term is left out, as the WGSL leaves it out -- not taken as +inf,
+// since fminf(NaN, +inf) == +inf would drop the enabled term's NaN with it (a ray whose position is NaN)
+__device__ __forceinline__ float sdf_of_terms(uint32_t flags, float disc, float m) {
+    if (!(flags & BH_SCENE_MARKERS)) return (flags & BH_SCENE_DISC) ? disc : __builtin_inff();
+    return (flags & BH_SCENE_DISC) ? fminf(disc, m) : m;
+}
+
 #if BH_FAST
 struct FOps {
     bool bad = false;  // no guard in fast mode
@@ -258,9 +265,7 @@ struct XOps {
         const float rho = sqrt(rho2);
         const float disc = fmaxf(fmaxf(rho - 6.0f * rs, -(rho - 3.0f * rs)), fabsf(p.y - 0.0f) - 0.02f);
         const float m = sqrt(qm) - 0.5f;
-        // fminf(disc, inf) == disc and fminf(inf, m) == m bit for bit: same result as selecting
-        return fminf((flags & BH_SCENE_DISC) ? disc : __builtin_inff(),
-                     (flags & BH_SCENE_MARKERS) ? m : __builtin_inff());
+        return sdf_of_terms(flags, disc, m);
     }
 };
 #endif

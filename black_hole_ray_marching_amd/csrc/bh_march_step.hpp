@@ -154,8 +154,11 @@ __device__ __forceinline__ SdfSlack sdf_term_slacks(const MarchArgs& a, uint32_t
     float mark = __builtin_fmaf(-um, um, qm);
     const float up = T + 0.075f;
     float ps = __builtin_fmaf(-up, up, qps);
-    if (!(flags & BH_SCENE_DISC)) disc = __builtin_inff();
-    if (!(flags & BH_SCENE_MARKERS)) mark = __builtin_inff();
+    // a disabled term clears -- unless T is NaN: sdf_skip_slack's fminf would drop the other terms' NaN for it, and
+    // with no surfaces at all the step's dt is then fminf(+inf, NaN) = +inf, not dtm r
+    const float off = T != T ? T : __builtin_inff();
+    if (!(flags & BH_SCENE_DISC)) disc = off;
+    if (!(flags & BH_SCENE_MARKERS)) mark = off;
     return {disc, mark, ps};
 }
 __device__ __forceinline__ float sdf_skip_slack(const SdfSlack& t) { return fminf(fminf(t.disc, t.mark), t.ps); }
@@ -262,8 +265,7 @@ __device__ __forceinline__ bool step_bf(const MarchArgs& a, const Frame& f, cons
                 mv = X.mark_from(qm);
                 X.sq_arg(qm);
             }
-            const float ds = fminf((scene_flags & BH_SCENE_DISC) ? dv : __builtin_inff(),
-                                   (scene_flags & BH_SCENE_MARKERS) ? mv : __builtin_inff());  // :285
+            const float ds = sdf_of_terms(scene_flags, dv, mv);          // :285
             if (blackout | (ds < MIN_DIST)) {                            // :286-288
                 fate = blackout ? (uint32_t)BH_FATE_BLACKOUT : (uint32_t)BH_FATE_SURFACE;
                 return true;
@@ -472,8 +474,7 @@ __device__ __forceinline__ bool step_tail(const MarchArgs& a, const Frame& f, co
     const f2 qyx = (sq_xy + t2.yx) + bc(zz);
     const float qm = fminf(qyx.x, qyx.y);
     const float m = crm::sqrt_core(qm) - 0.5f;
-    const float ds = fminf((scene_flags & BH_SCENE_DISC) ? disc : __builtin_inff(),
-                           (scene_flags & BH_SCENE_MARKERS) ? m : __builtin_inff());
+    const float ds = sdf_of_terms(scene_flags, disc, m);
     if constexpr (SFS == SF_DYN || SFS == BH_SCENE_DEFAULT) G.bad |= crm::sqrt_bad2(rho2, qm);
     else if constexpr (SFS == BH_SCENE_DISC) G.bad |= crm::sqrt_bad(rho2);
     else if constexpr (SFS == BH_SCENE_MARKERS) G.bad |= crm::sqrt_bad(qm);

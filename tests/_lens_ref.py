@@ -15,8 +15,8 @@ import numpy as np
 import black_hole_ray_marching_amd as bh
 import oracle
 from oracle import oracle_np
-from tests._cases import camera_uniform, uniforms
-from tests._ss_ref import CAP, FLAGS, resolve_np, sky_ss
+from tests._cases import camera_uniform
+from tests._ss_ref import CAP, DEFAULT, FLAGS, resolve_np, scenario_uniforms, sky_ss  # noqa: F401  (shared with the tests)
 
 f32 = np.float32
 CAMS = ["D", "E", "F2", "H"]       # E: all four fates at both sizes; F2, H: the camera at or inside the unit sphere
@@ -33,17 +33,17 @@ def sky(name: str) -> np.ndarray:
 
 
 @functools.lru_cache(maxsize=None)
-def records(cam: str, W: int, H: int, k: int = 1):
+def records(cam: str, W: int, H: int, k: int = 1, scenario=DEFAULT):
     """(records (kH, kW, 2) fp32, fate (kH, kW) uint8) of the virtual frame kW x kH with the camera uniform of
     W x H: what bh_render_lens must write."""
-    cu, U = camera_uniform(cam, W, H), bytes(uniforms().to_c())
+    cu, U = camera_uniform(cam, W, H), bytes(scenario_uniforms(scenario).to_c())
     raw = np.frombuffer(cu.to_bytes(), f32)
     pos, tri = raw[0:3], raw[16:28].reshape(3, 4)[:, :3]
     dirs = oracle_np.pixel_dirs(tri, k * W, k * H)
     rec = np.zeros((k * H * k * W, 2), f32)
     fate = np.zeros(k * H * k * W, np.uint8)
     for i, rd0 in enumerate(dirs):
-        _, _, f, _, rd = oracle.trace_ray(pos, rd0, U, sky_ss(), CAP, FLAGS)
+        _, _, f, _, rd = oracle.trace_ray(pos, rd0, U, sky_ss(), scenario[0], scenario[1])
         fate[i] = f
         if f == bh.BH_FATE_BLACKOUT:
             rec[i] = (bh.BH_LENS_BLACKOUT, 0.0)
@@ -63,11 +63,11 @@ def records(cam: str, W: int, H: int, k: int = 1):
 
 
 @functools.lru_cache(maxsize=None)
-def frame(cam: str, W: int, H: int, sky_name: str, k: int = 1):
+def frame(cam: str, W: int, H: int, sky_name: str, k: int = 1, scenario=DEFAULT):
     """(col, blackout_col) fp32 (H, W, 4) of the view through `sky_name`: the oracle's frame, for k > 1 the
     normative resolve of the oracle's virtual frame."""
-    cu, U = camera_uniform(cam, W, H), uniforms()
-    col, bo, _, _ = oracle.render_rows(cu.to_bytes(), bytes(U.to_c()), sky(sky_name), k * W, k * H, CAP, FLAGS)
+    cu, U = camera_uniform(cam, W, H), scenario_uniforms(scenario)
+    col, bo, _, _ = oracle.render_rows(cu.to_bytes(), bytes(U.to_c()), sky(sky_name), k * W, k * H, scenario[0], scenario[1])
     assert not np.isnan(col).any() and not np.isnan(bo).any(), "the oracle frame holds a NaN"
     if k > 1:
         col, bo = resolve_np(col, k), resolve_np(bo, k)

@@ -18,8 +18,8 @@ import black_hole_ray_marching_amd as bh
 import oracle
 from black_hole_ray_marching_amd import raymap
 from oracle import oracle_np
-from tests._cases import CAMERAS, camera_uniform, uniforms
-from tests._ss_ref import CAP, FLAGS, resolve_np, sky_ss
+from tests._cases import CAMERAS, camera_uniform
+from tests._ss_ref import CAP, DEFAULT, FLAGS, resolve_np, scenario_uniforms, sky_ss  # noqa: F401  (shared with the tests)
 
 f32 = np.float32
 POSITIONS = ["D", "H", "F2"]       # outside and far; just outside the unit sphere (camera-outside step); inside it
@@ -95,17 +95,17 @@ def normalise(m: np.ndarray) -> np.ndarray:
     return out
 
 
-def trace(m: np.ndarray, pos: np.ndarray):
+def trace(m: np.ndarray, pos: np.ndarray, scenario=DEFAULT):
     """(col, blackout_col (H, W, 4), records (H, W, 2), fate (H, W) uint8, n_rk (H, W) uint16) of the map from pos."""
     H, W = m.shape[:2]
-    U = bytes(uniforms().to_c())
+    U = bytes(scenario_uniforms(scenario).to_c())
     dirs = normalise(m).reshape(-1, 3)
     col = np.ones((H * W, 4), f32)
     rec = np.zeros((H * W, 2), f32)
     fate = np.zeros(H * W, np.uint8)
     n_rk = np.zeros(H * W, np.uint16)
     for i, rd0 in enumerate(dirs):
-        rgb, n, f, _, rd = oracle.trace_ray(pos, rd0, U, sky_ss(), CAP, FLAGS)
+        rgb, n, f, _, rd = oracle.trace_ray(pos, rd0, U, sky_ss(), scenario[0], scenario[1])
         col[i, :3], fate[i], n_rk[i] = rgb, f, n
         if f == bh.BH_FATE_BLACKOUT:
             rec[i] = (bh.BH_LENS_BLACKOUT, 0.0)
@@ -129,12 +129,13 @@ def trace(m: np.ndarray, pos: np.ndarray):
 
 
 @functools.lru_cache(maxsize=None)
-def general(name: str, W: int, H: int):
-    """trace() of general_map(name, W, H) from the position; the map reaches all four fates (asserted here)."""
-    out = trace(general_map(name, W, H), position(name))
+def general(name: str, W: int, H: int, scenario=DEFAULT):
+    """trace() of general_map(name, W, H) from the position; in the default scenario the map reaches all four fates
+    (asserted here; the fates of the others: tests/test_scenarios_host.py)."""
+    out = trace(general_map(name, W, H), position(name), scenario)
     seen = set(np.unique(out[3]).tolist())
     want = {bh.BH_FATE_CAP, bh.BH_FATE_ESCAPE, bh.BH_FATE_SURFACE, bh.BH_FATE_BLACKOUT}
-    assert seen == want, f"general map {name} {W}x{H}: fates {sorted(seen)}"
+    assert scenario != DEFAULT or seen == want, f"general map {name} {W}x{H}: fates {sorted(seen)}"
     return out
 
 
@@ -144,9 +145,9 @@ def nonfinite(name: str):
 
 
 @functools.lru_cache(maxsize=None)
-def equirect_ss(name: str, W: int, H: int, k: int):
+def equirect_ss(name: str, W: int, H: int, k: int, scenario=DEFAULT):
     """(col, blackout_col) (H, W, 4): ss = k over the virtual frame's equirect map, resolved by the normative tree."""
-    col, bo, _, _, _ = trace(equirect_map(k * W, k * H), position(name))
+    col, bo, _, _, _ = trace(equirect_map(k * W, k * H), position(name), scenario)
     assert not np.isnan(col).any() and not np.isnan(bo).any()
     rc, rb = resolve_np(col, k), resolve_np(bo, k)
     rc.setflags(write=False)
@@ -163,10 +164,10 @@ def pinhole_map(cam: str, W: int, H: int, k: int = 1) -> np.ndarray:
 
 
 @functools.lru_cache(maxsize=None)
-def oracle_dbg(cam: str, W: int, H: int):
+def oracle_dbg(cam: str, W: int, H: int, scenario=DEFAULT):
     """(n_rk (H, W) uint16, fate (H, W) uint8) of the oracle's frame (render_rows)."""
-    cu, U = camera_uniform(cam, W, H), uniforms()
-    _, _, n_rk, fate = oracle.render_rows(cu.to_bytes(), bytes(U.to_c()), sky_ss(), W, H, CAP, FLAGS)
+    cu, U = camera_uniform(cam, W, H), scenario_uniforms(scenario)
+    _, _, n_rk, fate = oracle.render_rows(cu.to_bytes(), bytes(U.to_c()), sky_ss(), W, H, scenario[0], scenario[1])
     return n_rk.astype(np.uint16), fate.astype(np.uint8)
 
 

@@ -10,8 +10,8 @@ import numpy as np
 
 import black_hole_ray_marching_amd as bh
 import oracle
-from tests._cases import CAMERAS, camera_uniform, uniforms
-from tests._ss_ref import CAP, FLAGS, SIZES, expected_bytes, resolve_np, sky_ss  # noqa: F401  (shared with the tests)
+from tests._cases import CAMERAS, camera_uniform
+from tests._ss_ref import CAP, DEFAULT, FLAGS, SIZES, expected_bytes, resolve_np, scenario_uniforms, sky_ss  # noqa: F401  (shared with the tests)
 
 NS = [2, 4, 8, 16]
 MIXED = ["D", "E", "H", "F2", "B", "C", "G", "F"]  # unrelated views, all four fates; cycled for n = 16
@@ -42,24 +42,25 @@ CAMERA_SETS = {"mixed": mixed, "sweep": sweep}
 
 
 @functools.lru_cache(maxsize=None)
-def _oracle_virtual(cam_bytes: bytes, W: int, H: int, k: int):
-    col, bo, _, fate = oracle.render_rows(cam_bytes, bytes(uniforms().to_c()), sky_ss(), k * W, k * H, CAP, FLAGS)
+def _oracle_virtual(cam_bytes: bytes, W: int, H: int, k: int, scenario=DEFAULT):
+    col, bo, _, fate = oracle.render_rows(cam_bytes, bytes(scenario_uniforms(scenario).to_c()), sky_ss(), k * W, k * H,
+                                          scenario[0], scenario[1])
     assert not np.isnan(col).any() and not np.isnan(bo).any(), "the oracle frame holds a NaN"
     for x in (col, bo, fate):
         x.setflags(write=False)
     return col, bo, fate
 
 
-def oracle_virtual(cam, W: int, H: int, k: int):
+def oracle_virtual(cam, W: int, H: int, k: int, scenario=DEFAULT):
     """The oracle's (col, blackout_col, fate) of the virtual frame kW x kH for CameraUniform `cam`."""
-    return _oracle_virtual(cam.to_bytes(), W, H, k)
+    return _oracle_virtual(cam.to_bytes(), W, H, k, scenario)
 
 
-def samples(cams, W: int, H: int, k: int):
+def samples(cams, W: int, H: int, k: int, scenario=DEFAULT):
     """(col, blackout_col) samples of every camera before the time resolve, fp32 (n, H, W, 4): the oracle's frame
     (ss = 1) or its k x k resolve."""
-    col = np.stack([resolve_np(oracle_virtual(c, W, H, k)[0], k) for c in cams])
-    bo = np.stack([resolve_np(oracle_virtual(c, W, H, k)[1], k) for c in cams])
+    col = np.stack([resolve_np(oracle_virtual(c, W, H, k, scenario)[0], k) for c in cams])
+    bo = np.stack([resolve_np(oracle_virtual(c, W, H, k, scenario)[1], k) for c in cams])
     return col, bo
 
 
@@ -85,9 +86,9 @@ def running_sum_np(v: np.ndarray) -> np.ndarray:
     return np.concatenate([s, np.ones(s.shape[:2] + (1,), np.float32)], -1)
 
 
-def reference(cams, W: int, H: int, k: int = 1):
+def reference(cams, W: int, H: int, k: int = 1, scenario=DEFAULT):
     """(col, blackout_col) fp32 (H, W, 4): the normative result for the cameras `cams` of one output frame."""
-    col, bo = samples(cams, W, H, k)
+    col, bo = samples(cams, W, H, k, scenario)
     rc, rb = time_tree_np(col), time_tree_np(bo)
     rc.setflags(write=False)
     rb.setflags(write=False)

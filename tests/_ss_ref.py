@@ -12,6 +12,7 @@ import oracle
 from tests._cases import camera_uniform, uniforms
 
 CAP, FLAGS = 64, 3
+DEFAULT = (CAP, FLAGS, ())    # a scenario (tests/_scenarios.py): (cap, flags, ((uniform name, value), ...))
 SIZES = [(13, 7), (40, 24)]   # 13x7: the virtual frame ends inside a tile on both axes at every k; 40x24: whole
 KS = [2, 4, 8]                # and partial tiles, interior groups
 
@@ -40,21 +41,26 @@ def resolve_np(a: np.ndarray, k: int) -> np.ndarray:
     return np.concatenate([v, np.ones(v.shape[:2] + (1,), np.float32)], -1)
 
 
+def scenario_uniforms(scenario=DEFAULT):
+    """The Uniforms of a scenario: the defaults with its overrides."""
+    return uniforms(**dict(scenario[2]))
+
+
 @functools.lru_cache(maxsize=None)
-def oracle_virtual(cam: str, W: int, H: int, k: int):
+def oracle_virtual(cam: str, W: int, H: int, k: int, scenario=DEFAULT):
     """The oracle's (col, blackout_col, fate) of the virtual frame kW x kH with the camera uniform of W x H."""
-    cu, U = camera_uniform(cam, W, H), uniforms()
-    col, bo, _, fate = oracle.render_rows(cu.to_bytes(), bytes(U.to_c()), sky_ss(), k * W, k * H, CAP, FLAGS)
+    cu, U = camera_uniform(cam, W, H), scenario_uniforms(scenario)
+    col, bo, _, fate = oracle.render_rows(cu.to_bytes(), bytes(U.to_c()), sky_ss(), k * W, k * H, scenario[0], scenario[1])
     for x in (col, bo, fate):
         x.setflags(write=False)
     return col, bo, fate
 
 
 @functools.lru_cache(maxsize=None)
-def reference(cam: str, W: int, H: int, k: int):
+def reference(cam: str, W: int, H: int, k: int, scenario=DEFAULT):
     """(col, blackout_col) fp32 (H, W, 4): the normative result of ss = k.  The blackout samples are the
     oracle's per-fragment blackout_col: the test runs per sample, not on the average."""
-    col, bo, _ = oracle_virtual(cam, W, H, k)
+    col, bo, _ = oracle_virtual(cam, W, H, k, scenario)
     assert not np.isnan(col).any() and not np.isnan(bo).any(), "the oracle frame holds a NaN"
     rc, rb = resolve_np(col, k), resolve_np(bo, k)
     rc.setflags(write=False)

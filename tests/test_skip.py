@@ -19,14 +19,21 @@ def fms(u, v):
         return (v.astype(np.float64) - u.astype(np.float64) ** 2).astype(f32)
 
 
+def sdf_of_terms(flags, disc, m):
+    """bh_march_ops.hpp sdf_of_terms (:119-123): a disabled term is left out, not taken as +inf"""
+    if not flags & MARKERS:
+        return disc if flags & DISC else np.full_like(disc, np.inf)
+    return np.fmin(disc, m) if flags & DISC else m
+
+
 def predicate(flags, dtr, rho2, yy, qm, qps, rs):
     """sdf_skip_slack(...) >= 0 (NaN fails)"""
     T = fma32(dtr, 1.125, f32(0.002))
     u6 = T + f32(6.0) * rs
     uy, um, up = T + f32(0.02), T + f32(0.5), T + f32(0.075)
-    inf = np.full_like(dtr, np.inf)
-    disc = np.fmax(fms(u6, rho2), fms(uy, yy)) if flags & DISC else inf
-    mark = fms(um, qm) if flags & MARKERS else inf
+    off = np.where(np.isnan(T), T, f32(np.inf))  # a disabled term clears, unless T is NaN
+    disc = np.fmax(fms(u6, rho2), fms(uy, yy)) if flags & DISC else off
+    mark = fms(um, qm) if flags & MARKERS else off
     slack = np.fmin(np.fmin(disc, mark), fms(up, qps))
     return slack >= 0
 
@@ -36,8 +43,7 @@ def full_step(flags, dtr, rho2, y, qm, qps, rs):
     rho = np.sqrt(rho2)
     disc = np.fmax(np.fmax(rho - f32(6.0) * rs, -(rho - f32(3.0) * rs)), np.abs(y) - f32(0.02))
     m = np.sqrt(qm) - f32(0.5)
-    inf = f32(np.inf)
-    ds = np.fmin(disc if flags & DISC else inf, m if flags & MARKERS else inf)
+    ds = sdf_of_terms(flags, disc, m)
     dps = np.sqrt(qps) - f32(0.075)
     dist = np.fmin(ds, dps)
     dt = np.fmin(dist * f32(0.9), dtr)
@@ -84,9 +90,9 @@ def term_slacks(flags, dtr, rho2, yy, qm, qps, rs):
     T = fma32(dtr, 1.125, f32(0.002))
     u6 = T + f32(6.0) * rs
     uy, um, up = T + f32(0.02), T + f32(0.5), T + f32(0.075)
-    inf = np.full_like(dtr, np.inf)
-    disc = np.fmax(fms(u6, rho2), fms(uy, yy)) if flags & DISC else inf
-    mark = fms(um, qm) if flags & MARKERS else inf
+    off = np.where(np.isnan(T), T, f32(np.inf))  # a disabled term clears, unless T is NaN
+    disc = np.fmax(fms(u6, rho2), fms(uy, yy)) if flags & DISC else off
+    mark = fms(um, qm) if flags & MARKERS else off
     return disc, mark, fms(up, qps)
 
 
@@ -96,7 +102,7 @@ def step_without(flags, dtr, rho2, y, qm, qps, rs, skip_d, skip_m, skip_p):
     inf = f32(np.inf)
     disc = np.where(skip_d, inf, np.fmax(np.fmax(rho - f32(6.0) * rs, -(rho - f32(3.0) * rs)), np.abs(y) - f32(0.02)))
     m = np.where(skip_m, inf, np.sqrt(qm) - f32(0.5))
-    ds = np.fmin(disc if flags & DISC else inf, m if flags & MARKERS else inf)
+    ds = sdf_of_terms(flags, disc, m)
     dps = np.where(skip_p, inf, np.sqrt(qps) - f32(0.075))
     dt = np.fmin(np.fmin(ds, dps) * f32(0.9), dtr)
     return dt, ds < f32(0.001)
@@ -136,6 +142,20 @@ def test_skip_rejects_nan_and_infinite_thresholds():
     assert ok.tolist() == [True, False, False, True, False, False]
     dt, surface = full_step(DISC | MARKERS, dtr[[0]], big[[0]], np.sqrt(big[[0]]), big[[0]], big[[0]], rs)
     assert dt[0] == dtr[0] and not surface[0]
+
+
+@pytest.mark.parametrize("flags", [0, DISC, MARKERS, DISC | MARKERS])
+def test_disabled_terms_do_not_hide_a_nan(flags):
+    """A ray whose position is NaN (r, dtm r and every enabled distance NaN): the test fails in every fold -- with
+    the disabled terms taken as +inf, fminf dropped the others' NaN and it passed -- and the step's dt is the
+    WGSL's: fminf(+inf, NaN) = +inf with no surfaces at all (the ray escapes), NaN as soon as one term is enabled
+    (it runs to the cap).  tests/test_gpu_forms_matrix.py::test_rays_general holds the kernels to that."""
+    nan, rs = np.array([np.nan], f32), f32(1.0)
+    assert not predicate(flags, nan, nan, nan, nan, nan, rs)[0]
+    assert not any((s >= 0)[0] for s in term_slacks(flags, nan, nan, nan, nan, nan, rs))
+    with np.errstate(invalid="ignore"):
+        dt, surface = full_step(flags, nan, nan, nan, nan, nan, rs)
+    assert not surface[0] and (np.isnan(dt[0]) if flags else dt[0] == np.inf)
 
 
 def far_r2(rs, dtm):
