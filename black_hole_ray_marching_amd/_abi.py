@@ -84,6 +84,10 @@ class bh_shade_desc(C.Structure):
                 ("lens", C.c_void_p), ("sky", C.c_void_p), ("out_col", C.c_void_p), ("out_blackout", C.c_void_p)]
 
 
+class bh_ray_pose(C.Structure):
+    _fields_ = [("pos", C.c_float * 3), ("r", C.c_float * 3), ("u", C.c_float * 3), ("f", C.c_float * 3)]
+
+
 class bh_presenter_desc(C.Structure):
     _fields_ = [(n, C.c_uint32) for n in ("width", "height", "max_iters", "scene_flags", "math", "levels", "batch",
                                           "bloom_cus", "depth", "march_streams")]
@@ -148,6 +152,14 @@ SIGNATURES = {
     "bh_render_lens_rays": (C.c_int, [C.c_void_p, C.POINTER(C.c_float), C.POINTER(bh_uniforms),
                                       C.POINTER(bh_render_desc), C.c_void_p, C.c_void_p, C.c_void_p]),
     "bh_ray_map_pinhole_host": (C.c_int, [C.POINTER(bh_camera_uniform), C.c_uint32, C.c_uint32, C.c_void_p]),
+    "bh_render_frames_rays": (C.c_int, [C.c_void_p, C.c_uint32, C.POINTER(bh_ray_pose), C.POINTER(bh_uniforms),
+                                        C.POINTER(bh_render_desc), C.c_void_p, C.c_uint32, C.c_void_p]),
+    "bh_render_frames_shutter_rays": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(bh_ray_pose),
+                                                C.POINTER(bh_uniforms), C.POINTER(bh_render_desc), C.c_void_p,
+                                                C.c_uint32, C.c_void_p]),
+    "bh_render_lens_rays_posed": (C.c_int, [C.c_void_p, C.POINTER(bh_ray_pose), C.POINTER(bh_uniforms),
+                                            C.POINTER(bh_render_desc), C.c_void_p, C.c_void_p, C.c_void_p]),
+    "bh_ray_pose_apply_host": (C.c_int, [C.POINTER(bh_ray_pose), C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p]),
     "bh_shard_tile_count": (C.c_int64, [C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32]),
     "bh_tiles_unpack": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32,
                                   C.c_uint64, C.c_uint32, C.c_void_p]),

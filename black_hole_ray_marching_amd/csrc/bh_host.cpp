@@ -411,9 +411,10 @@ static void frame_args(const bh_camera_uniform* cam, float rs, const bh_render_d
 // What a frame's per-tile costs (the march's step counts) depend on: the camera, the shader uniforms and the
 // launch shape -- FNV-1a over those fields' bits (padding and the unused bg_brightness left out).  The
 // outputs, their format and the sky do not change a step count.  A ray-map launch's rays are its map's: the map's
-// address enters the key (its contents cannot: a map rewritten in place may meet a stale order, never other bytes).
+// address enters the key (its contents cannot: a map rewritten in place may meet a stale order, never other bytes),
+// and so does every pose of a posed launch (after a marker: a posed launch is never taken for an unposed one).
 static uint64_t frame_cost_key(const bh_camera_uniform* cam, const bh_uniforms* U, const bh_render_desc* d,
-                               const float* ray_map = nullptr) {
+                               const float* ray_map = nullptr, const bh_ray_pose* poses = nullptr, uint32_t n_poses = 0u) {
     uint64_t h = 1469598103934665603ull;
     auto mix = [&](const void* p, size_t n) {
         const unsigned char* b = static_cast<const unsigned char*>(p);
@@ -430,6 +431,10 @@ static uint64_t frame_cost_key(const bh_camera_uniform* cam, const bh_uniforms* 
     mix(f, sizeof f);
     mix(&pser, sizeof pser);
     if (ray_map) mix(&ray_map, sizeof ray_map);
+    if (poses) {
+        mix(&n_poses, sizeof n_poses);
+        mix(poses, sizeof(bh_ray_pose) * n_poses);
+    }
     return h | 1u;  // never 0: 0 marks the fresh state's all-zero costs
 }
 
@@ -501,6 +506,7 @@ struct Launch {
     uint64_t n_tiles = 0;              // the shard's tiles
     uint32_t shutter_log2 = 0;         // bh_render_shutter: log2 of the cameras per output frame (a.n_frames counts cameras)
     const float* ray_map = nullptr;    // bh_render_rays, bh_render_lens_rays: the device map the rays come from
+    const bh_ray_pose* poses = nullptr;  // the posed ray-map forms: one pose per camera (a.n_frames of them), else null
 };
 
 // Every argument check of a launch; no HIP call.  Leaves the launch's desc and tile count in L.
@@ -628,7 +634,7 @@ static int learned_order(bh_ctx* c, Launch* L, const bh_camera_uniform* cam0, co
     // buffers behind them costs at most a stale order, never a disagreement.  BH_ORDER_ALWAYS (A/B):
     // build and write on every launch, as before round 5.
     static const bool always = std::getenv("BH_ORDER_ALWAYS") != nullptr;
-    const uint64_t key = frame_cost_key(cam0, U, d, L->ray_map);
+    const uint64_t key = frame_cost_key(cam0, U, d, L->ray_map, L->poses, a.n_frames);
     const bool repeat = !always && os->order_key == os->cost_key && os->cost_key == key;
     if (!repeat) {
         int oe = bh_launch_build_order(os->tile_cost, a.n_tiles, a.order_block, a.order_centre, os->counters,
@@ -651,7 +657,10 @@ static int launch_march(bh_ctx* c, const Launch& L, bh_ctx::OrderState* os, hipS
     const uint32_t sched = d->schedule & 0xFFu;
     const bool issue = march_variant_issue_order(d, a.n_tiles, a.n_frames, c->cus);  // every camera's tiles
     int e;
-    if (L.ray_map)  // exact math, tile schedule (render_rays)
+    if (L.poses)  // exact math, tile schedule (render_rays_posed); the shutter form when shutter_log2 != 0
+        e = issue ? bh_launch_rays_pose_exact(a, L.ray_map, L.shutter_log2, s)
+                  : bh_launch_rays_pose_exact_lat(a, L.ray_map, L.shutter_log2, s);
+    else if (L.ray_map)  // exact math, tile schedule (render_rays)
         e = issue ? bh_launch_rays_exact(a, L.ray_map, s) : bh_launch_rays_exact_lat(a, L.ray_map, s);
     else if (const uint32_t ln = L.shutter_log2)
         e = d->math != BH_MATH_EXACT ? bh_launch_shutter_fast(a, ln, s)
@@ -862,6 +871,96 @@ int bh_render_lens_rays(bh_ctx* c, const float pos[3], const bh_uniforms* U, con
                         const float* dirs_dev, bh_lens_px* out_lens, void* stream) {
     if (!out_lens || (reinterpret_cast<uintptr_t>(out_lens) & 7u)) return bad_arg(__func__, __LINE__);
     return render_rays(__func__, c, pos, U, d, dirs_dev, 1u, out_lens, stream);
+}
+
+// ---- posed ray maps (include/bh_render.h, bh_ray_pose): one camera-space map, one pose per camera -----------
+// bh_render_frames_rays (n_sub 1), bh_render_frames_shutter_rays (n_sub > 1) and bh_render_lens_rays_posed
+// (out_lens): render_rays' launch -- the ray-map order state, the map in the repeated-frame key -- of
+// n_frames * n_sub cameras as bh_render_frames(_ss) or bh_render_frames_shutter launches them: one FrameArgs entry
+// per camera, holding its position and, in c0..c2, its basis rows (march_slot's POSE form reads them there).
+static int render_rays_posed(const char* fn, bh_ctx* c, uint32_t n_frames, uint32_t n_sub, const bh_ray_pose* poses,
+                             const bh_uniforms* U, const bh_render_desc* descs, const float* dirs, uint32_t ss,
+                             bh_lens_px* out_lens, void* stream) {
+    if (!c || !poses || !U || !descs || !dirs || (reinterpret_cast<uintptr_t>(dirs) & 3u)) return bad_arg(fn, __LINE__);
+    const uint32_t ln = bh::shutter::log2_n(n_sub);
+    if (ln > bh::shutter::MAX_LOG2 || bh::ss::log2_k(ss) > 3u) return bad_arg(fn, __LINE__);
+    if (n_frames == 0 || (uint64_t)n_frames * n_sub > BH_MAX_FRAMES) return bad_arg(fn, __LINE__);
+    if (!frame_shape_ok(descs[0].width, descs[0].height, ss)) return bad_arg(fn, __LINE__);
+    const uint32_t n_cams = n_frames * n_sub;
+    std::vector<bh_render_desc> per_cam, plain;
+    std::vector<bh_camera_uniform> cams;
+    try {
+        per_cam.reserve(n_cams);
+        plain.assign(descs, descs + n_frames);
+        cams.resize(n_cams);
+    } catch (const std::bad_alloc&) {
+        return BH_ERR_OUT_OF_MEMORY;
+    }
+    // the dbg_* outputs are per ray: allowed where bh_render_frames allows them (ss == 1, no shutter)
+    if (ss == 1u && n_sub == 1u && !out_lens)
+        for (auto& e : plain) e.dbg_n_rk = nullptr, e.dbg_fate = nullptr, e.dbg_steps = nullptr;
+    const char* why = nullptr;
+    for (uint32_t i = 0; i < n_frames && !why; ++i)
+        why = descs[i].math == BH_MATH_FAST ? "exact math (BH_MATH_EXACT): a ray map has no fast-math kernels"
+              : out_lens && (descs[i].out_col || descs[i].out_blackout) ? "no out_col or out_blackout (it writes only the lens)"
+                                                                       : nullptr;
+    if (!why) why = ss_needs(plain.data(), n_frames);
+    if (why) {
+        g_last_error = std::string(fn) + ": a ray-map render needs " + why + ".";
+        return BH_ERR_UNSUPPORTED;
+    }
+    static const float st[3][2] = {{3.0f, 1.0f}, {-1.0f, 1.0f}, {-1.0f, -3.0f}};
+    for (uint32_t i = 0; i < n_cams; ++i) {  // as render_rays: a camera that holds only the position
+        std::memset(&cams[i], 0, sizeof cams[i]);
+        for (int k = 0; k < 3; ++k) {
+            cams[i].pos[k] = poses[i].pos[k];
+            cams[i].screen_tri[k][0] = st[k][0];
+            cams[i].screen_tri[k][1] = st[k][1];
+        }
+        per_cam.push_back(descs[i / n_sub]);
+        if (out_lens) {  // as bh_render_lens: the lens in place of target 0, the format word not read
+            per_cam.back().format = BH_OUT_RGBA32F;
+            per_cam.back().out_col = out_lens;
+        }
+    }
+    Launch L;
+    const int e = check_launch(c, n_cams, cams.data(), U, per_cam.data(), ss, &L);
+    if (e != BH_OK) return e;
+    fill_args(c, n_cams, cams.data(), U, per_cam.data(), ss, &L);
+    bh::FrameArgs* fa = L.table.empty() ? L.a.frames : L.table.data();
+    for (uint32_t i = 0; i < n_cams; ++i)
+        for (int k = 0; k < 3; ++k) {
+            fa[i].c0[k] = poses[i].r[k]; fa[i].c1[k] = poses[i].u[k]; fa[i].c2[k] = poses[i].f[k];
+        }
+    for (int k = 0; k < 3; ++k) {  // camera 0's again in the argument itself (fill_args)
+        L.a.c0[k] = fa[0].c0[k]; L.a.c1[k] = fa[0].c1[k]; L.a.c2[k] = fa[0].c2[k];
+    }
+    L.a.lens = out_lens ? 1u : 0u;
+    if (ln != 0u) {
+        L.a.ss_out_width = descs[0].width;  // the shutter kernels index the output through it at every ss
+        L.shutter_log2 = ln;
+    }
+    L.ray_map = dirs;
+    L.poses = poses;
+    return march_in_order(c, &L, cams.data(), U, stream);
+}
+
+int bh_render_frames_rays(bh_ctx* c, uint32_t n_frames, const bh_ray_pose* poses, const bh_uniforms* U,
+                          const bh_render_desc* descs, const float* dirs_dev, uint32_t ss, void* stream) {
+    return render_rays_posed(__func__, c, n_frames, 1u, poses, U, descs, dirs_dev, ss, nullptr, stream);
+}
+
+int bh_render_frames_shutter_rays(bh_ctx* c, uint32_t n_frames, uint32_t n_sub, const bh_ray_pose* poses,
+                                  const bh_uniforms* U, const bh_render_desc* descs, const float* dirs_dev, uint32_t ss,
+                                  void* stream) {
+    if (n_sub == 0u) return bad_arg(__func__, __LINE__);
+    return render_rays_posed(__func__, c, n_frames, n_sub, poses, U, descs, dirs_dev, ss, nullptr, stream);
+}
+
+int bh_render_lens_rays_posed(bh_ctx* c, const bh_ray_pose* pose, const bh_uniforms* U, const bh_render_desc* d,
+                              const float* dirs_dev, bh_lens_px* out_lens, void* stream) {
+    if (!out_lens || (reinterpret_cast<uintptr_t>(out_lens) & 7u)) return bad_arg(__func__, __LINE__);
+    return render_rays_posed(__func__, c, 1u, 1u, pose, U, d, dirs_dev, 1u, out_lens, stream);
 }
 
 // bh_sky_create and bh_sky_create_mips: the texels, and with `mips` the chain built from them (a synchronous call)

@@ -203,6 +203,11 @@ BH_INTERNAL int bh_launch_march_fast(const bh::MarchArgs& a, uint32_t schedule, 
 // the ray-map march (bh_march_rays.hip): one frame, tile schedule; a.lens / a.ss_log2 pick the form
 BH_INTERNAL int bh_launch_rays_exact(const bh::MarchArgs& a, const float* dirs, hipStream_t s);
 BH_INTERNAL int bh_launch_rays_exact_lat(const bh::MarchArgs& a, const float* dirs, hipStream_t s);
+// the posed ray-map march (bh_march_rays_pose.hip): a.n_frames cameras over one map, their bases in c0..c2;
+// shutter_log2 != 0: the shutter form, 2^shutter_log2 cameras per output frame
+BH_INTERNAL int bh_launch_rays_pose_exact(const bh::MarchArgs& a, const float* dirs, uint32_t shutter_log2, hipStream_t s);
+BH_INTERNAL int bh_launch_rays_pose_exact_lat(const bh::MarchArgs& a, const float* dirs, uint32_t shutter_log2,
+                hipStream_t s);
 // the shutter render's march: 2^ln cameras per output frame, a.n_frames cameras in all (ln in 1..4)
 BH_INTERNAL int bh_launch_shutter_exact(const bh::MarchArgs& a, uint32_t ln, hipStream_t s);
 BH_INTERNAL int bh_launch_shutter_exact_lat(const bh::MarchArgs& a, uint32_t ln, hipStream_t s);

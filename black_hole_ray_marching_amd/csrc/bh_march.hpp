@@ -102,6 +102,30 @@ __attribute__((visibility("hidden"))) inline int launch_rays(const MarchArgs& a,
         return (int)hipGetLastError();
     });
 }
+// The posed ray-map march (bh_render_frames_rays, bh_render_frames_shutter_rays, bh_render_lens_rays_posed; tile
+// schedule): any number of frames over one camera-space map; ln != 0: the shutter form, 2^ln cameras per output frame.
+template <bool FOLD_NONE>
+__attribute__((visibility("hidden"))) inline int launch_rays_pose(const MarchArgs& a, const float* dirs, uint32_t ln, hipStream_t s) {
+    if (!dirs || a.n_frames == 0u) return (int)hipErrorInvalidValue;
+    if (a.lens != 0u) {
+        if (ln != 0u || a.n_frames != 1u) return (int)hipErrorInvalidValue;
+        with_scene_fold<FOLD_NONE>(a.scene_flags, [&](auto sf) {
+            launch_tile_rays_schedule(march_tile_rays_pose_lens_kernel<decltype(sf)::value>, a, dirs, s);
+        });
+        return (int)hipGetLastError();
+    }
+    if (ln > shutter::MAX_LOG2 || (a.n_frames & ((1u << ln) - 1u)) != 0u) return (int)hipErrorInvalidValue;
+    return with_format(a.format, [&](auto fmt) {
+        constexpr uint32_t FMT = decltype(fmt)::value;
+        with_scene_fold<FOLD_NONE>(a.scene_flags, [&](auto sf) {
+            constexpr uint32_t SF = decltype(sf)::value;
+            if (ln != 0u) launch_shutter_rays_schedule<FMT, SF>(a, dirs, ln, s);
+            else if (a.ss_log2 != 0u) launch_tile_rays_schedule(march_tile_rays_pose_kernel<FMT, SF, true>, a, dirs, s);
+            else launch_tile_rays_schedule(march_tile_rays_pose_kernel<FMT, SF, false>, a, dirs, s);
+        });
+        return (int)hipGetLastError();
+    });
+}
 #endif
 // The shutter render's march (bh_render_shutter, n = 2^ln cameras per output frame; tile schedule): the same folds.
 template <bool FOLD_NONE>

@@ -44,16 +44,23 @@ __device__ __forceinline__ void select_outputs(MarchArgs& a, const FrameArgs& F)
 // RAYS (exact math, the march_tile_rays_*_kernel forms): the lane's direction is the caller's -- normalize_x of the 12
 // bytes of its pixel in the ray map `dirs` (bh_render_rays: row-major, the launch's width x height) -- instead of
 // pixel_ray's; c0..c2, rw2 and rh2 are not read.  A lane outside the frame loads nothing and takes (0, 0, 1).
+// POSE (with RAYS; the march_tile_rays_pose_*_kernel forms and march_tile_shutter_rays_kernel): the map is in camera
+// space and the frame's c0, c1, c2 hold its camera's basis rows r, u, f (bh_ray_pose): the loaded (mx, my, mz) becomes
+// (mx r + my u) + mz f, five roundings per component, before normalize_x.  The basis is wave-uniform and dead before
+// the loop; with POSE a ray map also feeds a shutter wave (SHUT), whose n waves read the same 12 bytes per pixel --
+// there without a branch: a lane outside the frame reads pixel (0, 0), inside any map, and still takes (0, 0, 1).
 struct ShutterLane { uint32_t px, py; bool valid, ok; };
 template <uint32_t FMT, uint32_t SF, bool SS = false, bool ITEM = false, bool LENS = false, bool SHUT = false,
-          bool RAYS = false>
+          bool RAYS = false, bool POSE = false>
 __device__ __forceinline__ void march_slot(const MarchArgs& A, uint32_t slot, const float* lut,
                                            uint32_t lane, uint32_t item_tx = 0u, uint32_t item_ty = 0u,
                                            ShutterLane* sl = nullptr, const float* dirs = nullptr) {
     static_assert(SS || !ITEM, "work items are supersampled tiles");
     static_assert(!LENS || (!SS && !BH_FAST), "a lens is one record per ray, in exact math");
     static_assert(!SHUT || (!SS && !ITEM && !LENS), "a shutter wave takes its ss from the argument");
-    static_assert(!RAYS || (!BH_FAST && !ITEM && !SHUT), "a ray map feeds the exact plain, supersampled and lens forms");
+    static_assert(!RAYS || (!BH_FAST && !ITEM && (!SHUT || POSE)),
+                  "a ray map feeds the exact plain, supersampled and lens forms, and posed the shutter form");
+    static_assert(!POSE || RAYS, "a pose turns a ray map");
     const uint32_t nf = A.n_frames;
     uint32_t fi = 0, j = slot;
     if constexpr (ITEM) {
@@ -92,9 +99,21 @@ __device__ __forceinline__ void march_slot(const MarchArgs& A, uint32_t slot, co
     if constexpr (RAYS) {
         // fs_main :362 with in.camera_to_vertex = the map's vector: any bit pattern, normalised as pixel_ray's is
         v3 d = mk(0.0f, 0.0f, 1.0f);
+        if constexpr (SHUT) {
+            // a shutter wave: no branch on the lane -- a lane outside the frame reads pixel (0, 0), always inside
+            // the map, and keeps (0, 0, 1)
+            const float* p = dirs + ((size_t)(valid ? py : 0u) * a.width + (valid ? px : 0u)) * 3u;
+            const v3 m = mk(p[0], p[1], p[2]);
+            const v3 t = add(add(smul(m.x, mk(a.c0[0], a.c0[1], a.c0[2])), smul(m.y, mk(a.c1[0], a.c1[1], a.c1[2]))),
+                             smul(m.z, mk(a.c2[0], a.c2[1], a.c2[2])));
+            d = sel(valid, t, d);
+        } else
         if (valid) {
             const float* p = dirs + ((size_t)py * a.width + px) * 3u;
             d = mk(p[0], p[1], p[2]);
+            if constexpr (POSE)  // bh_ray_pose (include/bh_render.h): (mx r + my u) + mz f, in this association
+                d = add(add(smul(d.x, mk(a.c0[0], a.c0[1], a.c0[2])), smul(d.y, mk(a.c1[0], a.c1[1], a.c1[2]))),
+                        smul(d.z, mk(a.c2[0], a.c2[1], a.c2[2])));
         }
         st.rd = normalize_x(d);
     } else
@@ -319,6 +338,66 @@ template <uint32_t SF>
 __global__ void __launch_bounds__(64 * WG_WAVES) march_tile_rays_lens_kernel(MarchArgs A, const float* dirs) {
     march_tile_rays_wave<BH_OUT_RGBA32F, SF, false, true>(A, nullptr, dirs);
 }
+
+// The posed ray-map forms (bh_render_frames_rays, bh_render_lens_rays_posed): the ray-map kernels over a map in camera
+// space, with march_slot's POSE switch and any number of frames -- frame fi's FrameArgs holds its camera's position
+// and basis (bh_ray_pose), every frame reads the one map.  A wave helper of their own: the unposed kernels keep the
+// machine code they were measured with.
+template <uint32_t FMT, uint32_t SF, bool SS, bool LENS>
+__device__ __forceinline__ void march_tile_rays_pose_wave(const MarchArgs& A, const float* lut, const float* dirs) {
+    const uint32_t slot = __builtin_amdgcn_readfirstlane(blockIdx.x * WG_WAVES + (threadIdx.x >> 6));
+    if (slot >= A.n_tiles * A.n_frames) return;  // wave-uniform
+    const bool probe = A.clk && ((slot + (slot >> 8)) & A.clk_mask) == 0u;  // as march_tile_wave
+    ClockStart c0{0u, 0u};
+    if (probe) c0 = clock_start();
+    march_slot<FMT, SF, SS, false, LENS, false, true, true>(A, slot, lut, threadIdx.x & 63u, 0u, 0u, nullptr, dirs);
+    if (probe) clock_end(A.clk, c0);
+}
+template <uint32_t FMT, uint32_t SF, bool SS>
+__global__ void __launch_bounds__(64 * WG_WAVES) march_tile_rays_pose_kernel(MarchArgs A, const float* dirs) {
+    __shared__ float lut[lds_tables<FMT>()];
+    load_srgb_tables<FMT, 64u * WG_WAVES>(A, lut);
+    __syncthreads();
+    march_tile_rays_pose_wave<FMT, SF, SS, false>(A, lut, dirs);
+}
+template <uint32_t SF>
+__global__ void __launch_bounds__(64 * WG_WAVES) march_tile_rays_pose_lens_kernel(MarchArgs A, const float* dirs) {
+    march_tile_rays_pose_wave<BH_OUT_RGBA32F, SF, false, true>(A, nullptr, dirs);
+}
+
+// The shutter form over a posed ray map (bh_render_frames_shutter_rays): march_tile_shutter_kernel, statement for
+// statement, with the map as the second argument and march_slot's RAYS and POSE switches -- the n waves of a
+// workgroup read the same 12 bytes per pixel and differ in their FrameArgs' pose.  Its barrier discipline is that
+// kernel's (the comment there): the map is loaded inside march_slot without a branch or a return of its own (a lane
+// outside the frame reads pixel (0, 0) and a select drops what it read), so nothing new stands between the barriers.
+template <uint32_t FMT, uint32_t SF>
+__global__ void __launch_bounds__(64u << shutter::MAX_LOG2) __attribute__((amdgpu_waves_per_eu(8)))
+march_tile_shutter_rays_kernel(MarchArgs A, const float* dirs, uint32_t ln) {
+    float* lut = reinterpret_cast<float*>(shutter_hist_lds() + (1u << ln));
+    const uint32_t nt = 64u << ln;
+    for (uint32_t i = threadIdx.x; i < (uint32_t)lds_tables<FMT>(); i += nt)
+        lut[i] = i < 256u ? A.srgb_lut[i] : A.srgb_enc[i - 256u];
+    __syncthreads();
+    const uint32_t n_out = A.n_frames >> ln;  // output frames
+    const uint32_t g = blockIdx.x;
+    if (g >= A.n_tiles * n_out) return;  // blockIdx and kernel arguments only: the whole workgroup or none of it
+    const uint32_t w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63u;
+    const uint32_t slot = shutter::wave_slot(g, w, n_out, ln);
+    const bool probe = A.clk && ((slot + (slot >> 8)) & A.clk_mask) == 0u;  // as march_tile_wave
+    ClockStart c0{0u, 0u};
+    if (probe) c0 = clock_start();
+    ShutterLane sl{0u, 0u, false, false};
+    march_slot<FMT, SF, false, false, false, true, true, true>(A, slot, lut, lane, 0u, 0u, &sl, dirs);
+    if (probe) clock_end(A.clk, c0);
+    __syncthreads();  // every wave of the workgroup, whatever its march did (march_tile_shutter_kernel)
+    if (!sl.ok || w > 1u) return;
+    const FrameArgs& F = A.frame_table ? A.frame_table[slot % A.n_frames] : A.frames[slot % A.n_frames];
+    void* out = w == 0u ? F.out_col : F.out_blackout;
+    if (!out) return;  // wave 1 of a frame without the second target: neither resolved nor written
+    const uint32_t lk = A.ss_log2;
+    if (sl.valid && ss::writer(lane, lk))
+        shutter_resolve_store<FMT>(out, w, ln, lane, ss::out_index(sl.px, sl.py, lk, A.ss_out_width), lut);
+}
 #endif
 
 // The adaptive render's second pass (bh_render_adaptive; bh_refine.hpp): the supersampled march over a work
@@ -404,6 +483,20 @@ inline void launch_shutter_schedule(const MarchArgs& a, uint32_t ln, hipStream_t
     }
     hipLaunchKernelGGL((march_tile_shutter_kernel<FMT, SF>), dim3(blocks), dim3(64u << ln), lds, s, a, ln);
 }
+#if !BH_FAST
+// ... the shutter form over a posed ray map: the same grid and LDS, the map as the second argument
+template <uint32_t FMT, uint32_t SF>
+inline void launch_shutter_rays_schedule(const MarchArgs& a, const float* dirs, uint32_t ln, hipStream_t s) {
+    const uint32_t blocks = a.n_tiles * (a.n_frames >> ln), lds = shutter_lds_bytes<FMT>(ln);
+    if (lds > 64u * 1024u) {  // as launch_shutter_schedule: once per kernel
+        static const hipError_t raised = hipFuncSetAttribute(reinterpret_cast<const void*>(&march_tile_shutter_rays_kernel<FMT, SF>),
+                                                              hipFuncAttributeMaxDynamicSharedMemorySize,
+                                                              (int)shutter_lds_bytes<FMT>(shutter::MAX_LOG2));
+        (void)raised;
+    }
+    hipLaunchKernelGGL((march_tile_shutter_rays_kernel<FMT, SF>), dim3(blocks), dim3(64u << ln), lds, s, a, dirs, ln);
+}
+#endif
 // ... and the adaptive render's work-list march: `waves` resident waves that pull (march_refine_kernel)
 template <uint32_t FMT, uint32_t SF>
 inline void launch_refine_schedule(const MarchArgs& a, const RefineArgs& r, uint32_t waves, hipStream_t s) {

@@ -12,6 +12,24 @@
 
 extern "C" {
 
+// The posed ray-map kernels' turn of a map's vector on the host (march_slot's POSE form, bh_march_tile.hpp):
+// (mx r + my u) + mz f per component, one statement per operation -- this unit is built without contraction.
+int bh_ray_pose_apply_host(const bh_ray_pose* pose, const float* dirs, uint32_t width, uint32_t height, float* out) {
+    if (!pose || !dirs || !out || width == 0 || height == 0 || width > 65536u || height > 65536u) return bad_arg(__func__, __LINE__);
+    const size_t n = (size_t)width * height;
+    for (size_t i = 0; i < n; ++i) {
+        const float mx = dirs[3u * i], my = dirs[3u * i + 1u], mz = dirs[3u * i + 2u];
+        for (int k = 0; k < 3; ++k) {
+            const float a = mx * pose->r[k];
+            const float b = my * pose->u[k];
+            const float ab = a + b;
+            const float c = mz * pose->f[k];
+            out[3u * i + (size_t)k] = ab + c;
+        }
+    }
+    return BH_OK;
+}
+
 // The supersampled march kernel's epilogue on the host: the functions of bh_ss.hpp that each lane of a wave
 // runs (ss_resolve_store, bh_march_resolve.hpp), run here wave by wave over 64-entry arrays -- one 8x8 tile of the
 // virtual frame per wave, invalid lanes 0, every lane taking each butterfly level together.

@@ -136,4 +136,51 @@ def cube_face(N: int, face: str, forward=(0.0, 0.0, 1.0), up=(0.0, 1.0, 0.0)) ->
     return _compose(x, y, z, r, u, f)
 
 
-__all__ = ["FACES", "basis", "pinhole", "perspective", "equirect", "fisheye", "cube_face"]
+def pose(pos, forward=(0.0, 0.0, 1.0), up=(0.0, 1.0, 0.0)) -> _abi.bh_ray_pose:
+    """A camera for a map in camera space (bh_ray_pose; Scene.render_frames_rays): the position and the rows
+    (r, u, f) of `basis(forward, up)`, each rounded once to float32.  A map built with the default forward and up
+    (its x along r, y along u, z along f) and turned by this pose looks along `forward`."""
+    try:
+        p = np.asarray(pos, np.float64).reshape(3)
+    except (TypeError, ValueError):
+        raise BhError(_abi.BH_ERR_INVALID_ARG, f"raymap: pos must be three numbers, got {pos!r}")
+    r, u, f = basis(forward, up)
+    out = _abi.bh_ray_pose()
+    for name, v in (("pos", p), ("r", r), ("u", u), ("f", f)):
+        setattr(out, name, (C.c_float * 3)(*np.asarray(v, np.float32).tolist()))
+    return out
+
+
+def pose_of(camera) -> _abi.bh_ray_pose:
+    """pose() of a scene camera (its pos, dir and up; a Camera or anything with those three attributes)."""
+    try:
+        return pose(camera.pos, camera.dir, camera.up)
+    except AttributeError:
+        raise BhError(_abi.BH_ERR_INVALID_ARG, f"raymap: pose_of takes a camera with pos, dir and up, got {type(camera).__name__}")
+
+
+def pose_rows(p) -> np.ndarray:
+    """The 12 floats of a pose as a (4, 3) float32 array: pos, r, u, f."""
+    return np.frombuffer(bytes(p), np.float32).reshape(4, 3).copy()
+
+
+def apply_pose(p, dirs) -> np.ndarray:
+    """bh_ray_pose_apply_host: the camera-space map `dirs` (H, W, 3) turned by pose `p` -- (mx r + my u) + mz f per
+    pixel, in the kernels' fp32 operations -- the world-space map whose render_rays from the pose's position is the
+    posed render, bit for bit."""
+    d = np.ascontiguousarray(dirs, dtype=np.float32)
+    if d.ndim != 3 or d.shape[2] != 3:
+        raise BhError(_abi.BH_ERR_INVALID_ARG, f"raymap: dirs must be (H, W, 3), got {d.shape}")
+    if not isinstance(p, _abi.bh_ray_pose):
+        rows = np.ascontiguousarray(p, dtype=np.float32)
+        if rows.shape != (4, 3):
+            raise BhError(_abi.BH_ERR_INVALID_ARG, "raymap: a pose is a raymap.pose or four rows of three floats (pos, r, u, f)")
+        p = _abi.bh_ray_pose.from_buffer_copy(rows.tobytes())
+    H, W = _size(d.shape[1], d.shape[0])[::-1]
+    out = np.empty((H, W, 3), np.float32)
+    check(load().bh_ray_pose_apply_host(C.byref(p), d.ctypes.data, W, H, out.ctypes.data), "bh_ray_pose_apply_host")
+    return out
+
+
+__all__ = ["FACES", "basis", "pinhole", "perspective", "equirect", "fisheye", "cube_face", "pose", "pose_of",
+           "pose_rows", "apply_pose"]

@@ -373,6 +373,32 @@ def _pos_arg(pos, what: str):
     return (C.c_float * 3)(*p)
 
 
+def _poses_arg(poses, n: int, what: str):
+    """n poses as the C ABI takes them: each a _abi.bh_ray_pose (raymap.pose, raymap.pose_of) or four rows of three
+    floats (pos, r, u, f)."""
+    try:
+        ps = list(poses)
+    except TypeError:
+        ps = None
+    if ps is None or not 1 <= n <= _abi.BH_MAX_FRAMES or len(ps) != n:
+        raise BhError(_abi.BH_ERR_INVALID_ARG, f"{what}: poses must hold one pose per camera (1..{_abi.BH_MAX_FRAMES}), "
+                                               f"{n} here")
+    out = (_abi.bh_ray_pose * n)()
+    for i, p in enumerate(ps):
+        if isinstance(p, _abi.bh_ray_pose):
+            out[i] = p
+            continue
+        try:
+            rows = np.ascontiguousarray(p, dtype=np.float32)
+        except (TypeError, ValueError):
+            rows = np.zeros(0, np.float32)
+        if rows.shape != (4, 3):
+            raise BhError(_abi.BH_ERR_INVALID_ARG, f"{what}: pose {i} must be a raymap.pose or four rows of three floats "
+                                                   "(pos, r, u, f)")
+        C.memmove(C.byref(out[i]), rows.ctypes.data, 48)
+    return out
+
+
 class FrameBatch:
     """A prepared bh_render_frames call (Scene.prepare_frames): its targets stay referenced, so the
     device pointers in its descriptors stay valid while the batch lives."""
@@ -615,13 +641,68 @@ class Scene:
         check(self.lib.bh_render_rays(self._ctx, p, C.byref(self.uniforms.to_c()), C.byref(d), _ptr(dirs), k,
                                       _stream_handle(stream)), "bh_render_rays")
 
+    def render_frames_rays(self, dirs, outputs, blackout_outputs=None, *, poses, fmt: int = BH_OUT_RGBA32F,
+                           ss: int = 1, stream=None, schedule: int = 0, dbg_n_rk=None, dbg_fate=None,
+                           width: int | None = None, height: int | None = None) -> None:
+        """bh_render_frames_rays: render_frames over one ray map in CAMERA space -- frame i is render_rays of the map
+        turned by poses[i] (raymap.pose / raymap.pose_of; include/bh_render.h, bh_ray_pose) from its position, into
+        outputs[i] / blackout_outputs[i].  `dirs` as render_rays takes it, shared by every frame; up to
+        BH_MAX_FRAMES frames; dbg_n_rk / dbg_fate: per-frame lists (ss == 1)."""
+        what = "render_frames_rays"
+        k = _ss_arg(ss)
+        n = len(outputs)
+        per = lambda v: v if v is not None else [None] * n  # noqa: E731
+        bos, nrks, fates = per(blackout_outputs), per(dbg_n_rk), per(dbg_fate)
+        if not (len(bos) == len(nrks) == len(fates) == n):
+            raise BhError(_abi.BH_ERR_INVALID_ARG, f"{what}: per-frame lists must have one entry per frame")
+        ps = _poses_arg(poses, n, what)
+        descs = (_abi.bh_render_desc * n)(*[self._desc(outputs[i], bos[i], fmt, nrks[i], fates[i], BH_MATH_EXACT,
+                                                       BH_LAYOUT_ROWMAJOR, 0, 1, width, height, schedule, None)
+                                            for i in range(n)])
+        _check_dirs(dirs, descs[0].height * k, descs[0].width * k, what)
+        check(self.lib.bh_render_frames_rays(self._ctx, n, ps, C.byref(self.uniforms.to_c()), descs, _ptr(dirs), k,
+                                             _stream_handle(stream)), "bh_render_frames_rays")
+
+    def render_shutter_rays(self, dirs, output, blackout_output=None, *, poses, fmt: int = BH_OUT_RGBA32F,
+                            ss: int = 1, stream=None, schedule: int = 0, width: int | None = None,
+                            height: int | None = None) -> None:
+        """bh_render_frames_shutter_rays of one frame: render_shutter over the camera-space map `dirs`, the
+        exposure's sub-frame cameras given as `poses` (n in {1, 2, 4, 8, 16})."""
+        self.render_frames_shutter_rays(dirs, [output], None if blackout_output is None else [blackout_output],
+                                        poses=[poses], fmt=fmt, ss=ss, stream=stream, schedule=schedule, width=width,
+                                        height=height)
+
+    def render_frames_shutter_rays(self, dirs, outputs, blackout_outputs=None, *, poses, fmt: int = BH_OUT_RGBA32F,
+                                   ss: int = 1, stream=None, schedule: int = 0, width: int | None = None,
+                                   height: int | None = None) -> None:
+        """bh_render_frames_shutter_rays: several shutter frames over one camera-space map in one launch; `poses` is
+        a list of n-lists, one per output frame, all of one length n, with len(outputs) * n at most BH_MAX_FRAMES."""
+        what = "render_frames_shutter_rays"
+        k = _ss_arg(ss)
+        n = len(outputs)
+        if n < 1 or len(poses) != n or not len(poses[0]) or any(len(g) != len(poses[0]) for g in poses):
+            raise BhError(_abi.BH_ERR_INVALID_ARG, f"{what}: one list of n poses per output frame")
+        n_sub = len(poses[0])
+        bos = blackout_outputs if blackout_outputs is not None else [None] * n
+        if len(bos) != n:
+            raise BhError(_abi.BH_ERR_INVALID_ARG, f"{what}: per-frame lists must have one entry per frame")
+        ps = _poses_arg([p for g in poses for p in g], n * n_sub, what)
+        descs = (_abi.bh_render_desc * n)(*[self._desc(outputs[i], bos[i], fmt, None, None, BH_MATH_EXACT,
+                                                       BH_LAYOUT_ROWMAJOR, 0, 1, width, height, schedule, None)
+                                            for i in range(n)])
+        _check_dirs(dirs, descs[0].height * k, descs[0].width * k, what)
+        check(self.lib.bh_render_frames_shutter_rays(self._ctx, n, n_sub, ps, C.byref(self.uniforms.to_c()), descs,
+                                                     _ptr(dirs), k, _stream_handle(stream)),
+              "bh_render_frames_shutter_rays")
+
     def render_lens(self, lens, *, width: int | None = None, height: int | None = None, schedule: int = 0,
-                    stream=None, dirs=None, pos=None) -> None:
+                    stream=None, dirs=None, pos=None, pose=None) -> None:
         """bh_render_lens: march this scene's camera once into `lens`, a device buffer of height x width records
         (u, v) of 8 bytes (e.g. a float32 tensor (H, W, 2)) -- the view, without any sky.  Exact math, whatever
         the scene's math mode.  Shade it with shade(), as often and with as many skies as wanted.
         `dirs` (a ray map as render_rays takes it, (height, width, 3)): bh_render_lens_rays, the view of that map
-        from `pos` (default: the scene camera's position)."""
+        from `pos` (default: the scene camera's position); with `pose` (raymap.pose) instead of `pos`,
+        bh_render_lens_rays_posed: the view of the camera-space map `dirs` turned by that pose."""
         d = _abi.bh_render_desc()
         d.width, d.height = width or self.width, height or self.height
         d.max_iters, d.scene_flags = self.max_iters, self.scene_flags
@@ -629,6 +710,15 @@ class Scene:
         if lens is None:
             raise BhError(_abi.BH_ERR_INVALID_ARG, "render_lens: lens is required")
         _check_size(lens, d.width * d.height * 8, "lens", "render_lens")
+        if pose is not None:
+            if pos is not None:
+                raise BhError(_abi.BH_ERR_INVALID_ARG, "render_lens: give pos or pose, not both (a pose holds its position)")
+            _check_dirs(dirs, d.height, d.width, "render_lens")
+            ps = _poses_arg([pose], 1, "render_lens")
+            check(self.lib.bh_render_lens_rays_posed(self._ctx, ps, C.byref(self.uniforms.to_c()), C.byref(d),
+                                                     _ptr(dirs), _ptr(lens), _stream_handle(stream)),
+                  "bh_render_lens_rays_posed")
+            return
         if dirs is not None:
             _check_dirs(dirs, d.height, d.width, "render_lens")
             p = _pos_arg(self.camera_uniform.pos if pos is None else pos, "render_lens")

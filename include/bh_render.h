@@ -523,8 +523,9 @@ int bh_lens_shade_mip_host(const bh_lens_px* lens, uint32_t width, uint32_t heig
  * map is an input like the sky's bytes: how the caller made it is outside parity.  A vector whose normalisation is
  * not finite (the zero vector, an inf, a NaN) renders what the WGSL gives that normalised direction; a kernel reads
  * the 12 bytes of its own pixel and nothing else of the map, whatever they hold.  One origin per frame: `pos`.
- * Exact math only.  Not built for ray maps: several frames per call, shutter and adaptive renders, the tiled
- * layouts, shards and partitions, fast math.
+ * Exact math only.  Several frames per call, a moving camera and shutter renders over one map: the posed forms
+ * below (bh_ray_pose).  Not built for ray maps: adaptive renders, the tiled layouts, shards and partitions, fast
+ * math, a per-ray origin.
  *
  * bh_render_rays: bh_render (ss == 1; the dbg_* outputs are allowed) or bh_render_ss (ss = k in {2, 4, 8}: `dirs_dev`
  * is the map of the virtual frame, k*height x k*width x 3, its samples resolved by bh_render_ss's normative tree and
@@ -552,6 +553,45 @@ int bh_render_lens_rays(bh_ctx* ctx, const float pos[3], const bh_uniforms* unif
  * "pinhole plus distortion" map.  BH_ERR_INVALID_ARG: a NULL pointer, a side of 0 or above 65536;
  * BH_ERR_UNSUPPORTED: a non-default screen triangle. */
 int bh_ray_map_pinhole_host(const bh_camera_uniform* camera, uint32_t width, uint32_t height, float* out_dirs);
+
+/* Posed ray maps: one map in CAMERA space, one pose per camera -- a camera path, several frames per launch and a
+ * shutter through any projection without a new map per frame.  A pose (normative) is a position and three rows: */
+typedef struct { float pos[3]; float r[3], u[3], f[3]; } bh_ray_pose;   /* 48 bytes */
+/* Pixel (x, y) of camera i is fs_main with camera.pos = pose[i].pos and, with (mx, my, mz) = dirs[y][x],
+ *     in.camera_to_vertex[c] = (mx * r[c] + my * u[c]) + mz * f[c]        (c = 0, 1, 2)
+ * -- five fp32 operations per component, each rounded once, no contraction, in exactly this association -- and
+ * then what bh_render_rays does with a map's vector: normalize_x, the ray's constant, the shared march.  The nine
+ * basis floats are any values: nothing requires them to be orthonormal, so a mirror, a shear or a scale is a pose.
+ * A non-finite product (inf * 0) gives what IEEE gives, and from there bh_render_rays' rule for non-finite vectors
+ * applies.  A pose of unit axes (r, u, f = x, y, z) is NOT promised bit-equal to bh_render_rays of the same map for
+ * vectors that hold a -0 or a non-finite component: x + (-0) is x only when x is not +0 ((+0) + (-0) = +0, so a -0
+ * component can come out +0 after the sum with the other two products), and inf * 0 is NaN, so an infinite
+ * component makes the other two components NaN.  Every finite vector without a -0 renders bh_render_rays' bytes.
+ *
+ * bh_render_frames_rays: bh_render_frames (ss == 1; the dbg_* outputs are allowed) or bh_render_frames_ss (ss = k in
+ * {2, 4, 8}; dbg_* refused) with one shared map -- of the virtual frame when ss > 1 -- and one pose per frame:
+ * n_frames in 1..BH_MAX_FRAMES (the inline table up to 32 frames, the stream's device table above), the three
+ * formats, one or two targets.  bh_render_frames_shutter_rays: bh_render_frames_shutter over the map --
+ * n_frames * n_sub poses, those of output frame f at poses[f * n_sub ..], n_sub in {2, 4, 8, 16} resolved by that
+ * call's normative tree; n_sub == 1 is bh_render_frames_rays (a shutter kernel's lanes beyond the frame's right or
+ * bottom edge read the map's pixel (0, 0) and drop it: reads stay inside the map).  bh_render_lens_rays_posed:
+ * bh_render_lens_rays with a pose.  Refusals: those of bh_render_rays (a NULL or misaligned dirs_dev, math, layout, shards, partition, base
+ * schedule, and what the outputs' form refuses) and of bh_render_frames(_shutter) (the frame and camera counts, descs
+ * that differ in more than their outputs), with `poses` NULL as `pos` NULL; BH_ERR_UNSUPPORTED comes with a sentence
+ * in bh_last_error() that starts with the function's name.  A refused call launches nothing and writes nothing.
+ * Graph contract, temporal order: bh_render_rays' -- a posed launch is a ray-map launch of its geometry and stream
+ * (it shares that state with bh_render_rays), and the map's address and every pose enter the repeated-frame key. */
+int bh_render_frames_rays(bh_ctx* ctx, uint32_t n_frames, const bh_ray_pose* poses, const bh_uniforms* uniforms,
+                          const bh_render_desc* descs, const float* dirs_dev, uint32_t ss, void* hip_stream);
+int bh_render_frames_shutter_rays(bh_ctx* ctx, uint32_t n_frames, uint32_t n_sub, const bh_ray_pose* poses,
+                                  const bh_uniforms* uniforms, const bh_render_desc* descs, const float* dirs_dev,
+                                  uint32_t ss, void* hip_stream);
+int bh_render_lens_rays_posed(bh_ctx* ctx, const bh_ray_pose* pose, const bh_uniforms* uniforms,
+                              const bh_render_desc* desc, const float* dirs_dev, bh_lens_px* out_lens, void* hip_stream);
+/* Host only: the formula above in plain C++ over a host map (height * width * 3 floats) into out_dirs (the same
+ * size; may be `dirs` itself) -- the world-space map whose bh_render_rays, from pose->pos, is the posed render of
+ * `dirs`, bit for bit.  BH_ERR_INVALID_ARG: a NULL pointer, a side of 0 or above 65536. */
+int bh_ray_pose_apply_host(const bh_ray_pose* pose, const float* dirs, uint32_t width, uint32_t height, float* out_dirs);
 
 /* Bloom::render (src/bloom.rs:53-71): the reference's Kawase bloom + remix chain over the scene's two
  * targets, on BGRA8-sRGB images (bh_render with BH_OUT_BGRA8_SRGB): `col` (full_image_input),

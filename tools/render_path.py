@@ -17,8 +17,10 @@ A moving sky behind a still camera instead: one frame per image in DIR, the view
 The sky filtered through its mip chain: per frame a lens render and a filtered shade (bh_shade_lens_mip).
 
     python tools/render_path.py --projection equirect --ss 2 --width 2048 --height 1024
-Another projection than the reference's pinhole: every frame marches a ray map (bh_render_rays) -- a 360-degree
-equirectangular frame, a fisheye:DEG dome frame, a perspective:DEG lens of another field of view."""
+Another projection than the reference's pinhole: the frames march one ray map in camera space, uploaded once, each
+with its camera's pose (bh_render_frames_rays, several frames per launch) -- a 360-degree equirectangular frame, a
+fisheye:DEG dome frame, a perspective:DEG lens of another field of view.  With --shutter N every frame averages N
+sub-frame poses over the same map (bh_render_frames_shutter_rays)."""
 import argparse
 import dataclasses
 import json
@@ -56,10 +58,11 @@ p.add_argument("--sky-filter", choices=["none", "mip"], default="none",
                help="mip: every frame is a lens render (bh_render_lens) shaded through the sky's mip chain, the level "
                     "taken from the lens (bh_shade_lens_mip); with --ss 1, 2 or 4 and with --sky-frames")
 p.add_argument("--projection", default=None, metavar="{pinhole,equirect,fisheye:DEG,perspective:DEG}",
-               help="march a ray map instead of the camera's own rays (bh_render_rays): the map of the (ss x) frame "
-                    "is built once in the camera's frame and turned with the camera per frame; pinhole is the "
-                    "camera's own projection through the map (the same bytes); DEG: the full field of view of a "
-                    "fisheye (up to 360), the vertical one of a perspective lens (below 180)")
+               help="march a ray map instead of the camera's own rays: the map of the (ss x) frame is built and uploaded "
+                    "once, in the camera's frame, and every frame passes its camera's pose (bh_render_frames_rays; "
+                    "with --shutter, bh_render_frames_shutter_rays); pinhole is the camera's own projection through a "
+                    "per-frame map of the library's helper (bh_render_rays: the same bytes); DEG: the full field of "
+                    "view of a fisheye (up to 360), the vertical one of a perspective lens (below 180)")
 args = p.parse_args()
 mip = args.sky_filter == "mip"
 proj, proj_deg = None, None
@@ -73,9 +76,11 @@ if args.projection is not None:
         p.error(f"--projection {proj}:DEG needs a number of degrees, got {deg!r}")
     if proj_deg is not None and not 0.0 < proj_deg <= (360.0 if proj == "fisheye" else 179.9):
         p.error(f"--projection {proj}: DEG must lie in (0, {360 if proj == 'fisheye' else 179.9}]")
-    if args.shutter > 1 or args.adaptive is not None:
-        sys.exit("render_path: --projection does not combine with --shutter or --adaptive (ray maps are not built for "
-                 "shutter or adaptive renders)")
+    if args.adaptive is not None:
+        sys.exit("render_path: --projection does not combine with --adaptive (ray maps are not built for adaptive renders)")
+    if args.shutter > 1 and proj == "pinhole":
+        sys.exit("render_path: --projection pinhole does not combine with --shutter (its map is per camera; the plain "
+                 "--shutter is the same picture)")
 if mip and (args.shutter > 1 or args.adaptive is not None):
     sys.exit("render_path: --sky-filter mip does not combine with --shutter or --adaptive (the filter is a lens shade)")
 if mip and args.ss == 8:
@@ -111,7 +116,7 @@ surf = torch.empty_like(col)
 log = []
 
 
-def shutter_cameras(frame_cam):
+def shutter_subcameras(frame_cam):
     """The N sub-frame cameras of a frame: a copy of the controller's state moves a copy of the frame's camera
     by dt * S * t / N (t = 0: the frame's own camera); the path itself is untouched."""
     out = []
@@ -119,30 +124,47 @@ def shutter_cameras(frame_cam):
         c2 = bh.CameraController()
         c2.c = type(ctrl.c).from_buffer_copy(ctrl.c)
         sub, _ = c2.update_camera(dataclasses.replace(frame_cam), args.dt * args.shutter_frac * t / args.shutter)
+        out.append(sub)
+    return out
+
+
+def shutter_cameras(frame_cam):
+    """... as the CameraUniforms bh_render_shutter takes."""
+    out = []
+    for sub in shutter_subcameras(frame_cam):
         cu = bh.CameraUniform()
         cu.update(sub)
         out.append(cu)
     return out
 
 
-local_map = None
+local_map, map_uploads = None, 0
 if proj in ("equirect", "fisheye", "perspective"):  # once per frame size, in the camera's own frame (r, u, f)
     kw, kh = args.ss * W, args.ss * H
     m = (raymap.equirect(kw, kh) if proj == "equirect" else raymap.fisheye(kw, kh, np.radians(proj_deg))
          if proj == "fisheye" else raymap.perspective(kw, kh, np.radians(proj_deg)))
-    local_map = torch.from_numpy(m).cuda()
+    local_map = torch.from_numpy(m).cuda()  # the run's only map: every frame passes a pose with it
+    map_uploads += 1
 
 
-def ray_map(frame_cam):
-    """The frame's map in world space: the local map turned into the camera's frame (a product on the device), or
-    -- pinhole -- the camera's own map from the library's helper."""
-    if local_map is None:
-        cu = bh.CameraUniform()
-        cu.update(frame_cam)
-        return torch.from_numpy(raymap.pinhole(cu, args.ss * W, args.ss * H)).cuda()
-    r, u, f = raymap.basis(frame_cam.dir, frame_cam.up)
-    turn = torch.from_numpy(np.stack([r, u, f]).astype(np.float32)).cuda()
-    return (local_map.reshape(-1, 3) @ turn).reshape(local_map.shape).contiguous()
+def pinhole_map(frame_cam):
+    """--projection pinhole: the camera's own map in world space, from the library's helper, per frame."""
+    global map_uploads
+    cu = bh.CameraUniform()
+    cu.update(frame_cam)
+    map_uploads += 1
+    return torch.from_numpy(raymap.pinhole(cu, args.ss * W, args.ss * H)).cuda()
+
+
+def lens_of(lens, frame_cam):
+    """The frame's view into `lens`: the camera's own rays, its pinhole map, or the local map under its pose."""
+    k = args.ss
+    if not proj:
+        scene.render_lens(lens, width=k * W, height=k * H)
+    elif local_map is None:
+        scene.render_lens(lens, width=k * W, height=k * H, dirs=pinhole_map(frame_cam))
+    else:
+        scene.render_lens(lens, width=k * W, height=k * H, dirs=local_map, pose=raymap.pose_of(frame_cam))
 
 
 t0 = time.perf_counter()
@@ -153,7 +175,7 @@ if args.sky_frames:
     k = args.ss
     scene.update(cam)
     lens = torch.empty((k * H, k * W, 2), dtype=torch.float32, device="cuda")
-    scene.render_lens(lens, width=k * W, height=k * H, dirs=ray_map(cam) if proj else None)  # the only march of the run
+    lens_of(lens, cam)  # the only march of the run
     for f, path in enumerate(images):
         frame_sky = bh.Sky(scene, bh.load_sky(path), mips=mip)
         scene.shade(lens, col, bo, fmt=bh.BH_OUT_BGRA8_SRGB, sky=frame_sky, ss=k, mip=mip)
@@ -167,16 +189,40 @@ if args.sky_frames:
 if mip and not args.sky_frames:  # the path's own sky with its chain, and the lens every frame marches into
     path_sky = bh.Sky(scene, sky, mips=True)
     path_lens = torch.empty((args.ss * H, args.ss * W, 2), dtype=torch.float32, device="cuda")
-for f in range(0 if args.sky_frames else args.frames):
+# a projection's frames in batches: one launch marches the batch's frames (with --shutter: their sub-frame poses)
+posed = local_map is not None and not mip and not args.sky_frames
+batch = max(1, min(8, 256 // args.shutter))
+targets = [(torch.empty_like(col), torch.empty_like(bo)) for _ in range(min(batch, args.frames))] if posed else []
+f0 = 0
+while posed and f0 < args.frames:
+    nb = min(batch, args.frames - f0)
+    poses = []
+    for f in range(f0, f0 + nb):
+        for k, a, b in keys:
+            ctrl.process_key(k, a <= f <= b)
+        cam, moved = ctrl.update_camera(cam, args.dt)
+        poses.append([raymap.pose_of(c) for c in (shutter_subcameras(cam) if args.shutter > 1 else [cam])])
+        log.append({"frame": f, "pos": cam.pos, "dir": cam.dir, "moved": moved})
+    cols, bos = [t[0] for t in targets[:nb]], [t[1] for t in targets[:nb]]
+    if args.shutter > 1:
+        scene.render_frames_shutter_rays(local_map, cols, bos, poses=poses, fmt=bh.BH_OUT_BGRA8_SRGB, ss=args.ss)
+    else:
+        scene.render_frames_rays(local_map, cols, bos, poses=[g[0] for g in poses], fmt=bh.BH_OUT_BGRA8_SRGB, ss=args.ss)
+    for i in range(nb):
+        scene.bloom(cols[i], bos[i], surf)
+        if not args.no_png:
+            write_png(out_dir / f"frame_{f0 + i:04d}.png", surf.cpu().numpy())
+    f0 += nb
+for f in range(0 if args.sky_frames or posed else args.frames):
     for k, a, b in keys:
         ctrl.process_key(k, a <= f <= b)
     cam, moved = ctrl.update_camera(cam, args.dt)
     scene.update(cam)
     if mip:
-        scene.render_lens(path_lens, width=args.ss * W, height=args.ss * H, dirs=ray_map(cam) if proj else None)
+        lens_of(path_lens, cam)
         scene.shade(path_lens, col, bo, fmt=bh.BH_OUT_BGRA8_SRGB, sky=path_sky, ss=args.ss, mip=True)
     elif proj:
-        scene.render_rays(ray_map(cam), col, bo, fmt=bh.BH_OUT_BGRA8_SRGB, ss=args.ss)
+        scene.render_rays(pinhole_map(cam), col, bo, fmt=bh.BH_OUT_BGRA8_SRGB, ss=args.ss)  # pinhole (the others: above)
     elif args.shutter > 1:
         scene.render_shutter(col, bo, cameras=shutter_cameras(cam), fmt=bh.BH_OUT_BGRA8_SRGB, ss=args.ss)
     else:
@@ -188,5 +234,5 @@ for f in range(0 if args.sky_frames else args.frames):
 torch.cuda.synchronize()
 dt = time.perf_counter() - t0
 (out_dir / "path.json").write_text(json.dumps(log, indent=0))
-print(json.dumps({"frames": args.frames, "width": W, "height": H, "ss": args.ss, "adaptive": args.adaptive, "shutter": args.shutter, "sky_filter": args.sky_filter, "projection": args.projection, "seconds": round(dt, 3),
+print(json.dumps({"frames": args.frames, "width": W, "height": H, "ss": args.ss, "adaptive": args.adaptive, "shutter": args.shutter, "sky_filter": args.sky_filter, "projection": args.projection, "map_uploads": map_uploads, "seconds": round(dt, 3),
                   "frames_per_s_incl_png": round(args.frames / dt, 2), "out": str(out_dir)}))
