@@ -96,12 +96,25 @@ struct MarchArgs {
     // frames of one launch (bh_render_frames): wave slot s marches frame s % n_frames, tile s / n_frames;
     // up to BH_INLINE_FRAMES of them inline, more from a device table (frame_table, else null)
     uint32_t n_frames;
+    // slot / n_frames as a multiply-high (div_magic below; 0: none, the wave divides).  In what was the padding
+    // in front of the pointer; tx_magic, for tile / tiles_x of an unsharded launch, in the padding behind clk_mask
+    uint32_t nf_magic;
     const FrameArgs* frame_table;
     // shader-clock probe (bh_set_clock_probe): per-XCD accumulators, sampled slots: (slot + slot / 256) & clk_mask == 0
     unsigned long long* clk;
     uint32_t clk_mask;
+    uint32_t tx_magic;
     FrameArgs frames[BH_INLINE_FRAMES];
 };
+// The multiply-high form of a wave-uniform division by a launch constant: m with (n * m) >> 32 == n / d for every
+// n <= n_max, or 0 when no 32-bit m does that.  m = floor(2^32 / d) + 1 overshoots 2^32 / d by e / (d 2^32) with
+// e = m d - 2^32 in [1, d], so n m / 2^32 = n / d + n e / (d 2^32): the floor is n / d's as long as the excess stays
+// under 1 / d, the least distance from n / d up to the next integer, that is n e < 2^32.  d = 1 has no such m.
+inline uint32_t div_magic(uint32_t d, uint32_t n_max) {
+    if (d < 2u) return 0u;
+    const uint64_t m = (1ull << 32) / d + 1u, e = m * d - (1ull << 32);
+    return (uint64_t)n_max * e < (1ull << 32) ? (uint32_t)m : 0u;
+}
 // passed by value: the kernel argument segment holds at most 4 KiB (with the persistent kernel's
 // extra pointer)
 static_assert(sizeof(MarchArgs) + 8 <= 4096, "MarchArgs must fit the kernel argument segment");

@@ -171,6 +171,16 @@ int bh_srgb_encode_table(float* out257) {
     return BH_OK;
 }
 
+int64_t bh_div_magic_misses(uint32_t d, uint32_t n_max, uint32_t* magic) {
+    if (d == 0u || !magic) return bad_arg(__func__, __LINE__);
+    const uint32_t m = *magic = bh::div_magic(d, n_max);
+    if (m == 0u) return 0;
+    int64_t misses = 0;
+    uint32_t n = 0;
+    do misses += (uint32_t)(((uint64_t)n * m) >> 32) != n / d; while (n++ != n_max);
+    return misses;
+}
+
 }  // extern "C"
 
 // One of the context's device tables: allocated and, with `src`, filled.  A failure is labelled hipMalloc(what) or
@@ -583,6 +593,11 @@ static void fill_args(const bh_ctx* c, uint32_t n_frames, const bh_camera_unifor
     a.rw2 = 1.0f / (2.0f * (float)a.width);
     a.rh2 = 1.0f / (2.0f * (float)a.height);
     a.n_frames = n_frames;
+    // the waves' two divisions by launch constants (bh_march_tile.hpp, slot_head): a slot by the frames, a tile
+    // by the tiles of a row; the largest dividend of each is known here
+    const uint64_t slots = L->n_tiles * n_frames;
+    a.nf_magic = slots - 1u <= 0xFFFFFFFFull ? bh::div_magic(n_frames, (uint32_t)(slots - 1u)) : 0u;
+    a.tx_magic = a.shard_count == 1u && a.n_tiles != 0u ? bh::div_magic(a.tiles_x, a.n_tiles - 1u) : 0u;
     a.clk = c->clk;
     a.clk_mask = c->clk_mask;
     if (n_frames > bh::BH_INLINE_FRAMES) L->table.resize(n_frames);

@@ -16,16 +16,80 @@ namespace BH_NS {
 // the centre-out permutation; each wave records its tile's max n_rk for the next frame's order.
 // wave_max_u32: bh_common.hpp
 
-// The per-frame fields of frame f of a multi-frame launch: its camera (read before and in the march
-// loop) and its outputs (read after it).
-__device__ __forceinline__ void select_camera(MarchArgs& a, const FrameArgs& F) {
+// The per-frame fields of frame fi of a launch: its camera (read before and in the march loop) and its outputs
+// (read after it).  frames[0] == the top-level fields for a one-frame launch; launches of more than
+// BH_INLINE_FRAMES frames read them from the device table.  Either way the frame's record is read through the
+// constant address space -- the kernel argument lives there, and the table was staged on the stream before this
+// launch -- at a wave-uniform index: scalar loads into SGPRs (one flat pointer chosen per wave made them vector
+// loads into 15 VGPRs, three of which -- cps -- stayed live through every step of the loop).
+#define BH_CONST_AS __attribute__((address_space(4)))
+template <class T>
+__device__ __forceinline__ const BH_CONST_AS T* const_as(const T* p) { return (const BH_CONST_AS T*)p; }
+__device__ __forceinline__ const BH_CONST_AS FrameArgs* frame_args_of(const MarchArgs& A, uint32_t fi) {
+    return (A.frame_table ? const_as(A.frame_table) : const_as(&A.frames[0])) + fi;
+}
+struct FrameCamera { float pos[3], c0[3], c1[3], c2[3], cps[3]; };
+__device__ __forceinline__ FrameCamera load_camera(const BH_CONST_AS FrameArgs* F) {
+    FrameCamera c;
     for (int k = 0; k < 3; ++k) {
-        a.pos[k] = F.pos[k]; a.c0[k] = F.c0[k]; a.c1[k] = F.c1[k]; a.c2[k] = F.c2[k]; a.cps[k] = F.cps[k];
+        c.pos[k] = F->pos[k]; c.c0[k] = F->c0[k]; c.c1[k] = F->c1[k]; c.c2[k] = F->c2[k]; c.cps[k] = F->cps[k];
+    }
+    return c;
+}
+__device__ __forceinline__ void select_camera(MarchArgs& a, const FrameCamera& c) {
+    for (int k = 0; k < 3; ++k) {
+        a.pos[k] = c.pos[k]; a.c0[k] = c.c0[k]; a.c1[k] = c.c1[k]; a.c2[k] = c.c2[k]; a.cps[k] = c.cps[k];
     }
 }
-__device__ __forceinline__ void select_outputs(MarchArgs& a, const FrameArgs& F) {
-    a.out_col = F.out_col; a.out_blackout = F.out_blackout;
-    a.dbg_n_rk = F.dbg_n_rk; a.dbg_fate = F.dbg_fate; a.dbg_steps = F.dbg_steps;
+__device__ __forceinline__ void select_outputs(MarchArgs& a, const BH_CONST_AS FrameArgs* F) {
+    a.out_col = F->out_col; a.out_blackout = F->out_blackout;
+    a.dbg_n_rk = F->dbg_n_rk; a.dbg_fate = F->dbg_fate; a.dbg_steps = F->dbg_steps;
+}
+
+// What a wave learns from its dispatch slot before it touches a pixel, all of it wave-uniform and held in SGPRs:
+// the frame and its camera, the shard-local tile and its coordinates.  slot_head issues the loads behind it (the
+// order entry, the tile list's, the frame's record: scalar loads of data another kernel or the host wrote before
+// this launch) so that a kernel can have them in flight while its table copy is (march_tile_wave).  The two
+// divisions by launch constants are multiply-highs by the host's magics (bh_host.cpp, div_magic; 0: none, divide).
+// ok == false: the order entry is out of range (defensive: a corrupt order must not address outside the shard).
+struct SlotHead {
+    uint32_t fi, t, tx, ty;
+    FrameCamera cam;
+    bool ok;
+};
+template <bool ITEM>
+__device__ __forceinline__ SlotHead slot_head(const MarchArgs& A, uint32_t slot, uint32_t item_tx = 0u, uint32_t item_ty = 0u) {
+    SlotHead h{};
+    const uint32_t nf = A.n_frames;
+    uint32_t fi = 0, j = slot;
+    if constexpr (ITEM) {
+        fi = slot;
+    } else if (nf > 1u) {
+        j = A.nf_magic ? __umulhi(slot, A.nf_magic) : slot / nf;
+        fi = slot - j * nf;
+    }
+    h.fi = fi;
+    h.cam = load_camera(frame_args_of(A, fi));
+    if constexpr (ITEM) {
+        h.tx = item_tx;
+        h.ty = item_ty;
+    } else {
+        const uint32_t t = A.order ? const_as(A.order)[j] : centre_out(j, A.n_tiles, A.order_block, A.order_centre);
+        h.t = t;
+        if (t >= A.n_tiles) return h;
+        if (A.tile_list) {  // weighted partition (bh_partition): the shard's tile list
+            const uint32_t v = const_as(A.tile_list)[t];
+            h.tx = v & 0xFFFFu;
+            h.ty = v >> 16;
+        } else if (A.shard_count == 1u && A.tx_magic) {
+            h.ty = __umulhi(t, A.tx_magic);
+            h.tx = t - h.ty * A.tiles_x;
+        } else {
+            shard_tile_coords(t, A.tiles_x, A.shard_index, A.shard_count, &h.tx, &h.ty);
+        }
+    }
+    h.ok = true;
+    return h;
 }
 
 // Several frames in one launch (bh_render_frames): dispatch slot s is tile s / n_frames of the order
@@ -52,44 +116,18 @@ __device__ __forceinline__ void select_outputs(MarchArgs& a, const FrameArgs& F)
 struct ShutterLane { uint32_t px, py; bool valid, ok; };
 template <uint32_t FMT, uint32_t SF, bool SS = false, bool ITEM = false, bool LENS = false, bool SHUT = false,
           bool RAYS = false, bool POSE = false>
-__device__ __forceinline__ void march_slot(const MarchArgs& A, uint32_t slot, const float* lut,
-                                           uint32_t lane, uint32_t item_tx = 0u, uint32_t item_ty = 0u,
-                                           ShutterLane* sl = nullptr, const float* dirs = nullptr) {
+__device__ __forceinline__ void march_slot_body(const MarchArgs& A, const SlotHead& h, const float* lut,
+                                                uint32_t lane, ShutterLane* sl = nullptr, const float* dirs = nullptr) {
     static_assert(SS || !ITEM, "work items are supersampled tiles");
     static_assert(!LENS || (!SS && !BH_FAST), "a lens is one record per ray, in exact math");
     static_assert(!SHUT || (!SS && !ITEM && !LENS), "a shutter wave takes its ss from the argument");
     static_assert(!RAYS || (!BH_FAST && !ITEM && (!SHUT || POSE)),
                   "a ray map feeds the exact plain, supersampled and lens forms, and posed the shutter form");
     static_assert(!POSE || RAYS, "a pose turns a ray map");
-    const uint32_t nf = A.n_frames;
-    uint32_t fi = 0, j = slot;
-    if constexpr (ITEM) {
-        fi = slot;
-    } else if (nf > 1u) {
-        j = slot / nf;
-        fi = slot - j * nf;
-    }
+    const uint32_t fi = h.fi, t = h.t, tx = h.tx, ty = h.ty;
     MarchArgs a = A;
-    // frames[0] == the top-level fields for a one-frame launch; launches of more than
-    // BH_INLINE_FRAMES frames read them from the device table (wave-uniform index: one load per wave)
-    if (A.frame_table) select_camera(a, A.frame_table[fi]);
-    else select_camera(a, A.frames[fi]);
+    select_camera(a, h.cam);
     if (ITEM || fi != 0u) a.tile_cost = nullptr;
-    uint32_t t = 0u, tx, ty;
-    if constexpr (ITEM) {
-        tx = item_tx;
-        ty = item_ty;
-    } else {
-    t = a.order ? a.order[j] : centre_out(j, a.n_tiles, a.order_block, a.order_centre);
-    if (t >= a.n_tiles) return;  // defensive: a corrupt order must not address outside the shard
-    if (a.tile_list) {  // weighted partition (bh_partition): the shard's tile list
-        const uint32_t v = a.tile_list[t];
-        tx = v & 0xFFFFu;
-        ty = v >> 16;
-    } else {
-        shard_tile_coords(t, a.tiles_x, a.shard_index, a.shard_count, &tx, &ty);
-    }
-    }
     const uint32_t px = tx * 8u + (lane & 7u), py = ty * 8u + (lane >> 3);
     const bool valid = px < a.width && py < a.height;
     const Frame f = make_frame(a);
@@ -145,8 +183,7 @@ __device__ __forceinline__ void march_slot(const MarchArgs& A, uint32_t slot, co
         // every lane takes the resolve (its butterfly reads the wave's other lanes); invalid lanes hold 0
         uint32_t fo = fi;
         asm volatile("" : "+s"(fo));
-        if (A.frame_table) select_outputs(a, A.frame_table[fo]);
-        else select_outputs(a, A.frames[fo]);
+        select_outputs(a, frame_args_of(A, fo));
         v3 sc, sb;
         ss_samples(a, lut, lane, valid, fate, st, steps, sc, sb);
         ss_resolve_store<FMT>(a, lut, lane, px, py, valid, sc, sb);
@@ -157,8 +194,7 @@ __device__ __forceinline__ void march_slot(const MarchArgs& A, uint32_t slot, co
         // workgroups per CU resident (MI355X_MICROARCH.md, Residency)
         uint32_t fo = fi;
         asm volatile("" : "+s"(fo));
-        if (A.frame_table) select_outputs(a, A.frame_table[fo]);
-        else select_outputs(a, A.frames[fo]);
+        select_outputs(a, frame_args_of(A, fo));
 #if !BH_FAST
         if constexpr (LENS) {
             // out_col is the lens (bh_render_lens: row-major, whole frame): one 8-byte vector store per lane
@@ -181,6 +217,16 @@ __device__ __forceinline__ void march_slot(const MarchArgs& A, uint32_t slot, co
                 __hip_atomic_fetch_add(&a.order_tot[b], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         }
     }
+}
+// Head and body back to back: the shutter workgroups' waves and the work-list march's items.
+template <uint32_t FMT, uint32_t SF, bool SS = false, bool ITEM = false, bool LENS = false, bool SHUT = false,
+          bool RAYS = false, bool POSE = false>
+__device__ __forceinline__ void march_slot(const MarchArgs& A, uint32_t slot, const float* lut,
+                                           uint32_t lane, uint32_t item_tx = 0u, uint32_t item_ty = 0u,
+                                           ShutterLane* sl = nullptr, const float* dirs = nullptr) {
+    const SlotHead h = slot_head<ITEM>(A, slot, item_tx, item_ty);
+    if (!h.ok) return;
+    march_slot_body<FMT, SF, SS, ITEM, LENS, SHUT, RAYS, POSE>(A, h, lut, lane, sl, dirs);
 }
 
 // Shader-clock probe (bh_set_clock_probe): a sampled wave reads both counters when it starts and adds
@@ -208,36 +254,44 @@ __device__ __forceinline__ void clock_end(unsigned long long* acc, const ClockSt
 }
 
 // One wave of the tile schedule: its dispatch slot (the grid covers every slot, WG_WAVES waves per workgroup),
-// marched with march_slot's SS / LENS form, between the clock probe's two readings.
-template <uint32_t FMT, uint32_t SF, bool SS, bool LENS = false>
-__device__ __forceinline__ void march_tile_wave(const MarchArgs& A, const float* lut) {
+// marched with march_slot_body's SS / LENS / RAYS / POSE form, between the clock probe's two readings.
+// The wave's start is one trip to memory deep where it can be: the table copy's loads (lut != null: 16 bytes of
+// each table per lane, srgb_fetch) are issued first and awaited last, and the slot's own chain -- kernel argument,
+// order entry and frame record, tile list -- runs on the scalar unit while they fly (slot_head); then the one LDS
+// store per table and the workgroup's barrier.  (The copy by four guarded loads, each awaited, then the barrier,
+// then the chain through vector loads put about eight dependent round trips in front of pixel_ray's first
+// multiply: DESIGN.md §5 item 32.)
+template <uint32_t FMT, uint32_t SF, bool SS, bool LENS = false, bool RAYS = false, bool POSE = false>
+__device__ __forceinline__ void march_tile_wave(const MarchArgs& A, float* lut, const float* dirs = nullptr) {
+    static_assert(WG_WAVES == 1u, "the table copy is one wave's: 64 lanes x 16 bytes per table");
+    // every argument word the start branches on or indexes with, wanted here: one group of scalar loads and one
+    // wait for them (left to their uses, each is loaded in the block of its use and waited for there in turn)
+    asm volatile("" ::"s"(A.srgb_lut), "s"(A.n_tiles), "s"(A.n_frames), "s"(A.nf_magic), "s"(A.frame_table),
+                 "s"(A.order), "s"(A.tile_list), "s"(A.shard_count), "s"(A.tx_magic), "s"(A.tiles_x), "s"(A.clk),
+                 "s"(A.clk_mask), "s"(A.width), "s"(A.height), "s"(A.rw2), "s"(A.rh2));
+    SrgbRows<FMT> rows;
+    if constexpr (!LENS) rows = srgb_fetch<FMT>(A);
     const uint32_t slot = __builtin_amdgcn_readfirstlane(blockIdx.x * WG_WAVES + (threadIdx.x >> 6));
-    if (slot >= A.n_tiles * A.n_frames) return;  // wave-uniform
+    if (slot >= A.n_tiles * A.n_frames) return;  // wave-uniform, and the wave is its workgroup: nobody waits for it
+    const SlotHead h = slot_head<false>(A, slot);
+    if constexpr (!LENS) {
+        srgb_store<FMT>(rows, lut);
+        __syncthreads();
+    }
     // one slot in `stride`, rotated by slot / stride: the dispatcher deals workgroups to the 8 XCDs
     // round robin, so plain multiples of the stride would all land on one XCD
     const bool probe = A.clk && ((slot + (slot >> 8)) & A.clk_mask) == 0u;
     ClockStart c0{0u, 0u};
     if (probe) c0 = clock_start();
-    march_slot<FMT, SF, SS, false, LENS>(A, slot, lut, threadIdx.x & 63u);
+    if (h.ok) march_slot_body<FMT, SF, SS, false, LENS, false, RAYS, POSE>(A, h, lut, threadIdx.x & 63u, nullptr, dirs);
     if (probe) clock_end(A.clk, c0);
 }
 
-// The plain form: march_tile_wave<FMT, SF, false>, written out.  (Called through the helper -- whole, or only
-// its probe and march_slot -- the eight RGBA16F instantiations of this kernel come out at the same size with
-// other register numbers and instruction order in their store epilogue; the supersampled and lens kernels keep
-// their machine code either way: profiles/r12/march_split/.)
+// The plain form.
 template <uint32_t FMT, uint32_t SF>
 __global__ void __launch_bounds__(64 * WG_WAVES) march_tile_kernel(MarchArgs A) {
-    __shared__ float lut[lds_tables<FMT>()];
-    load_srgb_tables<FMT, 64u * WG_WAVES>(A, lut);
-    __syncthreads();
-    const uint32_t slot = __builtin_amdgcn_readfirstlane(blockIdx.x * WG_WAVES + (threadIdx.x >> 6));
-    if (slot >= A.n_tiles * A.n_frames) return;  // wave-uniform
-    const bool probe = A.clk && ((slot + (slot >> 8)) & A.clk_mask) == 0u;  // as march_tile_wave
-    ClockStart c0{0u, 0u};
-    if (probe) c0 = clock_start();
-    march_slot<FMT, SF>(A, slot, lut, threadIdx.x & 63u);
-    if (probe) clock_end(A.clk, c0);
+    __shared__ __attribute__((aligned(16))) float lut[lds_tables<FMT>()];
+    march_tile_wave<FMT, SF, false>(A, lut);
 }
 
 // The tile schedule's supersampled form (bh_render_ss, ss > 1): the same waves over the virtual frame's
@@ -246,9 +300,7 @@ __global__ void __launch_bounds__(64 * WG_WAVES) march_tile_kernel(MarchArgs A) 
 // kernel per format and scene-flag fold, not three.
 template <uint32_t FMT, uint32_t SF>
 __global__ void __launch_bounds__(64 * WG_WAVES) march_tile_ss_kernel(MarchArgs A) {
-    __shared__ float lut[lds_tables<FMT>()];
-    load_srgb_tables<FMT, 64u * WG_WAVES>(A, lut);
-    __syncthreads();
+    __shared__ __attribute__((aligned(16))) float lut[lds_tables<FMT>()];
     march_tile_wave<FMT, SF, true>(A, lut);
 }
 
@@ -296,8 +348,8 @@ march_tile_shutter_kernel(MarchArgs A, uint32_t ln) {
     // holds a barrier.  A wave whose lanes are all outside the frame marches nothing and stages zeros.
     __syncthreads();
     if (!sl.ok || w > 1u) return;
-    const FrameArgs& F = A.frame_table ? A.frame_table[slot % A.n_frames] : A.frames[slot % A.n_frames];
-    void* out = w == 0u ? F.out_col : F.out_blackout;
+    const BH_CONST_AS FrameArgs* F = frame_args_of(A, slot % A.n_frames);
+    void* out = w == 0u ? F->out_col : F->out_blackout;
     if (!out) return;  // wave 1 of a frame without the second target: neither resolved nor written
     const uint32_t lk = A.ss_log2;
     if (sl.valid && ss::writer(lane, lk))
@@ -317,52 +369,27 @@ __global__ void __launch_bounds__(64 * WG_WAVES) march_tile_lens_kernel(MarchArg
 // with march_slot's RAYS switch -- the lane's direction from the caller's map, everything after it shared.  The map
 // is a second kernel argument of these kernels only (MarchArgs has no free word, and its layout is what the other
 // kernels were compiled against); it is read once per lane, before the loop.
-template <uint32_t FMT, uint32_t SF, bool SS, bool LENS>
-__device__ __forceinline__ void march_tile_rays_wave(const MarchArgs& A, const float* lut, const float* dirs) {
-    const uint32_t slot = __builtin_amdgcn_readfirstlane(blockIdx.x * WG_WAVES + (threadIdx.x >> 6));
-    if (slot >= A.n_tiles * A.n_frames) return;  // wave-uniform
-    const bool probe = A.clk && ((slot + (slot >> 8)) & A.clk_mask) == 0u;  // as march_tile_wave
-    ClockStart c0{0u, 0u};
-    if (probe) c0 = clock_start();
-    march_slot<FMT, SF, SS, false, LENS, false, true>(A, slot, lut, threadIdx.x & 63u, 0u, 0u, nullptr, dirs);
-    if (probe) clock_end(A.clk, c0);
-}
 template <uint32_t FMT, uint32_t SF, bool SS>
 __global__ void __launch_bounds__(64 * WG_WAVES) march_tile_rays_kernel(MarchArgs A, const float* dirs) {
-    __shared__ float lut[lds_tables<FMT>()];
-    load_srgb_tables<FMT, 64u * WG_WAVES>(A, lut);
-    __syncthreads();
-    march_tile_rays_wave<FMT, SF, SS, false>(A, lut, dirs);
+    __shared__ __attribute__((aligned(16))) float lut[lds_tables<FMT>()];
+    march_tile_wave<FMT, SF, SS, false, true>(A, lut, dirs);
 }
 template <uint32_t SF>
 __global__ void __launch_bounds__(64 * WG_WAVES) march_tile_rays_lens_kernel(MarchArgs A, const float* dirs) {
-    march_tile_rays_wave<BH_OUT_RGBA32F, SF, false, true>(A, nullptr, dirs);
+    march_tile_wave<BH_OUT_RGBA32F, SF, false, true, true>(A, nullptr, dirs);
 }
 
 // The posed ray-map forms (bh_render_frames_rays, bh_render_lens_rays_posed): the ray-map kernels over a map in camera
-// space, with march_slot's POSE switch and any number of frames -- frame fi's FrameArgs holds its camera's position
-// and basis (bh_ray_pose), every frame reads the one map.  A wave helper of their own: the unposed kernels keep the
-// machine code they were measured with.
-template <uint32_t FMT, uint32_t SF, bool SS, bool LENS>
-__device__ __forceinline__ void march_tile_rays_pose_wave(const MarchArgs& A, const float* lut, const float* dirs) {
-    const uint32_t slot = __builtin_amdgcn_readfirstlane(blockIdx.x * WG_WAVES + (threadIdx.x >> 6));
-    if (slot >= A.n_tiles * A.n_frames) return;  // wave-uniform
-    const bool probe = A.clk && ((slot + (slot >> 8)) & A.clk_mask) == 0u;  // as march_tile_wave
-    ClockStart c0{0u, 0u};
-    if (probe) c0 = clock_start();
-    march_slot<FMT, SF, SS, false, LENS, false, true, true>(A, slot, lut, threadIdx.x & 63u, 0u, 0u, nullptr, dirs);
-    if (probe) clock_end(A.clk, c0);
-}
+// space, with march_slot_body's POSE switch and any number of frames -- frame fi's FrameArgs holds its camera's
+// position and basis (bh_ray_pose), every frame reads the one map.
 template <uint32_t FMT, uint32_t SF, bool SS>
 __global__ void __launch_bounds__(64 * WG_WAVES) march_tile_rays_pose_kernel(MarchArgs A, const float* dirs) {
-    __shared__ float lut[lds_tables<FMT>()];
-    load_srgb_tables<FMT, 64u * WG_WAVES>(A, lut);
-    __syncthreads();
-    march_tile_rays_pose_wave<FMT, SF, SS, false>(A, lut, dirs);
+    __shared__ __attribute__((aligned(16))) float lut[lds_tables<FMT>()];
+    march_tile_wave<FMT, SF, SS, false, true, true>(A, lut, dirs);
 }
 template <uint32_t SF>
 __global__ void __launch_bounds__(64 * WG_WAVES) march_tile_rays_pose_lens_kernel(MarchArgs A, const float* dirs) {
-    march_tile_rays_pose_wave<BH_OUT_RGBA32F, SF, false, true>(A, nullptr, dirs);
+    march_tile_wave<BH_OUT_RGBA32F, SF, false, true, true, true>(A, nullptr, dirs);
 }
 
 // The shutter form over a posed ray map (bh_render_frames_shutter_rays): march_tile_shutter_kernel, statement for
@@ -391,8 +418,8 @@ march_tile_shutter_rays_kernel(MarchArgs A, const float* dirs, uint32_t ln) {
     if (probe) clock_end(A.clk, c0);
     __syncthreads();  // every wave of the workgroup, whatever its march did (march_tile_shutter_kernel)
     if (!sl.ok || w > 1u) return;
-    const FrameArgs& F = A.frame_table ? A.frame_table[slot % A.n_frames] : A.frames[slot % A.n_frames];
-    void* out = w == 0u ? F.out_col : F.out_blackout;
+    const BH_CONST_AS FrameArgs* F = frame_args_of(A, slot % A.n_frames);
+    void* out = w == 0u ? F->out_col : F->out_blackout;
     if (!out) return;  // wave 1 of a frame without the second target: neither resolved nor written
     const uint32_t lk = A.ss_log2;
     if (sl.valid && ss::writer(lane, lk))

@@ -109,6 +109,31 @@ __device__ __forceinline__ void load_srgb_tables(const Args& a, float* tab) {
         if (threadIdx.x == 0) tab[256 + 256] = a.srgb_enc[256];
 }
 
+// The same copy by a workgroup of ONE wave, in two halves with the caller's own loads between them: 16 bytes of
+// each table per lane (srgb_fetch: the loads, nothing waits for them), then one LDS store each (srgb_store: the
+// first use, so the only wait), the barrier after it the caller's.  The guarded loop above waits for each of its
+// four loads in turn.  Both tables are allocations of their own (bh_host.cpp, upload) and `tab` is 16-byte aligned.
+template <uint32_t FMT>
+struct SrgbRows { float4 lut, enc; float last; };
+template <uint32_t FMT, class Args>
+__device__ __forceinline__ SrgbRows<FMT> srgb_fetch(const Args& a) {
+    SrgbRows<FMT> r;
+    r.lut = reinterpret_cast<const float4*>(a.srgb_lut)[threadIdx.x];
+    if constexpr (FMT == BH_OUT_BGRA8_SRGB) {
+        r.enc = reinterpret_cast<const float4*>(a.srgb_enc)[threadIdx.x];
+        r.last = a.srgb_enc[256];
+    }
+    return r;
+}
+template <uint32_t FMT>
+__device__ __forceinline__ void srgb_store(const SrgbRows<FMT>& r, float* tab) {
+    reinterpret_cast<float4*>(tab)[threadIdx.x] = r.lut;
+    if constexpr (FMT == BH_OUT_BGRA8_SRGB) {
+        reinterpret_cast<float4*>(tab)[64u + threadIdx.x] = r.enc;
+        if (threadIdx.x == 0) tab[256 + 256] = r.last;
+    }
+}
+
 }  // namespace bh
 
 // The host's builders of B and E from the 257 thresholds (bh_host.cpp; the self-test builds its own copies)

@@ -732,6 +732,11 @@ int64_t bh_tile_bytes(uint32_t layout, uint32_t format);
  * encode(x) >= k, out[0] = 0, out[256] = +inf; encode(x) = the largest k with x >= out[k]. */
 int bh_srgb_encode_table(float* out257);
 
+/* Diagnostics of a launch's host-side constants: the multiply-high magic a launch passes for its waves' divisions
+ * by d with dividends up to n_max (0: none, the waves divide) in *magic; returns the number of n in [0, n_max] at
+ * which (n * magic) >> 32 differs from n / d (0 when magic is 0), or a negative status. */
+int64_t bh_div_magic_misses(uint32_t d, uint32_t n_max, uint32_t* magic);
+
 /* Diagnostics: check the correctly rounded division/sqrt cores the exact kernel uses against IEEE
  * results on `device` (op 0: sqrt over float bit patterns [base, base+count); op 1: x/6 over bit
  * patterns [base, base+count); op 2: n/d on `count` random pairs seeded by base; op 3: n/d near exact
