@@ -4,6 +4,11 @@ import numpy as np
 import black_hole_ray_marching_amd as bh
 import oracle
 
+# the fast mode's colour tolerance (DESIGN.md "Math modes"), the one definition every fast-mode test imports.
+# NOT the north_star 1e-4: a one-ulp change of the final ray direction moves the sky coordinate by ~2e-4
+# texels, so at single-texel stars any non-bit-exact trajectory shows |delta| ~1e-3.
+FAST_TOL = 5e-3
+
 # every schedule, and both builds of the exact kernels (source order / machine-scheduled; the small
 # test frames pick the latter by default)
 SCHEDULES = [bh.BH_SCHED_PAIR, bh.BH_SCHED_TILE | bh.BH_SCHED_FLAG_ISSUE_ORDER,

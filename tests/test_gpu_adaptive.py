@@ -12,6 +12,7 @@ import black_hole_ray_marching_amd as bh
 from black_hole_ray_marching_amd import _abi
 from tests._adaptive_ref import CAMS, KS, SIZES, T, composed, pixel_mask, plain, tile_mask
 from tests._cases import camera_uniform, uniforms
+from tests._gpu_common import FAST_TOL
 from tests._ss_ref import CAP, FLAGS, expected_bytes, reference, sky_ss
 
 pytestmark = pytest.mark.gpu
@@ -255,7 +256,6 @@ def test_graph(torch_cuda):
         sc.close()
 
 
-FAST_TOL = 5e-3  # the fast mode's documented tolerance (tests/test_gpu_parity.py, DESIGN.md "Math modes")
 
 
 @pytest.mark.parametrize("k", [2, 4])

@@ -143,16 +143,18 @@ def test_frames_of_far_near_default_and_origin_cameras_in_one_launch(torch_cuda,
 
 @pytest.mark.parametrize("cam,W,H,cap,flags,over", EDGE_CASES, ids=EDGE_IDS)
 def test_fast_mode_outputs_are_valid_at_the_edges(torch_cuda, scene_small, cam, W, H, cap, flags, over):
-    """BH_MATH_FAST promises no bits on these inputs, only valid outputs: a fate in 0..3, n_rk <= cap, every
+    """BH_MATH_FAST promises no bits on these inputs, only valid outputs, under the tile, pair and persistent
+    schedules (three kernels, two forms of the step): a fate in 0..3, n_rk <= cap, every
     colour channel finite and in [0, 1], alpha 1, and the blackout target the per-pixel function of col
     (src/black_hole_maybe.wgsl:365-368).  No comparison with the oracle's colours."""
     cu, U = camera_uniform(cam, W, H), uniforms(**over)
-    gc, gb, gn, gf = gpu_render(torch_cuda, scene_small, cu, U, W, H, cap, flags, bh.BH_MATH_FAST,
-                                schedule=bh.BH_SCHED_TILE)
-    assert gf.max() <= 3, np.unique(gf)
-    assert int(gn.max()) <= cap
-    assert np.isfinite(gc).all(), f"non-finite colour at {np.argwhere(~np.isfinite(gc))[:5]}"
-    assert (gc[..., :3] >= 0).all() and (gc[..., :3] <= 1).all() and (gc[..., 3] == 1).all()
-    keep = ~(((gc[..., 0] * gc[..., 0] + gc[..., 1] * gc[..., 1]) + gc[..., 2] * gc[..., 2]) < 1.0)
-    exp = np.where(keep[..., None], gc, np.array([0, 0, 0, 1], np.float32))
-    assert np.array_equal(gb, exp)
+    for schedule in (bh.BH_SCHED_TILE, bh.BH_SCHED_PAIR, bh.BH_SCHED_PERSISTENT):
+        gc, gb, gn, gf = gpu_render(torch_cuda, scene_small, cu, U, W, H, cap, flags, bh.BH_MATH_FAST,
+                                    schedule=schedule)
+        assert gf.max() <= 3, (schedule, np.unique(gf))
+        assert int(gn.max()) <= cap, schedule
+        assert np.isfinite(gc).all(), f"schedule {schedule}: non-finite colour at {np.argwhere(~np.isfinite(gc))[:5]}"
+        assert (gc[..., :3] >= 0).all() and (gc[..., :3] <= 1).all() and (gc[..., 3] == 1).all(), schedule
+        keep = ~(((gc[..., 0] * gc[..., 0] + gc[..., 1] * gc[..., 1]) + gc[..., 2] * gc[..., 2]) < 1.0)
+        exp = np.where(keep[..., None], gc, np.array([0, 0, 0, 1], np.float32))
+        assert np.array_equal(gb, exp), schedule

@@ -15,7 +15,7 @@ from black_hole_ray_marching_amd import _abi
 from tests import _adaptive_ref, _lens_ref, _rays_ref, _shutter_ref
 from tests import _scenarios as S
 from tests._cases import camera_uniform
-from tests._gpu_common import gpu_render
+from tests._gpu_common import FAST_TOL, gpu_render
 from tests._lens_mip_ref import shade_mip_np
 from tests._ss_ref import expected_bytes, reference, resolve_np, scenario_uniforms, sky_ss
 
@@ -27,7 +27,6 @@ GUARD = 4096     # bytes on either side of a target that no render may touch
 T = bh.BH_SCHED_TILE
 PASSES = [("fresh order", 0), ("learned order", 0), ("issue-order build", T | bh.BH_SCHED_FLAG_ISSUE_ORDER),
           ("latency build", T | bh.BH_SCHED_FLAG_LATENCY)]
-FAST_TOL = 5e-3  # the fast mode's documented tolerance (tests/test_gpu_parity.py, DESIGN.md "Math modes")
 
 
 @pytest.fixture(scope="module")

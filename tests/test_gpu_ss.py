@@ -11,6 +11,7 @@ import pytest
 import black_hole_ray_marching_amd as bh
 from black_hole_ray_marching_amd import _abi
 from tests._cases import camera_uniform, uniforms
+from tests._gpu_common import FAST_TOL
 from tests._ss_ref import CAP, FLAGS, KS, SIZES, expected_bytes, reference, resolve_np, sky_ss
 
 pytestmark = pytest.mark.gpu
@@ -181,7 +182,6 @@ def _fast_pair(torch, W, H, k):
         sc.close()
 
 
-FAST_TOL = 5e-3  # the fast mode's documented tolerance (tests/test_gpu_parity.py, DESIGN.md "Math modes")
 
 
 @pytest.mark.parametrize("k", KS)
