@@ -160,6 +160,13 @@ SIGNATURES = {
     "bh_render_lens_rays_posed": (C.c_int, [C.c_void_p, C.POINTER(bh_ray_pose), C.POINTER(bh_uniforms),
                                             C.POINTER(bh_render_desc), C.c_void_p, C.c_void_p, C.c_void_p]),
     "bh_ray_pose_apply_host": (C.c_int, [C.POINTER(bh_ray_pose), C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p]),
+    "bh_render_frames_rays_origins": (C.c_int, [C.c_void_p, C.c_uint32, C.POINTER(bh_ray_pose), C.POINTER(bh_uniforms),
+                                                C.POINTER(bh_render_desc), C.c_void_p, C.c_void_p, C.c_uint32,
+                                                C.c_void_p]),
+    "bh_render_lens_rays_origins": (C.c_int, [C.c_void_p, C.POINTER(bh_ray_pose), C.POINTER(bh_uniforms),
+                                              C.POINTER(bh_render_desc), C.c_void_p, C.c_void_p, C.c_void_p,
+                                              C.c_void_p]),
+    "bh_ray_origins_apply_host": (C.c_int, [C.POINTER(bh_ray_pose), C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p]),
     "bh_shard_tile_count": (C.c_int64, [C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32]),
     "bh_tiles_unpack": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32,
                                   C.c_uint64, C.c_uint32, C.c_void_p]),

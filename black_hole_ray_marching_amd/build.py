@@ -64,6 +64,11 @@ TU_FLAGS = {
                                "-mllvm", "-enable-misched=0", "-mllvm", "-enable-post-misched=0",
                                "-mllvm", "-disable-machine-licm"],
     "bh_march_rays_pose_lat.hip": ["-ffp-contract=off", "-fhip-fp32-correctly-rounded-divide-sqrt", "-fno-slp-vectorize"],
+    # the posed ray-map march with an origin map (bh_render_frames_rays_origins, its lens form): the same two sets
+    "bh_march_rays_org.hip": ["-ffp-contract=off", "-fhip-fp32-correctly-rounded-divide-sqrt", "-fno-slp-vectorize",
+                              "-mllvm", "-enable-misched=0", "-mllvm", "-enable-post-misched=0",
+                              "-mllvm", "-disable-machine-licm"],
+    "bh_march_rays_org_lat.hip": ["-ffp-contract=off", "-fhip-fp32-correctly-rounded-divide-sqrt", "-fno-slp-vectorize"],
     "bh_tiles.hip": [],
     # the lens shades and the sky chain: the march kernels' shading arithmetic, one rounding per op (bh_lens.hpp)
     "bh_lens.hip": ["-ffp-contract=off", "-fhip-fp32-correctly-rounded-divide-sqrt", "-fno-slp-vectorize"],
@@ -116,7 +121,8 @@ def build_product(force: bool = False, out_dir: Path | None = None, extra: dict[
         o = obj_dir / (s.stem + ".o")
         deps = [s, *headers, Path(__file__)] + ([csrc / "bh_march_exact.hip"] if src in ("bh_march_exact_lat.hip", "bh_march_refine_lat.hip") else []) \
             + ([csrc / "bh_march_rays.hip"] if src == "bh_march_rays_lat.hip" else []) \
-            + ([csrc / "bh_march_rays_pose.hip"] if src == "bh_march_rays_pose_lat.hip" else [])
+            + ([csrc / "bh_march_rays_pose.hip"] if src == "bh_march_rays_pose_lat.hip" else []) \
+            + ([csrc / "bh_march_rays_org.hip"] if src == "bh_march_rays_org_lat.hip" else [])
         if force or _stale(o, deps):
             jobs.append([HIPCC, *COMMON, *flags, *extra.get(src, []), "-c", str(s), "-o", str(o)])
         objs.append(o)

@@ -422,9 +422,12 @@ static void frame_args(const bh_camera_uniform* cam, float rs, const bh_render_d
 // launch shape -- FNV-1a over those fields' bits (padding and the unused bg_brightness left out).  The
 // outputs, their format and the sky do not change a step count.  A ray-map launch's rays are its map's: the map's
 // address enters the key (its contents cannot: a map rewritten in place may meet a stale order, never other bytes),
-// and so does every pose of a posed launch (after a marker: a posed launch is never taken for an unposed one).
+// and so does every pose of a posed launch (after a marker: a posed launch is never taken for an unposed one), and
+// an origin map's address beside the direction map's (after a marker of its own: a launch with origins is never
+// taken for one without).
 static uint64_t frame_cost_key(const bh_camera_uniform* cam, const bh_uniforms* U, const bh_render_desc* d,
-                               const float* ray_map = nullptr, const bh_ray_pose* poses = nullptr, uint32_t n_poses = 0u) {
+                               const float* ray_map = nullptr, const bh_ray_pose* poses = nullptr, uint32_t n_poses = 0u,
+                               const float* origin_map = nullptr) {
     uint64_t h = 1469598103934665603ull;
     auto mix = [&](const void* p, size_t n) {
         const unsigned char* b = static_cast<const unsigned char*>(p);
@@ -444,6 +447,11 @@ static uint64_t frame_cost_key(const bh_camera_uniform* cam, const bh_uniforms* 
     if (poses) {
         mix(&n_poses, sizeof n_poses);
         mix(poses, sizeof(bh_ray_pose) * n_poses);
+    }
+    if (origin_map) {
+        const uint32_t marker = 0x4F524947u;  // "ORIG"
+        mix(&marker, sizeof marker);
+        mix(&origin_map, sizeof origin_map);
     }
     return h | 1u;  // never 0: 0 marks the fresh state's all-zero costs
 }
@@ -517,6 +525,7 @@ struct Launch {
     uint32_t shutter_log2 = 0;         // bh_render_shutter: log2 of the cameras per output frame (a.n_frames counts cameras)
     const float* ray_map = nullptr;    // bh_render_rays, bh_render_lens_rays: the device map the rays come from
     const bh_ray_pose* poses = nullptr;  // the posed ray-map forms: one pose per camera (a.n_frames of them), else null
+    const float* origin_map = nullptr;   // bh_render_frames_rays_origins, bh_render_lens_rays_origins: the rays' origins
 };
 
 // Every argument check of a launch; no HIP call.  Leaves the launch's desc and tile count in L.
@@ -649,7 +658,7 @@ static int learned_order(bh_ctx* c, Launch* L, const bh_camera_uniform* cam0, co
     // buffers behind them costs at most a stale order, never a disagreement.  BH_ORDER_ALWAYS (A/B):
     // build and write on every launch, as before round 5.
     static const bool always = std::getenv("BH_ORDER_ALWAYS") != nullptr;
-    const uint64_t key = frame_cost_key(cam0, U, d, L->ray_map, L->poses, a.n_frames);
+    const uint64_t key = frame_cost_key(cam0, U, d, L->ray_map, L->poses, a.n_frames, L->origin_map);
     const bool repeat = !always && os->order_key == os->cost_key && os->cost_key == key;
     if (!repeat) {
         int oe = bh_launch_build_order(os->tile_cost, a.n_tiles, a.order_block, a.order_centre, os->counters,
@@ -672,7 +681,10 @@ static int launch_march(bh_ctx* c, const Launch& L, bh_ctx::OrderState* os, hipS
     const uint32_t sched = d->schedule & 0xFFu;
     const bool issue = march_variant_issue_order(d, a.n_tiles, a.n_frames, c->cus);  // every camera's tiles
     int e;
-    if (L.poses)  // exact math, tile schedule (render_rays_posed); the shutter form when shutter_log2 != 0
+    if (L.origin_map)  // exact math, tile schedule, no shutter form (render_rays_posed with an origin map)
+        e = issue ? bh_launch_rays_org_exact(a, L.ray_map, L.origin_map, s)
+                  : bh_launch_rays_org_exact_lat(a, L.ray_map, L.origin_map, s);
+    else if (L.poses)  // exact math, tile schedule (render_rays_posed); the shutter form when shutter_log2 != 0
         e = issue ? bh_launch_rays_pose_exact(a, L.ray_map, L.shutter_log2, s)
                   : bh_launch_rays_pose_exact_lat(a, L.ray_map, L.shutter_log2, s);
     else if (L.ray_map)  // exact math, tile schedule (render_rays)
@@ -893,10 +905,15 @@ int bh_render_lens_rays(bh_ctx* c, const float pos[3], const bh_uniforms* U, con
 // (out_lens): render_rays' launch -- the ray-map order state, the map in the repeated-frame key -- of
 // n_frames * n_sub cameras as bh_render_frames(_ss) or bh_render_frames_shutter launches them: one FrameArgs entry
 // per camera, holding its position and, in c0..c2, its basis rows (march_slot's POSE form reads them there).
+// with_origins (bh_render_frames_rays_origins, bh_render_lens_rays_origins; n_sub 1): the same launch by the ORG
+// kernels, which read each ray's origin from `origins` and form the photon-sphere centre per lane (FrameArgs::cps,
+// filled as ever, is not read by them).
 static int render_rays_posed(const char* fn, bh_ctx* c, uint32_t n_frames, uint32_t n_sub, const bh_ray_pose* poses,
                              const bh_uniforms* U, const bh_render_desc* descs, const float* dirs, uint32_t ss,
-                             bh_lens_px* out_lens, void* stream) {
+                             bh_lens_px* out_lens, void* stream, bool with_origins = false,
+                             const float* origins = nullptr) {
     if (!c || !poses || !U || !descs || !dirs || (reinterpret_cast<uintptr_t>(dirs) & 3u)) return bad_arg(fn, __LINE__);
+    if (with_origins && (!origins || (reinterpret_cast<uintptr_t>(origins) & 3u) || n_sub != 1u)) return bad_arg(fn, __LINE__);
     const uint32_t ln = bh::shutter::log2_n(n_sub);
     if (ln > bh::shutter::MAX_LOG2 || bh::ss::log2_k(ss) > 3u) return bad_arg(fn, __LINE__);
     if (n_frames == 0 || (uint64_t)n_frames * n_sub > BH_MAX_FRAMES) return bad_arg(fn, __LINE__);
@@ -957,6 +974,7 @@ static int render_rays_posed(const char* fn, bh_ctx* c, uint32_t n_frames, uint3
     }
     L.ray_map = dirs;
     L.poses = poses;
+    L.origin_map = with_origins ? origins : nullptr;
     return march_in_order(c, &L, cams.data(), U, stream);
 }
 
@@ -976,6 +994,18 @@ int bh_render_lens_rays_posed(bh_ctx* c, const bh_ray_pose* pose, const bh_unifo
                               const float* dirs_dev, bh_lens_px* out_lens, void* stream) {
     if (!out_lens || (reinterpret_cast<uintptr_t>(out_lens) & 7u)) return bad_arg(__func__, __LINE__);
     return render_rays_posed(__func__, c, 1u, 1u, pose, U, d, dirs_dev, 1u, out_lens, stream);
+}
+
+int bh_render_frames_rays_origins(bh_ctx* c, uint32_t n_frames, const bh_ray_pose* poses, const bh_uniforms* U,
+                                  const bh_render_desc* descs, const float* dirs_dev, const float* origins_dev,
+                                  uint32_t ss, void* stream) {
+    return render_rays_posed(__func__, c, n_frames, 1u, poses, U, descs, dirs_dev, ss, nullptr, stream, true, origins_dev);
+}
+
+int bh_render_lens_rays_origins(bh_ctx* c, const bh_ray_pose* pose, const bh_uniforms* U, const bh_render_desc* d,
+                                const float* dirs_dev, const float* origins_dev, bh_lens_px* out_lens, void* stream) {
+    if (!out_lens || (reinterpret_cast<uintptr_t>(out_lens) & 7u)) return bad_arg(__func__, __LINE__);
+    return render_rays_posed(__func__, c, 1u, 1u, pose, U, d, dirs_dev, 1u, out_lens, stream, true, origins_dev);
 }
 
 // bh_sky_create and bh_sky_create_mips: the texels, and with `mips` the chain built from them (a synchronous call)

@@ -206,6 +206,9 @@ BH_INTERNAL int bh_launch_rays_exact_lat(const bh::MarchArgs& a, const float* di
 // the posed ray-map march (bh_march_rays_pose.hip): a.n_frames cameras over one map, their bases in c0..c2;
 // shutter_log2 != 0: the shutter form, 2^shutter_log2 cameras per output frame
 BH_INTERNAL int bh_launch_rays_pose_exact(const bh::MarchArgs& a, const float* dirs, uint32_t shutter_log2, hipStream_t s);
+// ... with an origin map (bh_march_rays_org.hip): the posed launch without a shutter form, the lane's origin from `orgs`
+BH_INTERNAL int bh_launch_rays_org_exact(const bh::MarchArgs& a, const float* dirs, const float* orgs, hipStream_t s);
+BH_INTERNAL int bh_launch_rays_org_exact_lat(const bh::MarchArgs& a, const float* dirs, const float* orgs, hipStream_t s);
 BH_INTERNAL int bh_launch_rays_pose_exact_lat(const bh::MarchArgs& a, const float* dirs, uint32_t shutter_log2,
                 hipStream_t s);
 // the shutter render's march: 2^ln cameras per output frame, a.n_frames cameras in all (ln in 1..4)

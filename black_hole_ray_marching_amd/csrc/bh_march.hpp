@@ -4,7 +4,8 @@
 //   bh_march_exact.hip  (BH_FAST 0; built -ffp-contract=off, correctly-rounded f32 div/sqrt):
 //       same op sequence as the normative arithmetic of oracle/bh_oracle.c -> bit-exact parity
 //       (bh_march_exact_lat.hip and bh_march_refine_lat.hip build the same file again; bh_march_rays.hip and
-//       bh_march_rays_lat.hip hold the ray-map kernels alone, with the same two sets of flags);
+//       bh_march_rays_lat.hip hold the ray-map kernels alone, with the same two sets of flags, bh_march_rays_pose*.hip
+//       the posed ones and bh_march_rays_org*.hip those with an origin map);
 //   bh_march_fast.hip   (BH_FAST 1; built -ffp-contract=fast, hardware rcp/rsq/sqrt):
 //       algebraically identical reformulation for throughput -> tolerance parity.
 //
@@ -122,6 +123,28 @@ __attribute__((visibility("hidden"))) inline int launch_rays_pose(const MarchArg
             if (ln != 0u) launch_shutter_rays_schedule<FMT, SF>(a, dirs, ln, s);
             else if (a.ss_log2 != 0u) launch_tile_rays_schedule(march_tile_rays_pose_kernel<FMT, SF, true>, a, dirs, s);
             else launch_tile_rays_schedule(march_tile_rays_pose_kernel<FMT, SF, false>, a, dirs, s);
+        });
+        return (int)hipGetLastError();
+    });
+}
+// The posed ray-map march with an origin map (bh_render_frames_rays_origins, bh_render_lens_rays_origins; tile
+// schedule, no shutter form): any number of frames over one pair of camera-space maps.
+template <bool FOLD_NONE>
+__attribute__((visibility("hidden"))) inline int launch_rays_org(const MarchArgs& a, const float* dirs, const float* orgs, hipStream_t s) {
+    if (!dirs || !orgs || a.n_frames == 0u) return (int)hipErrorInvalidValue;
+    if (a.lens != 0u) {
+        if (a.n_frames != 1u) return (int)hipErrorInvalidValue;
+        with_scene_fold<FOLD_NONE>(a.scene_flags, [&](auto sf) {
+            launch_tile_rays_org_schedule(march_tile_rays_org_lens_kernel<decltype(sf)::value>, a, dirs, orgs, s);
+        });
+        return (int)hipGetLastError();
+    }
+    return with_format(a.format, [&](auto fmt) {
+        constexpr uint32_t FMT = decltype(fmt)::value;
+        with_scene_fold<FOLD_NONE>(a.scene_flags, [&](auto sf) {
+            constexpr uint32_t SF = decltype(sf)::value;
+            if (a.ss_log2 != 0u) launch_tile_rays_org_schedule(march_tile_rays_org_kernel<FMT, SF, true>, a, dirs, orgs, s);
+            else launch_tile_rays_org_schedule(march_tile_rays_org_kernel<FMT, SF, false>, a, dirs, orgs, s);
         });
         return (int)hipGetLastError();
     });

@@ -1,5 +1,5 @@
 // bh_march_tile.hpp -- the tile schedule (BH_SCHED_TILE, the default): one dispatch slot marched by one wave
-// (march_slot), the shader-clock probe, the plain, supersampled, shutter, lens and work-list kernels, and their
+// (march_slot), the shader-clock probe, the plain, supersampled, shutter, lens, ray-map and work-list kernels, and their
 // launchers.
 // Needs bh_march_ray.hpp, bh_march_shade.hpp, bh_march_resolve.hpp and bh_refine.hpp (the work list).
 #pragma once
@@ -113,30 +113,81 @@ __device__ __forceinline__ SlotHead slot_head(const MarchArgs& A, uint32_t slot,
 // (mx r + my u) + mz f, five roundings per component, before normalize_x.  The basis is wave-uniform and dead before
 // the loop; with POSE a ray map also feeds a shutter wave (SHUT), whose n waves read the same 12 bytes per pixel --
 // there without a branch: a lane outside the frame reads pixel (0, 0), inside any map, and still takes (0, 0, 1).
+// ORG (with RAYS and POSE, not SHUT or ITEM; the march_tile_rays_org_*_kernel forms): the ray's origin is the lane's
+// too -- its 12 bytes of the origin map `orgs` (bh_render_frames_rays_origins: camera space, the direction map's
+// geometry), turned as the direction is and added to the frame's position -- so the Frame is formed per lane
+// (org_load, slot_frame): ro0 and cps live in VGPRs through the loop, in these kernels alone.  The Frame of every
+// other form comes from the same call, slot_frame<false>: a forced-inline template keeps their machine code byte for
+// byte, which a lambda around the choice did not.
 struct ShutterLane { uint32_t px, py; bool valid, ok; };
+// The ORG form's prologue.  org_load: both 12-byte loads of a valid lane issued before either is used (one wait), and
+//     d = (mx r + my u) + mz f,   ro0 = pos + ((ox r + oy u) + oz f)
+// per component, one rounding per op in this association (bh_ray_pose's formula, twice); a lane outside the frame
+// loads nothing and takes d = (0, 0, 1) and ro0 = pos.  slot_frame<true>: make_frame's per-frame invariants per lane
+// -- cps = ((-normalize(ro0)) * 1.5) * RS as the host forms it per frame (bh_host.cpp, frame_args; normalize_x holds
+// the IEEE form's bits, fallback included); FrameArgs::cps is not read.  slot_frame<false> is make_frame.
+struct OrgRay { v3 d, ro0; };
+__device__ __forceinline__ OrgRay org_load(const MarchArgs& a, const float* dirs, const float* orgs, uint32_t px,
+                                           uint32_t py, bool valid) {
+    OrgRay g;
+    g.d = mk(0.0f, 0.0f, 1.0f);
+    g.ro0 = mk(a.pos[0], a.pos[1], a.pos[2]);
+    if (valid) {
+        const size_t i = ((size_t)py * a.width + px) * 3u;
+        const float* p = dirs + i;
+        const float* q = orgs + i;
+        const v3 m = mk(p[0], p[1], p[2]);
+        const v3 o = mk(q[0], q[1], q[2]);
+        const v3 r = mk(a.c0[0], a.c0[1], a.c0[2]), u = mk(a.c1[0], a.c1[1], a.c1[2]), fw = mk(a.c2[0], a.c2[1], a.c2[2]);
+        g.d = add(add(smul(m.x, r), smul(m.y, u)), smul(m.z, fw));
+        g.ro0 = add(g.ro0, add(add(smul(o.x, r), smul(o.y, u)), smul(o.z, fw)));
+    }
+    return g;
+}
+template <bool ORG>
+__device__ __forceinline__ Frame slot_frame(const MarchArgs& a, const OrgRay& g) {
+#if !BH_FAST
+    if constexpr (ORG) {
+        Frame f;
+        f.ro0 = g.ro0;
+        const v3 n = normalize_x(g.ro0);
+        f.cps = muls(muls(mk(-n.x, -n.y, -n.z), 1.5f), a.rs);
+        f.k = a.kfac;
+        return f;
+    } else
+#endif
+    return make_frame(a);
+}
 template <uint32_t FMT, uint32_t SF, bool SS = false, bool ITEM = false, bool LENS = false, bool SHUT = false,
-          bool RAYS = false, bool POSE = false>
+          bool RAYS = false, bool POSE = false, bool ORG = false>
 __device__ __forceinline__ void march_slot_body(const MarchArgs& A, const SlotHead& h, const float* lut,
-                                                uint32_t lane, ShutterLane* sl = nullptr, const float* dirs = nullptr) {
+                                                uint32_t lane, ShutterLane* sl = nullptr, const float* dirs = nullptr,
+                                                const float* orgs = nullptr) {
     static_assert(SS || !ITEM, "work items are supersampled tiles");
     static_assert(!LENS || (!SS && !BH_FAST), "a lens is one record per ray, in exact math");
     static_assert(!SHUT || (!SS && !ITEM && !LENS), "a shutter wave takes its ss from the argument");
     static_assert(!RAYS || (!BH_FAST && !ITEM && (!SHUT || POSE)),
                   "a ray map feeds the exact plain, supersampled and lens forms, and posed the shutter form");
     static_assert(!POSE || RAYS, "a pose turns a ray map");
+    static_assert(!ORG || (RAYS && POSE && !SHUT && !ITEM), "an origin map goes with a posed ray map, outside the shutter form");
     const uint32_t fi = h.fi, t = h.t, tx = h.tx, ty = h.ty;
     MarchArgs a = A;
     select_camera(a, h.cam);
     if (ITEM || fi != 0u) a.tile_cost = nullptr;
     const uint32_t px = tx * 8u + (lane & 7u), py = ty * 8u + (lane >> 3);
     const bool valid = px < a.width && py < a.height;
-    const Frame f = make_frame(a);
+    [[maybe_unused]] OrgRay og;  // ORG: the lane's turned direction and its origin
+    if constexpr (ORG) og = org_load(a, dirs, orgs, px, py, valid);
+    const Frame f = slot_frame<ORG>(a, og);
     RayState st;
     st.ro = f.ro0;
 #if !BH_FAST
     if constexpr (RAYS) {
         // fs_main :362 with in.camera_to_vertex = the map's vector: any bit pattern, normalised as pixel_ray's is
         v3 d = mk(0.0f, 0.0f, 1.0f);
+        if constexpr (ORG) {
+            d = og.d;
+        } else
         if constexpr (SHUT) {
             // a shutter wave: no branch on the lane -- a lane outside the frame reads pixel (0, 0), always inside
             // the map, and keeps (0, 0, 1)
@@ -167,7 +218,10 @@ __device__ __forceinline__ void march_slot_body(const MarchArgs& A, const SlotHe
         // step's own r^2 > 1 + 2^-23 at iteration 0) and |s| <= 2^30 on every lane: the step without the
         // ingoing test and the |s| guard (wave-uniform: a scalar branch)
         if constexpr (SF != SF_DYN) {
-            const bool out = (dot(f.ro0, f.ro0) > 1.01f) && (__builtin_amdgcn_ballot_w64(!(fabsf(st.s) <= 0x1p30f)) == 0ull);
+            // ORG: the origin is the lane's, so the choice is a property of the wave's valid lanes -- every one of
+            // them outside, in the one ballot; any other mix takes the general step, which covers each lane
+            const bool out = ORG ? __builtin_amdgcn_ballot_w64(!((dot(f.ro0, f.ro0) > 1.01f) & (fabsf(st.s) <= 0x1p30f))) == 0ull
+                                 : (dot(f.ro0, f.ro0) > 1.01f) && (__builtin_amdgcn_ballot_w64(!(fabsf(st.s) <= 0x1p30f)) == 0ull);
             if (__builtin_amdgcn_readfirstlane((int)out)) march_ray<SF | SF_CAM_OUT, SHUT>(a, f, st, fate, steps, lane);
             else march_ray<SF, SHUT>(a, f, st, fate, steps, lane);
         } else {
@@ -261,8 +315,9 @@ __device__ __forceinline__ void clock_end(unsigned long long* acc, const ClockSt
 // store per table and the workgroup's barrier.  (The copy by four guarded loads, each awaited, then the barrier,
 // then the chain through vector loads put about eight dependent round trips in front of pixel_ray's first
 // multiply: DESIGN.md §5 item 32.)
-template <uint32_t FMT, uint32_t SF, bool SS, bool LENS = false, bool RAYS = false, bool POSE = false>
-__device__ __forceinline__ void march_tile_wave(const MarchArgs& A, float* lut, const float* dirs = nullptr) {
+template <uint32_t FMT, uint32_t SF, bool SS, bool LENS = false, bool RAYS = false, bool POSE = false, bool ORG = false>
+__device__ __forceinline__ void march_tile_wave(const MarchArgs& A, float* lut, const float* dirs = nullptr,
+                                                const float* orgs = nullptr) {
     static_assert(WG_WAVES == 1u, "the table copy is one wave's: 64 lanes x 16 bytes per table");
     // every argument word the start branches on or indexes with, wanted here: one group of scalar loads and one
     // wait for them (left to their uses, each is loaded in the block of its use and waited for there in turn)
@@ -283,7 +338,7 @@ __device__ __forceinline__ void march_tile_wave(const MarchArgs& A, float* lut, 
     const bool probe = A.clk && ((slot + (slot >> 8)) & A.clk_mask) == 0u;
     ClockStart c0{0u, 0u};
     if (probe) c0 = clock_start();
-    if (h.ok) march_slot_body<FMT, SF, SS, false, LENS, false, RAYS, POSE>(A, h, lut, threadIdx.x & 63u, nullptr, dirs);
+    if (h.ok) march_slot_body<FMT, SF, SS, false, LENS, false, RAYS, POSE, ORG>(A, h, lut, threadIdx.x & 63u, nullptr, dirs, orgs);
     if (probe) clock_end(A.clk, c0);
 }
 
@@ -392,6 +447,19 @@ __global__ void __launch_bounds__(64 * WG_WAVES) march_tile_rays_pose_lens_kerne
     march_tile_wave<BH_OUT_RGBA32F, SF, false, true, true, true>(A, nullptr, dirs);
 }
 
+// The posed ray-map forms with an origin map (bh_render_frames_rays_origins, bh_render_lens_rays_origins): the posed
+// kernels with march_slot_body's ORG switch -- the lane's origin from a second camera-space map of the same geometry,
+// the third argument of these kernels only (MarchArgs and FrameArgs keep their layout).
+template <uint32_t FMT, uint32_t SF, bool SS>
+__global__ void __launch_bounds__(64 * WG_WAVES) march_tile_rays_org_kernel(MarchArgs A, const float* dirs, const float* orgs) {
+    __shared__ __attribute__((aligned(16))) float lut[lds_tables<FMT>()];
+    march_tile_wave<FMT, SF, SS, false, true, true, true>(A, lut, dirs, orgs);
+}
+template <uint32_t SF>
+__global__ void __launch_bounds__(64 * WG_WAVES) march_tile_rays_org_lens_kernel(MarchArgs A, const float* dirs, const float* orgs) {
+    march_tile_wave<BH_OUT_RGBA32F, SF, false, true, true, true, true>(A, nullptr, dirs, orgs);
+}
+
 // The shutter form over a posed ray map (bh_render_frames_shutter_rays): march_tile_shutter_kernel, statement for
 // statement, with the map as the second argument and march_slot's RAYS and POSE switches -- the n waves of a
 // workgroup read the same 12 bytes per pixel and differ in their FrameArgs' pose.  Its barrier discipline is that
@@ -497,6 +565,13 @@ inline void launch_tile_rays_schedule(K kernel, const MarchArgs& a, const float*
     const uint32_t waves = a.n_tiles * a.n_frames;
     const uint32_t blocks = (waves + (WG_WAVES - 1u)) / WG_WAVES;
     hipLaunchKernelGGL(kernel, dim3(blocks), dim3(64u * WG_WAVES), 0, s, a, dirs);
+}
+// ... with an origin map: the two maps as the second and third arguments
+template <class K>
+inline void launch_tile_rays_org_schedule(K kernel, const MarchArgs& a, const float* dirs, const float* orgs, hipStream_t s) {
+    const uint32_t waves = a.n_tiles * a.n_frames;
+    const uint32_t blocks = (waves + (WG_WAVES - 1u)) / WG_WAVES;
+    hipLaunchKernelGGL(kernel, dim3(blocks), dim3(64u * WG_WAVES), 0, s, a, dirs, orgs);
 }
 // ... its shutter form: one workgroup of 2^ln waves per (output frame, tile); a.n_frames counts cameras
 template <uint32_t FMT, uint32_t SF>

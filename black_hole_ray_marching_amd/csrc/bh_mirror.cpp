@@ -30,6 +30,26 @@ int bh_ray_pose_apply_host(const bh_ray_pose* pose, const float* dirs, uint32_t 
     return BH_OK;
 }
 
+// The origin-map kernels' ray origin on the host (org_frame, bh_march_tile.hpp): pos + ((ox r + oy u) + oz f) per
+// component, one statement per operation.  Each pixel's three inputs are read before its outputs are written, so
+// `out` may be `origins`.
+int bh_ray_origins_apply_host(const bh_ray_pose* pose, const float* origins, uint32_t width, uint32_t height, float* out) {
+    if (!pose || !origins || !out || width == 0 || height == 0 || width > 65536u || height > 65536u) return bad_arg(__func__, __LINE__);
+    const size_t n = (size_t)width * height;
+    for (size_t i = 0; i < n; ++i) {
+        const float ox = origins[3u * i], oy = origins[3u * i + 1u], oz = origins[3u * i + 2u];
+        for (int k = 0; k < 3; ++k) {
+            const float a = ox * pose->r[k];
+            const float b = oy * pose->u[k];
+            const float ab = a + b;
+            const float c = oz * pose->f[k];
+            const float w = ab + c;
+            out[3u * i + (size_t)k] = pose->pos[k] + w;
+        }
+    }
+    return BH_OK;
+}
+
 // The supersampled march kernel's epilogue on the host: the functions of bh_ss.hpp that each lane of a wave
 // runs (ss_resolve_store, bh_march_resolve.hpp), run here wave by wave over 64-entry arrays -- one 8x8 tile of the
 // virtual frame per wave, invalid lanes 0, every lane taking each butterfly level together.

@@ -342,24 +342,24 @@ def _check_size(t, need: int, name: str, what: str = "render") -> None:
         raise BhError(_abi.BH_ERR_INVALID_ARG, f"{what}: {name} must be contiguous")
 
 
-def _check_dirs(dirs, height: int, width: int, what: str) -> None:
+def _check_dirs(dirs, height: int, width: int, what: str, name: str = "dirs") -> None:
     """A ray map as bh_render_rays takes it: a contiguous float32 device tensor of shape (height, width, 3) (raw
-    pointers are trusted)."""
+    pointers are trusted).  `name`: the argument checked ("origins": an origin map, the same checks)."""
     if dirs is None:
-        raise BhError(_abi.BH_ERR_INVALID_ARG, f"{what}: dirs is required")
+        raise BhError(_abi.BH_ERR_INVALID_ARG, f"{what}: {name} is required")
     if isinstance(dirs, int):
         return
     if not hasattr(dirs, "data_ptr") or not hasattr(dirs, "is_cuda"):
-        raise BhError(_abi.BH_ERR_INVALID_ARG, f"{what}: dirs must be a device tensor (upload a raymap.* array first), "
+        raise BhError(_abi.BH_ERR_INVALID_ARG, f"{what}: {name} must be a device tensor (upload a raymap.* array first), "
                                                f"got {type(dirs).__name__}")
     if tuple(dirs.shape) != (height, width, 3):
-        raise BhError(_abi.BH_ERR_INVALID_ARG, f"{what}: dirs must be ({height}, {width}, 3), got {tuple(dirs.shape)}")
+        raise BhError(_abi.BH_ERR_INVALID_ARG, f"{what}: {name} must be ({height}, {width}, 3), got {tuple(dirs.shape)}")
     if dirs.element_size() != 4 or not dirs.dtype.is_floating_point:
-        raise BhError(_abi.BH_ERR_INVALID_ARG, f"{what}: dirs must be float32, got {dirs.dtype}")
+        raise BhError(_abi.BH_ERR_INVALID_ARG, f"{what}: {name} must be float32, got {dirs.dtype}")
     if not dirs.is_contiguous():
-        raise BhError(_abi.BH_ERR_INVALID_ARG, f"{what}: dirs must be contiguous")
+        raise BhError(_abi.BH_ERR_INVALID_ARG, f"{what}: {name} must be contiguous")
     if not dirs.is_cuda:
-        raise BhError(_abi.BH_ERR_INVALID_ARG, f"{what}: dirs must be in device memory")
+        raise BhError(_abi.BH_ERR_INVALID_ARG, f"{what}: {name} must be in device memory")
 
 
 def _pos_arg(pos, what: str):
@@ -641,16 +641,22 @@ class Scene:
         check(self.lib.bh_render_rays(self._ctx, p, C.byref(self.uniforms.to_c()), C.byref(d), _ptr(dirs), k,
                                       _stream_handle(stream)), "bh_render_rays")
 
-    def render_frames_rays(self, dirs, outputs, blackout_outputs=None, *, poses, fmt: int = BH_OUT_RGBA32F,
-                           ss: int = 1, stream=None, schedule: int = 0, dbg_n_rk=None, dbg_fate=None,
-                           width: int | None = None, height: int | None = None) -> None:
+    def render_frames_rays(self, dirs, outputs, blackout_outputs=None, *, poses, origins=None,
+                           fmt: int = BH_OUT_RGBA32F, ss: int = 1, stream=None, schedule: int = 0, dbg_n_rk=None,
+                           dbg_fate=None, width: int | None = None, height: int | None = None) -> None:
         """bh_render_frames_rays: render_frames over one ray map in CAMERA space -- frame i is render_rays of the map
         turned by poses[i] (raymap.pose / raymap.pose_of; include/bh_render.h, bh_ray_pose) from its position, into
         outputs[i] / blackout_outputs[i].  `dirs` as render_rays takes it, shared by every frame; up to
-        BH_MAX_FRAMES frames; dbg_n_rk / dbg_fate: per-frame lists (ss == 1)."""
+        BH_MAX_FRAMES frames; dbg_n_rk / dbg_fate: per-frame lists (ss == 1).
+        `origins` (an origin map: a tensor as `dirs`, of its shape, in camera space; raymap.thin_lens, ods,
+        orthographic, stereo build pairs): bh_render_frames_rays_origins -- every ray starts at its pose's position
+        plus its own turned origin."""
         what = "render_frames_rays"
         k = _ss_arg(ss)
         n = len(outputs)
+        if origins is not None and poses is None:
+            raise BhError(_abi.BH_ERR_INVALID_ARG, f"{what}: origins are in camera space and need a pose: give "
+                                                   "poses=[raymap.pose(pos)] for the unit axes at pos")
         per = lambda v: v if v is not None else [None] * n  # noqa: E731
         bos, nrks, fates = per(blackout_outputs), per(dbg_n_rk), per(dbg_fate)
         if not (len(bos) == len(nrks) == len(fates) == n):
@@ -660,6 +666,12 @@ class Scene:
                                                        BH_LAYOUT_ROWMAJOR, 0, 1, width, height, schedule, None)
                                             for i in range(n)])
         _check_dirs(dirs, descs[0].height * k, descs[0].width * k, what)
+        if origins is not None:
+            _check_dirs(origins, descs[0].height * k, descs[0].width * k, what, "origins")
+            check(self.lib.bh_render_frames_rays_origins(self._ctx, n, ps, C.byref(self.uniforms.to_c()), descs,
+                                                         _ptr(dirs), _ptr(origins), k, _stream_handle(stream)),
+                  "bh_render_frames_rays_origins")
+            return
         check(self.lib.bh_render_frames_rays(self._ctx, n, ps, C.byref(self.uniforms.to_c()), descs, _ptr(dirs), k,
                                              _stream_handle(stream)), "bh_render_frames_rays")
 
@@ -696,13 +708,14 @@ class Scene:
               "bh_render_frames_shutter_rays")
 
     def render_lens(self, lens, *, width: int | None = None, height: int | None = None, schedule: int = 0,
-                    stream=None, dirs=None, pos=None, pose=None) -> None:
+                    stream=None, dirs=None, pos=None, pose=None, origins=None) -> None:
         """bh_render_lens: march this scene's camera once into `lens`, a device buffer of height x width records
         (u, v) of 8 bytes (e.g. a float32 tensor (H, W, 2)) -- the view, without any sky.  Exact math, whatever
         the scene's math mode.  Shade it with shade(), as often and with as many skies as wanted.
         `dirs` (a ray map as render_rays takes it, (height, width, 3)): bh_render_lens_rays, the view of that map
         from `pos` (default: the scene camera's position); with `pose` (raymap.pose) instead of `pos`,
-        bh_render_lens_rays_posed: the view of the camera-space map `dirs` turned by that pose."""
+        bh_render_lens_rays_posed: the view of the camera-space map `dirs` turned by that pose; with `origins` (an
+        origin map of `dirs`' shape) beside the pose, bh_render_lens_rays_origins."""
         d = _abi.bh_render_desc()
         d.width, d.height = width or self.width, height or self.height
         d.max_iters, d.scene_flags = self.max_iters, self.scene_flags
@@ -710,11 +723,20 @@ class Scene:
         if lens is None:
             raise BhError(_abi.BH_ERR_INVALID_ARG, "render_lens: lens is required")
         _check_size(lens, d.width * d.height * 8, "lens", "render_lens")
+        if origins is not None and pose is None:
+            raise BhError(_abi.BH_ERR_INVALID_ARG, "render_lens: origins are in camera space and need a pose: give "
+                                                   "pose=raymap.pose(pos) for the unit axes at pos")
         if pose is not None:
             if pos is not None:
                 raise BhError(_abi.BH_ERR_INVALID_ARG, "render_lens: give pos or pose, not both (a pose holds its position)")
             _check_dirs(dirs, d.height, d.width, "render_lens")
             ps = _poses_arg([pose], 1, "render_lens")
+            if origins is not None:
+                _check_dirs(origins, d.height, d.width, "render_lens", "origins")
+                check(self.lib.bh_render_lens_rays_origins(self._ctx, ps, C.byref(self.uniforms.to_c()), C.byref(d),
+                                                           _ptr(dirs), _ptr(origins), _ptr(lens),
+                                                           _stream_handle(stream)), "bh_render_lens_rays_origins")
+                return
             check(self.lib.bh_render_lens_rays_posed(self._ctx, ps, C.byref(self.uniforms.to_c()), C.byref(d),
                                                      _ptr(dirs), _ptr(lens), _stream_handle(stream)),
                   "bh_render_lens_rays_posed")

@@ -524,8 +524,8 @@ int bh_lens_shade_mip_host(const bh_lens_px* lens, uint32_t width, uint32_t heig
  * not finite (the zero vector, an inf, a NaN) renders what the WGSL gives that normalised direction; a kernel reads
  * the 12 bytes of its own pixel and nothing else of the map, whatever they hold.  One origin per frame: `pos`.
  * Exact math only.  Several frames per call, a moving camera and shutter renders over one map: the posed forms
- * below (bh_ray_pose).  Not built for ray maps: adaptive renders, the tiled layouts, shards and partitions, fast
- * math, a per-ray origin.
+ * below (bh_ray_pose); an origin per ray beside a posed map: the origin maps below them.  Not built for ray maps:
+ * adaptive renders, the tiled layouts, shards and partitions, fast math.
  *
  * bh_render_rays: bh_render (ss == 1; the dbg_* outputs are allowed) or bh_render_ss (ss = k in {2, 4, 8}: `dirs_dev`
  * is the map of the virtual frame, k*height x k*width x 3, its samples resolved by bh_render_ss's normative tree and
@@ -592,6 +592,47 @@ int bh_render_lens_rays_posed(bh_ctx* ctx, const bh_ray_pose* pose, const bh_uni
  * size; may be `dirs` itself) -- the world-space map whose bh_render_rays, from pose->pos, is the posed render of
  * `dirs`, bit for bit.  BH_ERR_INVALID_ARG: a NULL pointer, a side of 0 or above 65536. */
 int bh_ray_pose_apply_host(const bh_ray_pose* pose, const float* dirs, uint32_t width, uint32_t height, float* out_dirs);
+
+/* Origin maps: a ray origin per pixel beside a posed direction map -- a finite aperture (thin-lens depth of field: the
+ * k x k samples of ss are the lens samples), an eye per column (omnidirectional stereo), an orthographic view, a
+ * side-by-side stereo pair in one frame.  An origin map (normative) is a device array of height x width x 3 fp32
+ * values, row-major, 12 bytes per pixel, 4-byte aligned, of the geometry of the direction map it accompanies (with
+ * ss = k both are the virtual frame's), in CAMERA space like that map.  For camera i and pixel (x, y), with
+ * (ox, oy, oz) = origins[y][x], (mx, my, mz) = dirs[y][x] and pose[i] = (pos, r, u, f):
+ *     w[c]   = (ox * r[c] + oy * u[c]) + oz * f[c]      five fp32 roundings, this association, no contraction
+ *     ro0[c] = pos[c] + w[c]                            one more rounding
+ *     d[c]   = (mx * r[c] + my * u[c]) + mz * f[c]      as bh_render_frames_rays
+ * and the pixel is fs_main with camera.pos = ro0 and in.camera_to_vertex = d, that is get_col(Photon(ro0,
+ * normalize(d))): the ray's constant is |ro0 x rd0|^2 and the photon-sphere marker's centre ((-normalize(ro0)) * 1.5)
+ * * RS, with normalize(v) = v / sqrt((x x + y y) + z z) in IEEE fp32 -- what every frame's position gets today, here
+ * per ray.  The origin bytes are an input like the direction bytes, any bit pattern: an origin at 0 (a NaN centre, a
+ * zero constant), inside the unit sphere or non-finite renders what the WGSL gives that photon; a kernel reads the 12
+ * bytes of its own pixel of each map and nothing else of either.
+ * Identity: an origin map of all +0 renders bh_render_frames_rays' bytes for every pose whose nine basis floats are
+ * finite and whose position has no -0 component: pos + (+0) = pos.  NOT promised otherwise: a -0 component of pos
+ * becomes +0 ((-0) + (+0) = +0, which changes no radius but can change the sign of a zero downstream), and 0 * inf
+ * is NaN, so a non-finite basis float makes every origin NaN.
+ *
+ * bh_render_frames_rays_origins: bh_render_frames_rays with origins_dev after dirs_dev -- n_frames poses over the one
+ * pair of maps, ss in {1, 2, 4, 8}, the three formats, one or two targets, the dbg_* outputs where that call allows
+ * them.  bh_render_lens_rays_origins: bh_render_lens_rays_posed likewise.  Refusals: those of the call it extends, and
+ * BH_ERR_INVALID_ARG for a NULL or misaligned origins_dev; BH_ERR_UNSUPPORTED comes with a sentence in
+ * bh_last_error() that starts with the function's name.  A refused call launches nothing and writes nothing.  Graph
+ * contract, temporal order: bh_render_rays' -- the launch is a ray-map launch of its geometry and stream, and the
+ * origin map's address enters the repeated-frame key beside the direction map's (a map rewritten in place may meet a
+ * stale order: time, never bytes).  Not built with an origin map: the shutter form, adaptive renders, the tiled
+ * layouts, shards and partitions, fast math, the pair and persistent schedules. */
+int bh_render_frames_rays_origins(bh_ctx* ctx, uint32_t n_frames, const bh_ray_pose* poses, const bh_uniforms* uniforms,
+                                  const bh_render_desc* descs, const float* dirs_dev, const float* origins_dev,
+                                  uint32_t ss, void* hip_stream);
+int bh_render_lens_rays_origins(bh_ctx* ctx, const bh_ray_pose* pose, const bh_uniforms* uniforms,
+                                const bh_render_desc* desc, const float* dirs_dev, const float* origins_dev,
+                                bh_lens_px* out_lens, void* hip_stream);
+/* Host only: ro0 above in plain C++ over a host origin map (height * width * 3 floats) into out_origins (the same
+ * size; may be `origins` itself) -- the world-space origins of the pose's rays, bit for bit what the kernels form.
+ * BH_ERR_INVALID_ARG: a NULL pointer, a side of 0 or above 65536. */
+int bh_ray_origins_apply_host(const bh_ray_pose* pose, const float* origins, uint32_t width, uint32_t height,
+                              float* out_origins);
 
 /* Bloom::render (src/bloom.rs:53-71): the reference's Kawase bloom + remix chain over the scene's two
  * targets, on BGRA8-sRGB images (bh_render with BH_OUT_BGRA8_SRGB): `col` (full_image_input),

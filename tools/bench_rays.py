@@ -19,6 +19,13 @@ Posed ray maps (one raymap.perspective map of camera A's field of view in camera
             it also runs against an older library through BH_LIB).
   shutter   Scene.render_shutter_rays of n = 4, 8, 16 sub-frame poses against Scene.render_frames_rays of the same poses
             into n frames.
+Origin maps (--legs origins, not in the default list; camera A's orbit as above, RGBA16F and BGRA8, both targets).  The
+yardstick is always the existing posed form, interleaved in the same process:
+  origins1   Scene.render_frames_rays(origins = an all-zero map), n = 1, against the same call without origins: the same
+             rays and output bytes, so the ratio is the cost of the form alone (per-lane ro0 and cps, 12 more bytes per ray).
+  origins32  the same with 32 frames per launch.
+  thinlens   (1920x1080 only) raymap.thin_lens at ss = 4 against the posed ss = 4 render of raymap.perspective.
+  ods        (4096x2048 only) raymap.ods against the posed render of raymap.equirect.
     python tools/bench_rays.py [--cases 1920x1080:256,4096x2048:512] [--frames 20] [--rounds 5] [--legs LIST] [--out FILE]"""
 import argparse
 import json
@@ -42,11 +49,12 @@ p.add_argument("--rounds", type=int, default=5)
 p.add_argument("--warm-ms", type=float, default=400.0, help="warm-up of both legs before a pair's first window")
 p.add_argument("--out", default=None, help="also append the JSON rows to this file")
 UNPOSED, POSED = {"rays", "equirect", "lens"}, {"pose1", "pose32", "path32", "torch32", "shutter"}
-p.add_argument("--legs", default=",".join(sorted(UNPOSED | POSED)), help="comma list of the leg pairs to run")
+ORIGINS = {"origins"}
+p.add_argument("--legs", default=",".join(sorted(UNPOSED | POSED)), help="comma list of the leg pairs to run (and: origins)")
 args = p.parse_args()
 LEGS = set(args.legs.split(","))
-if LEGS - UNPOSED - POSED:
-    p.error(f"--legs: no such leg pair: {sorted(LEGS - UNPOSED - POSED)}")
+if LEGS - UNPOSED - POSED - ORIGINS:
+    p.error(f"--legs: no such leg pair: {sorted(LEGS - UNPOSED - POSED - ORIGINS)}")
 DEGREES, N_BATCH = 0.2, 32
 if not torch.cuda.is_available():
     sys.exit("bench_rays: no GPU (there is no CPU timing path)")
@@ -201,6 +209,50 @@ for case in args.cases.split(",") if POSED & LEGS else []:
         del fcol, fbo
         torch.cuda.empty_cache()
     scene.close()
+
+# ---- origin maps (bh_render_frames_rays_origins): the posed form of the same maps is the yardstick ---------------------
+for case in args.cases.split(",") if ORIGINS & LEGS else []:
+    size, cap = case.split(":")
+    W, H = (int(v) for v in size.split("x"))
+    cap = int(cap)
+    scene = bh.Scene(W, H, sky=sky, max_iters=cap, math=bh.BH_MATH_EXACT)
+    s = torch.cuda.Stream()
+    acc = torch.zeros(128, dtype=torch.int64, device="cuda")
+    tags = dict(width=W, height=H, max_iters=cap)
+    local = torch.from_numpy(raymap.perspective(W, H, scene.camera.fovy)).cuda()
+    zero = torch.zeros((H, W, 3), dtype=torch.float32, device="cuda")
+    cams, poses = orbit_poses(scene, W, H, N_BATCH, 1)
+    special = []  # (what, dirs of the new form, its origins, the yardstick's dirs, ss)
+    if (W, H) == (1920, 1080):
+        d, o = raymap.thin_lens(W, H, scene.camera.fovy, 0.05, 20.0, k=4)
+        special.append(("thinlens", torch.from_numpy(d).cuda(), torch.from_numpy(o).cuda(),
+                        torch.from_numpy(raymap.perspective(4 * W, 4 * H, scene.camera.fovy)).cuda(), 4))
+        del d, o
+    if (W, H) == (4096, 2048):
+        d, o = raymap.ods(W, H, 0.065, "left")
+        dd = torch.from_numpy(d).cuda()
+        special.append(("ods", dd, torch.from_numpy(o).cuda(), dd, 1))
+        del d, o
+    for name, (fmt, dt) in FMTS.items():
+        fcol = [torch.empty((H, W, 4), dtype=dt, device="cuda") for _ in range(N_BATCH)]
+        fbo = [torch.empty((H, W, 4), dtype=dt, device="cuda") for _ in range(N_BATCH)]
+        for n in (1, N_BATCH):
+            pair(f"origins{n}", scene, s, acc,
+                 lambda st: scene.render_frames_rays(local, fcol[:n], fbo[:n], poses=poses[:n], origins=zero, fmt=fmt, stream=st),
+                 lambda st: scene.render_frames_rays(local, fcol[:n], fbo[:n], poses=poses[:n], fmt=fmt, stream=st),
+                 format=name, targets=2, map="perspective", n_frames=n, a="render_frames_rays, zero origins",
+                 b="render_frames_rays", **tags)
+        for what, da, oa, db, k in special:
+            pair(what, scene, s, acc,
+                 lambda st: scene.render_frames_rays(da, fcol[:1], fbo[:1], poses=poses[:1], origins=oa, fmt=fmt, ss=k, stream=st),
+                 lambda st: scene.render_frames_rays(db, fcol[:1], fbo[:1], poses=poses[:1], fmt=fmt, ss=k, stream=st),
+                 format=name, targets=2, ss=k, n_frames=1, a=f"render_frames_rays, raymap.{what.replace('thinlens', 'thin_lens')}",
+                 b="render_frames_rays, " + ("raymap.perspective" if what == "thinlens" else "raymap.equirect"), **tags)
+        del fcol, fbo
+        torch.cuda.empty_cache()
+    del special, local, zero
+    scene.close()
+    torch.cuda.empty_cache()
 if args.out:
     Path(args.out).parent.mkdir(parents=True, exist_ok=True)
     with open(args.out, "a") as f:

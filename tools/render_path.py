@@ -20,7 +20,16 @@ The sky filtered through its mip chain: per frame a lens render and a filtered s
 Another projection than the reference's pinhole: the frames march one ray map in camera space, uploaded once, each
 with its camera's pose (bh_render_frames_rays, several frames per launch) -- a 360-degree equirectangular frame, a
 fisheye:DEG dome frame, a perspective:DEG lens of another field of view.  With --shutter N every frame averages N
-sub-frame poses over the same map (bh_render_frames_shutter_rays)."""
+sub-frame poses over the same map (bh_render_frames_shutter_rays).
+
+    python tools/render_path.py --projection ods:0.065 --width 4096 --height 2048
+Omnidirectional stereo, the 360-degree format of VR players: two frame sets, OUT/left and OUT/right, each column's eye
+on the viewing circle of diameter IPD (raymap.ods; an origin per ray beside the equirect map:
+bh_render_frames_rays_origins).
+
+    python tools/render_path.py --projection perspective:60 --ss 4 --aperture 0.05 --focus 20
+Depth of field: the ss x ss samples of a pixel start on a thin lens of radius A and meet at distance D
+(raymap.thin_lens).  The direction and origin maps are uploaded once per path."""
 import argparse
 import dataclasses
 import json
@@ -57,30 +66,49 @@ p.add_argument("--shutter-frac", type=float, default=0.5, metavar="S",
 p.add_argument("--sky-filter", choices=["none", "mip"], default="none",
                help="mip: every frame is a lens render (bh_render_lens) shaded through the sky's mip chain, the level "
                     "taken from the lens (bh_shade_lens_mip); with --ss 1, 2 or 4 and with --sky-frames")
-p.add_argument("--projection", default=None, metavar="{pinhole,equirect,fisheye:DEG,perspective:DEG}",
+p.add_argument("--aperture", type=float, default=None, metavar="A",
+               help="with --projection perspective:DEG: a thin lens of radius A (world units) focused at --focus; the "
+                    "--ss x --ss samples of a pixel are its lens samples")
+p.add_argument("--focus", type=float, default=None, metavar="D", help="with --aperture: the distance of the plane in focus")
+p.add_argument("--projection", default=None, metavar="{pinhole,equirect,fisheye:DEG,perspective:DEG,ods:IPD}",
                help="march a ray map instead of the camera's own rays: the map of the (ss x) frame is built and uploaded "
                     "once, in the camera's frame, and every frame passes its camera's pose (bh_render_frames_rays; "
                     "with --shutter, bh_render_frames_shutter_rays); pinhole is the camera's own projection through a "
                     "per-frame map of the library's helper (bh_render_rays: the same bytes); DEG: the full field of "
-                    "view of a fisheye (up to 360), the vertical one of a perspective lens (below 180)")
+                    "view of a fisheye (up to 360), the vertical one of a perspective lens (below 180); ods:IPD: "
+                    "omnidirectional stereo, two frame sets (left, right) with the eyes IPD apart (world units)")
 args = p.parse_args()
 mip = args.sky_filter == "mip"
 proj, proj_deg = None, None
 if args.projection is not None:
     proj, _, deg = args.projection.partition(":")
-    if proj not in ("pinhole", "equirect", "fisheye", "perspective") or bool(deg) != (proj in ("fisheye", "perspective")):
-        p.error("--projection is one of pinhole, equirect, fisheye:DEG, perspective:DEG")
+    if proj not in ("pinhole", "equirect", "fisheye", "perspective", "ods") or bool(deg) != (proj in ("fisheye", "perspective", "ods")):
+        p.error("--projection is one of pinhole, equirect, fisheye:DEG, perspective:DEG, ods:IPD")
     try:
         proj_deg = float(deg) if deg else None
     except ValueError:
-        p.error(f"--projection {proj}:DEG needs a number of degrees, got {deg!r}")
-    if proj_deg is not None and not 0.0 < proj_deg <= (360.0 if proj == "fisheye" else 179.9):
+        p.error(f"--projection {proj}:{'IPD' if proj == 'ods' else 'DEG'} needs a number, got {deg!r}")
+    if proj == "ods" and not 0.0 <= proj_deg < float("inf"):
+        p.error("--projection ods: IPD must be a finite distance, 0 or more")
+    if proj != "ods" and proj_deg is not None and not 0.0 < proj_deg <= (360.0 if proj == "fisheye" else 179.9):
         p.error(f"--projection {proj}: DEG must lie in (0, {360 if proj == 'fisheye' else 179.9}]")
     if args.adaptive is not None:
         sys.exit("render_path: --projection does not combine with --adaptive (ray maps are not built for adaptive renders)")
     if args.shutter > 1 and proj == "pinhole":
         sys.exit("render_path: --projection pinhole does not combine with --shutter (its map is per camera; the plain "
                  "--shutter is the same picture)")
+thin = args.aperture is not None
+if thin or args.focus is not None:
+    if not thin or args.focus is None or proj != "perspective":
+        p.error("--aperture A and --focus D go together, with --projection perspective:DEG (and --ss k: the lens samples)")
+    if not (0.0 <= args.aperture < float("inf") and 0.0 < args.focus < float("inf")):
+        p.error("--aperture must be 0 or more and --focus positive")
+if thin or proj == "ods":  # a ray origin per pixel: what the origin-map kernels are not built for
+    if args.shutter > 1 or args.adaptive is not None:
+        sys.exit("render_path: --projection ods and --aperture do not combine with --shutter or --adaptive (an origin "
+                 "map has no shutter or adaptive form)")
+    if args.sky_filter == "mip" or args.sky_frames:
+        sys.exit("render_path: --projection ods and --aperture do not combine with --sky-filter mip or --sky-frames")
 if mip and (args.shutter > 1 or args.adaptive is not None):
     sys.exit("render_path: --sky-filter mip does not combine with --shutter or --adaptive (the filter is a lens shade)")
 if mip and args.ss == 8:
@@ -139,7 +167,18 @@ def shutter_cameras(frame_cam):
 
 
 local_map, map_uploads = None, 0
-if proj in ("equirect", "fisheye", "perspective"):  # once per frame size, in the camera's own frame (r, u, f)
+views = None  # with an origin per ray: [(frame set's sub-directory, the origin map)] over local_map
+if proj == "ods":  # one equirect map, one origin map per eye
+    d, left = raymap.ods(W * args.ss, H * args.ss, proj_deg, "left")
+    local_map = torch.from_numpy(d).cuda()
+    views = [("left", torch.from_numpy(left).cuda()),
+             ("right", torch.from_numpy(raymap.ods(W * args.ss, H * args.ss, proj_deg, "right")[1]).cuda())]
+    map_uploads += 3
+elif thin:  # the virtual frame's directions and lens points
+    d, o = raymap.thin_lens(W, H, np.radians(proj_deg), args.aperture, args.focus, k=args.ss)
+    local_map, views = torch.from_numpy(d).cuda(), [("", torch.from_numpy(o).cuda())]
+    map_uploads += 2
+elif proj in ("equirect", "fisheye", "perspective"):  # once per frame size, in the camera's own frame (r, u, f)
     kw, kh = args.ss * W, args.ss * H
     m = (raymap.equirect(kw, kh) if proj == "equirect" else raymap.fisheye(kw, kh, np.radians(proj_deg))
          if proj == "fisheye" else raymap.perspective(kw, kh, np.radians(proj_deg)))
@@ -204,14 +243,17 @@ while posed and f0 < args.frames:
         poses.append([raymap.pose_of(c) for c in (shutter_subcameras(cam) if args.shutter > 1 else [cam])])
         log.append({"frame": f, "pos": cam.pos, "dir": cam.dir, "moved": moved})
     cols, bos = [t[0] for t in targets[:nb]], [t[1] for t in targets[:nb]]
-    if args.shutter > 1:
-        scene.render_frames_shutter_rays(local_map, cols, bos, poses=poses, fmt=bh.BH_OUT_BGRA8_SRGB, ss=args.ss)
-    else:
-        scene.render_frames_rays(local_map, cols, bos, poses=[g[0] for g in poses], fmt=bh.BH_OUT_BGRA8_SRGB, ss=args.ss)
-    for i in range(nb):
-        scene.bloom(cols[i], bos[i], surf)
-        if not args.no_png:
-            write_png(out_dir / f"frame_{f0 + i:04d}.png", surf.cpu().numpy())
+    for sub, origin_map in views or [("", None)]:
+        if args.shutter > 1:
+            scene.render_frames_shutter_rays(local_map, cols, bos, poses=poses, fmt=bh.BH_OUT_BGRA8_SRGB, ss=args.ss)
+        else:
+            scene.render_frames_rays(local_map, cols, bos, poses=[g[0] for g in poses], origins=origin_map,
+                                     fmt=bh.BH_OUT_BGRA8_SRGB, ss=args.ss)
+        for i in range(nb):
+            scene.bloom(cols[i], bos[i], surf)
+            if not args.no_png:
+                (out_dir / sub).mkdir(parents=True, exist_ok=True)
+                write_png(out_dir / sub / f"frame_{f0 + i:04d}.png", surf.cpu().numpy())
     f0 += nb
 for f in range(0 if args.sky_frames or posed else args.frames):
     for k, a, b in keys:
