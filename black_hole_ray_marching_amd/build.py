@@ -13,6 +13,7 @@ writes DIR/libbh_render.so and its objects (DIR/*.o, what tools/kernel_text_cmp.
 from __future__ import annotations
 
 import os
+import re
 import shutil
 import subprocess
 import sys
@@ -34,44 +35,38 @@ ARCH = os.environ.get("BH_OFFLOAD_ARCH", "gfx950")
 HIPCC = os.environ.get("HIPCC", shutil.which("hipcc") or "/opt/rocm/bin/hipcc")
 
 COMMON = ["-O3", "-fPIC", "-std=c++17", f"--offload-arch={ARCH}", "-Wall", "-Wno-unused-function"]
+# The exact kernels' arithmetic: one rounding per op, IEEE division and square root.  No SLP packing: packed FP32 has
+# no throughput advantage on gfx950 (tools/ubench/valu_rates.hip).  Alone, these are the flags of the scheduled builds
+# (LLVM's machine schedulers: shorter per-step latency for tail-bound frames).
+EXACT = ["-ffp-contract=off", "-fhip-fp32-correctly-rounded-divide-sqrt", "-fno-slp-vectorize"]
+# The issue-order builds.  No machine scheduling (pre- or post-RA): the step's source order issues faster than the
+# scheduler's interleavings (0.687 -> 0.644 ms headline, A/B r01).  No machine LICM: it hoists
+# loop-invariant materialisations (e.g. the shading's f64 constants) out of the frame-independent loops and lengthens
+# live ranges; off, 0.6226 -> 0.6168 ms per frame headline, 1920x1080 0.162 -> 0.159 ms (A/B r02,
+# profiles/r02b/ab_nolicm.log; the scheduled builds got slower with it, 0.736 -> 0.768 ms at cap 1000, so they keep
+# LICM).
+EXACT_ISSUE_ORDER = EXACT + ["-mllvm", "-enable-misched=0", "-mllvm", "-enable-post-misched=0",
+                             "-mllvm", "-disable-machine-licm"]
 # per-translation-unit floating-point contracts (DESIGN.md "Math modes")
 TU_FLAGS = {
-    # packed FP32 has no throughput advantage on gfx950 (tools/ubench/valu_rates.hip): no SLP packing.
-    # No machine scheduling (pre- or post-RA): the step's source order issues faster than the
-    # scheduler's interleavings (0.687 -> 0.644 ms headline, A/B r01).  No
-    # machine LICM: it hoists loop-invariant materialisations (e.g. the shading's f64 constants) out of
-    # the frame-independent loops and lengthens live ranges; off, 0.6226 -> 0.6168 ms per frame
-    # headline, 1920x1080 0.162 -> 0.159 ms (A/B r02, profiles/r02b/ab_nolicm.log; the scheduled
-    # build below got slower with it, 0.736 -> 0.768 ms at cap 1000, so it keeps LICM).
-    "bh_march_exact.hip": ["-ffp-contract=off", "-fhip-fp32-correctly-rounded-divide-sqrt", "-fno-slp-vectorize",
-                           "-mllvm", "-enable-misched=0", "-mllvm", "-enable-post-misched=0",
-                           "-mllvm", "-disable-machine-licm"],
-    # the same kernels WITH machine scheduling: shorter per-step latency for tail-bound frames
-    "bh_march_exact_lat.hip": ["-ffp-contract=off", "-fhip-fp32-correctly-rounded-divide-sqrt", "-fno-slp-vectorize"],
+    "bh_march_exact.hip": EXACT_ISSUE_ORDER,
+    "bh_march_exact_lat.hip": EXACT,
     # the fast (tolerance) kernels: no machine scheduling either (0.468 -> 0.440 ms headline, A/B r01)
     "bh_march_fast.hip": ["-ffp-contract=fast", "-fno-hip-fp32-correctly-rounded-divide-sqrt",
                           "-mllvm", "-enable-misched=0", "-mllvm", "-enable-post-misched=0"],
     # the scheduled build of the adaptive render's work-list march alone, without machine LICM (see the file)
-    "bh_march_refine_lat.hip": ["-ffp-contract=off", "-fhip-fp32-correctly-rounded-divide-sqrt", "-fno-slp-vectorize",
-                                "-mllvm", "-disable-machine-licm"],
-    # the ray-map march (bh_render_rays): the two exact builds' flags, in units of their own
-    "bh_march_rays.hip": ["-ffp-contract=off", "-fhip-fp32-correctly-rounded-divide-sqrt", "-fno-slp-vectorize",
-                          "-mllvm", "-enable-misched=0", "-mllvm", "-enable-post-misched=0",
-                          "-mllvm", "-disable-machine-licm"],
-    "bh_march_rays_lat.hip": ["-ffp-contract=off", "-fhip-fp32-correctly-rounded-divide-sqrt", "-fno-slp-vectorize"],
-    # the posed ray-map march (bh_render_frames_rays, its shutter and lens forms): the same two sets of flags
-    "bh_march_rays_pose.hip": ["-ffp-contract=off", "-fhip-fp32-correctly-rounded-divide-sqrt", "-fno-slp-vectorize",
-                               "-mllvm", "-enable-misched=0", "-mllvm", "-enable-post-misched=0",
-                               "-mllvm", "-disable-machine-licm"],
-    "bh_march_rays_pose_lat.hip": ["-ffp-contract=off", "-fhip-fp32-correctly-rounded-divide-sqrt", "-fno-slp-vectorize"],
-    # the posed ray-map march with an origin map (bh_render_frames_rays_origins, its lens form): the same two sets
-    "bh_march_rays_org.hip": ["-ffp-contract=off", "-fhip-fp32-correctly-rounded-divide-sqrt", "-fno-slp-vectorize",
-                              "-mllvm", "-enable-misched=0", "-mllvm", "-enable-post-misched=0",
-                              "-mllvm", "-disable-machine-licm"],
-    "bh_march_rays_org_lat.hip": ["-ffp-contract=off", "-fhip-fp32-correctly-rounded-divide-sqrt", "-fno-slp-vectorize"],
+    "bh_march_refine_lat.hip": EXACT + ["-mllvm", "-disable-machine-licm"],
+    # the ray-map march (bh_render_rays), the posed one (bh_render_frames_rays, its shutter and lens forms) and the
+    # one with an origin map (bh_render_frames_rays_origins, its lens form): the two exact builds, in units of their own
+    "bh_march_rays.hip": EXACT_ISSUE_ORDER,
+    "bh_march_rays_lat.hip": EXACT,
+    "bh_march_rays_pose.hip": EXACT_ISSUE_ORDER,
+    "bh_march_rays_pose_lat.hip": EXACT,
+    "bh_march_rays_org.hip": EXACT_ISSUE_ORDER,
+    "bh_march_rays_org_lat.hip": EXACT,
     "bh_tiles.hip": [],
     # the lens shades and the sky chain: the march kernels' shading arithmetic, one rounding per op (bh_lens.hpp)
-    "bh_lens.hip": ["-ffp-contract=off", "-fhip-fp32-correctly-rounded-divide-sqrt", "-fno-slp-vectorize"],
+    "bh_lens.hip": EXACT,
     # post-RA scheduling off: fused bloom chain 0.556 -> 0.548 ms (A/B r01; pre-RA off too: 0.561)
     # no SLP vectorisation: packed-FP32 forms of the filter's adjacent channel ops cost more than the
     # scalar ops on gfx950 (a v_pk op issues slower than two scalar ones, plus the shuffles and hazard
@@ -119,10 +114,9 @@ def build_product(force: bool = False, out_dir: Path | None = None, extra: dict[
     for src, flags in TU_FLAGS.items():
         s = csrc / src
         o = obj_dir / (s.stem + ".o")
-        deps = [s, *headers, Path(__file__)] + ([csrc / "bh_march_exact.hip"] if src in ("bh_march_exact_lat.hip", "bh_march_refine_lat.hip") else []) \
-            + ([csrc / "bh_march_rays.hip"] if src == "bh_march_rays_lat.hip" else []) \
-            + ([csrc / "bh_march_rays_pose.hip"] if src == "bh_march_rays_pose_lat.hip" else []) \
-            + ([csrc / "bh_march_rays_org.hip"] if src == "bh_march_rays_org_lat.hip" else [])
+        deps = [s, *headers, Path(__file__)]
+        if s.stem.endswith("_lat"):  # a second build of another unit: the file it includes
+            deps += [csrc / inc for inc in re.findall(r'^#include "(\w+\.hip)"', s.read_text(), re.M)]
         if force or _stale(o, deps):
             jobs.append([HIPCC, *COMMON, *flags, *extra.get(src, []), "-c", str(s), "-o", str(o)])
         objs.append(o)

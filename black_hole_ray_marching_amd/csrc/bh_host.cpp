@@ -129,11 +129,21 @@ uint32_t bh_tile_row(const bh_camera_uniform* c, uint32_t height) {
     return (uint32_t)(py / 8.0);
 }
 
+// The default screen triangle: the only one the kernels' pixel_ray inverts.
+constexpr float SCREEN_TRI[3][2] = {{3.0f, 1.0f}, {-1.0f, 1.0f}, {-1.0f, -3.0f}};
 bool screen_tri_default(const bh_camera_uniform* c) {
-    static const float st[3][2] = {{3.0f, 1.0f}, {-1.0f, 1.0f}, {-1.0f, -3.0f}};
     for (int i = 0; i < 3; ++i)
-        if (c->screen_tri[i][0] != st[i][0] || c->screen_tri[i][1] != st[i][1]) return false;
+        if (c->screen_tri[i][0] != SCREEN_TRI[i][0] || c->screen_tri[i][1] != SCREEN_TRI[i][1]) return false;
     return true;
+}
+// A camera that holds only the position (the ray-map renders: their kernels do not read the corner rays).
+void position_camera(bh_camera_uniform* cam, const float* pos) {
+    std::memset(cam, 0, sizeof *cam);
+    for (int i = 0; i < 3; ++i) {
+        cam->pos[i] = pos[i];
+        cam->screen_tri[i][0] = SCREEN_TRI[i][0];
+        cam->screen_tri[i][1] = SCREEN_TRI[i][1];
+    }
 }
 
 }  // namespace
@@ -850,6 +860,21 @@ int bh_render_lens(bh_ctx* c, const bh_camera_uniform* cam, const bh_uniforms* U
 }
 
 // ---- ray maps (include/bh_render.h): the caller's direction per pixel, one origin per frame -----------------
+// What both ray-map paths refuse: fast math or, with a lens, a colour target in any of descs[0..n_frames), then
+// whatever ss_needs refuses in `plain` (the same frames, their dbg_* outputs cleared where the call allows them).
+// true: refused, and the error is set.
+static bool rays_refused(const char* fn, const bh_render_desc* descs, const bh_render_desc* plain, uint32_t n_frames,
+                         const bh_lens_px* out_lens) {
+    const char* why = nullptr;
+    for (uint32_t i = 0; i < n_frames && !why; ++i)
+        why = descs[i].math == BH_MATH_FAST ? "exact math (BH_MATH_EXACT): a ray map has no fast-math kernels"
+              : out_lens && (descs[i].out_col || descs[i].out_blackout) ? "no out_col or out_blackout (it writes only the lens)"
+                                                                       : nullptr;
+    if (!why) why = ss_needs(plain, n_frames);
+    if (why) g_last_error = std::string(fn) + ": a ray-map render needs " + why + ".";
+    return why != nullptr;
+}
+
 // bh_render_rays (out_lens null) and bh_render_lens_rays: the launch of bh_render / bh_render_ss / bh_render_lens of
 // this geometry from a camera that holds only the position -- the corner rays are not read by the ray-map kernels
 // -- with an order state and a repeated-frame key of its own (Launch::ray_map).
@@ -859,22 +884,11 @@ static int render_rays(const char* fn, bh_ctx* c, const float* pos, const bh_uni
     if (bh::ss::log2_k(ss) > 3u) return bad_arg(fn, __LINE__);
     if (!frame_shape_ok(d->width, d->height, ss)) return bad_arg(fn, __LINE__);
     bh_render_desc one = *d;
-    if (ss == 1u) one.dbg_n_rk = nullptr, one.dbg_fate = nullptr, one.dbg_steps = nullptr;  // per ray: as bh_render
-    const char* why = d->math == BH_MATH_FAST ? "exact math (BH_MATH_EXACT): a ray map has no fast-math kernels"
-                      : out_lens && (d->out_col || d->out_blackout) ? "no out_col or out_blackout (it writes only the lens)"
-                                                                   : ss_needs(out_lens ? d : &one, 1u);
-    if (why) {
-        g_last_error = std::string(fn) + ": a ray-map render needs " + why + ".";
-        return BH_ERR_UNSUPPORTED;
-    }
+    // the dbg_* outputs are per ray: allowed where bh_render allows them
+    if (ss == 1u && !out_lens) one.dbg_n_rk = nullptr, one.dbg_fate = nullptr, one.dbg_steps = nullptr;
+    if (rays_refused(fn, d, &one, 1u, out_lens)) return BH_ERR_UNSUPPORTED;
     bh_camera_uniform cam;
-    std::memset(&cam, 0, sizeof cam);
-    static const float st[3][2] = {{3.0f, 1.0f}, {-1.0f, 1.0f}, {-1.0f, -3.0f}};
-    for (int i = 0; i < 3; ++i) {
-        cam.pos[i] = pos[i];
-        cam.screen_tri[i][0] = st[i][0];
-        cam.screen_tri[i][1] = st[i][1];
-    }
+    position_camera(&cam, pos);
     bh_render_desc ld = *d;
     if (out_lens) {  // as bh_render_lens: the lens in place of target 0, the format word not read
         ld.format = BH_OUT_RGBA32F;
@@ -931,24 +945,9 @@ static int render_rays_posed(const char* fn, bh_ctx* c, uint32_t n_frames, uint3
     // the dbg_* outputs are per ray: allowed where bh_render_frames allows them (ss == 1, no shutter)
     if (ss == 1u && n_sub == 1u && !out_lens)
         for (auto& e : plain) e.dbg_n_rk = nullptr, e.dbg_fate = nullptr, e.dbg_steps = nullptr;
-    const char* why = nullptr;
-    for (uint32_t i = 0; i < n_frames && !why; ++i)
-        why = descs[i].math == BH_MATH_FAST ? "exact math (BH_MATH_EXACT): a ray map has no fast-math kernels"
-              : out_lens && (descs[i].out_col || descs[i].out_blackout) ? "no out_col or out_blackout (it writes only the lens)"
-                                                                       : nullptr;
-    if (!why) why = ss_needs(plain.data(), n_frames);
-    if (why) {
-        g_last_error = std::string(fn) + ": a ray-map render needs " + why + ".";
-        return BH_ERR_UNSUPPORTED;
-    }
-    static const float st[3][2] = {{3.0f, 1.0f}, {-1.0f, 1.0f}, {-1.0f, -3.0f}};
-    for (uint32_t i = 0; i < n_cams; ++i) {  // as render_rays: a camera that holds only the position
-        std::memset(&cams[i], 0, sizeof cams[i]);
-        for (int k = 0; k < 3; ++k) {
-            cams[i].pos[k] = poses[i].pos[k];
-            cams[i].screen_tri[k][0] = st[k][0];
-            cams[i].screen_tri[k][1] = st[k][1];
-        }
+    if (rays_refused(fn, descs, plain.data(), n_frames, out_lens)) return BH_ERR_UNSUPPORTED;
+    for (uint32_t i = 0; i < n_cams; ++i) {
+        position_camera(&cams[i], poses[i].pos);
         per_cam.push_back(descs[i / n_sub]);
         if (out_lens) {  // as bh_render_lens: the lens in place of target 0, the format word not read
             per_cam.back().format = BH_OUT_RGBA32F;

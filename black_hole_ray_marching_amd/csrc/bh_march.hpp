@@ -15,13 +15,15 @@
 // VGPRs; the 256-entry sRGB decode table is staged in LDS once per workgroup; the 32 MiB RGBA8 sky
 // is read with 4 dword gathers per escaped ray (L2/MALL-resident).
 //
-// This file holds the launchers; the kernels are in its parts, each of which names what it needs:
+// This file holds the dispatch: with_scene_fold, with_tile_form (the tile schedule's choice of form, once) and one
+// launch_* per hidden entry point.  The kernels are in its parts, each of which names what it needs:
 //   bh_march_ops.hpp      v3, the constants, the math modes' op sets (FOps, XOps)
 //   bh_march_step.hpp     one iteration: the ray state, the root-free tests, step_bf, the packed tail step
 //   bh_march_shade.hpp    sky sample, shading, the output encoders, write_pixel
 //   bh_march_ray.hpp      one ray to its end: the ping-pong loop, the tail's cycle fast-forward
 //   bh_march_resolve.hpp  the supersampled render's resolve in the wave, the shutter render's in the workgroup
-//   bh_march_tile.hpp     the tile schedule: march_slot, the tile / ss / shutter / lens / work-list kernels
+//   bh_march_tile.hpp     the tile schedule: the form mask, march_slot, the tile-schedule wave and the shutter
+//                         workgroup, their kernels (tile / ss / lens / ray map / shutter / work list) and launchers
 //   bh_march_alt.hpp      the persistent and pair schedules (A/B options)
 #pragma once
 #include <hip/hip_runtime.h>
@@ -54,24 +56,45 @@ __attribute__((visibility("hidden"))) inline void with_scene_fold(uint32_t flags
         if (flags == 0u) return f(Const<0u>{});
     f(Const<SF_DYN>{});
 }
-// The march over every tile under `schedule` (a bh_schedule without its flags); counters, grid: the persistent
-// schedule's.  Returns a hipError_t.
-template <bool FOLD_NONE>
-__attribute__((visibility("hidden"))) inline int launch_march(const MarchArgs& a, uint32_t schedule, uint32_t* counters, uint32_t grid, hipStream_t s) {
+// The tile schedule's choice of form, written once for its four families of kernels (plain, ray map, posed ray map,
+// with an origin map): a lens launch (a.lens set: exact builds) by the scene-flag fold alone, whatever the format word
+// says -- lens(sf); any other by format and fold, supersampled when a.ss_log2 != 0 (bh_render_ss, ss > 1) --
+// tile(fmt, sf, ss), ss a Const<0 or 1>.  The two callables launch their family's kernel of that form.  Returns a
+// hipError_t.
+template <bool FOLD_NONE, class L, class T>
+__attribute__((visibility("hidden"))) inline int with_tile_form(const MarchArgs& a, L&& lens, T&& tile) {
 #if !BH_FAST
-    if (a.lens != 0u) {  // bh_render_lens (tile schedule): one kernel per scene-flag fold, whatever the format word says
-        if (schedule != BH_SCHED_TILE) return (int)hipErrorInvalidValue;
-        with_scene_fold<FOLD_NONE>(a.scene_flags, [&](auto sf) { launch_tile_schedule(march_tile_lens_kernel<decltype(sf)::value>, a, s); });
+    if (a.lens != 0u) {
+        with_scene_fold<FOLD_NONE>(a.scene_flags, lens);
         return (int)hipGetLastError();
     }
 #endif
     return with_format(a.format, [&](auto fmt) {
+        with_scene_fold<FOLD_NONE>(a.scene_flags, [&](auto sf) {
+            if (a.ss_log2 != 0u) tile(fmt, sf, Const<1u>{});
+            else tile(fmt, sf, Const<0u>{});
+        });
+        return (int)hipGetLastError();
+    });
+}
+// The march over every tile under `schedule` (a bh_schedule without its flags); counters, grid: the persistent
+// schedule's.  Returns a hipError_t.
+template <bool FOLD_NONE>
+__attribute__((visibility("hidden"))) inline int launch_march(const MarchArgs& a, uint32_t schedule, uint32_t* counters, uint32_t grid, hipStream_t s) {
+    if (schedule == BH_SCHED_TILE)
+        return with_tile_form<FOLD_NONE>(
+            a, [&](auto sf) { launch_tile_schedule(march_tile_lens_kernel<decltype(sf)::value>, a, s); },
+            [&](auto fmt, auto sf, auto ss) {
+                constexpr uint32_t FMT = decltype(fmt)::value, SF = decltype(sf)::value;
+                if constexpr (decltype(ss)::value != 0u) launch_tile_schedule(march_tile_ss_kernel<FMT, SF>, a, s);
+                else launch_tile_schedule(march_tile_kernel<FMT, SF>, a, s);
+            });
+#if !BH_FAST
+    if (a.lens != 0u) return (int)hipErrorInvalidValue;  // bh_render_lens: the tile schedule only
+#endif
+    return with_format(a.format, [&](auto fmt) {
         constexpr uint32_t FMT = decltype(fmt)::value;
-        if (schedule == BH_SCHED_TILE && a.ss_log2 != 0u) {  // bh_render_ss, ss > 1: the same folds
-            with_scene_fold<FOLD_NONE>(a.scene_flags, [&](auto sf) { launch_tile_schedule(march_tile_ss_kernel<FMT, decltype(sf)::value>, a, s); });
-        } else if (schedule == BH_SCHED_TILE) {
-            with_scene_fold<FOLD_NONE>(a.scene_flags, [&](auto sf) { launch_tile_schedule(march_tile_kernel<FMT, decltype(sf)::value>, a, s); });
-        } else if (schedule == BH_SCHED_PAIR) {
+        if (schedule == BH_SCHED_PAIR) {
             const uint32_t pairs = (a.n_tiles + 1u) / 2u;
             hipLaunchKernelGGL(march_pair_kernel<FMT>, dim3((pairs + 3u) / 4u), dim3(256), 0, s, a);
         } else {
@@ -83,71 +106,43 @@ __attribute__((visibility("hidden"))) inline int launch_march(const MarchArgs& a
     });
 }
 #if !BH_FAST
-// The ray-map march (bh_render_rays, bh_render_lens_rays; tile schedule, one frame): the lens, supersampled or plain
-// form by the same fields as launch_march, with the same folds.
+// The ray-map march (bh_render_rays, bh_render_lens_rays; tile schedule, one frame).
 template <bool FOLD_NONE>
 __attribute__((visibility("hidden"))) inline int launch_rays(const MarchArgs& a, const float* dirs, hipStream_t s) {
     if (!dirs || a.n_frames != 1u) return (int)hipErrorInvalidValue;
-    if (a.lens != 0u) {
-        with_scene_fold<FOLD_NONE>(a.scene_flags, [&](auto sf) {
-            launch_tile_rays_schedule(march_tile_rays_lens_kernel<decltype(sf)::value>, a, dirs, s);
+    return with_tile_form<FOLD_NONE>(
+        a, [&](auto sf) { launch_tile_schedule(march_tile_rays_lens_kernel<decltype(sf)::value>, a, s, dirs); },
+        [&](auto fmt, auto sf, auto ss) {
+            constexpr uint32_t FMT = decltype(fmt)::value, SF = decltype(sf)::value;
+            launch_tile_schedule(march_tile_rays_kernel<FMT, SF, decltype(ss)::value != 0u>, a, s, dirs);
         });
-        return (int)hipGetLastError();
-    }
-    return with_format(a.format, [&](auto fmt) {
-        constexpr uint32_t FMT = decltype(fmt)::value;
-        with_scene_fold<FOLD_NONE>(a.scene_flags, [&](auto sf) {
-            if (a.ss_log2 != 0u) launch_tile_rays_schedule(march_tile_rays_kernel<FMT, decltype(sf)::value, true>, a, dirs, s);
-            else launch_tile_rays_schedule(march_tile_rays_kernel<FMT, decltype(sf)::value, false>, a, dirs, s);
-        });
-        return (int)hipGetLastError();
-    });
 }
 // The posed ray-map march (bh_render_frames_rays, bh_render_frames_shutter_rays, bh_render_lens_rays_posed; tile
 // schedule): any number of frames over one camera-space map; ln != 0: the shutter form, 2^ln cameras per output frame.
 template <bool FOLD_NONE>
 __attribute__((visibility("hidden"))) inline int launch_rays_pose(const MarchArgs& a, const float* dirs, uint32_t ln, hipStream_t s) {
     if (!dirs || a.n_frames == 0u) return (int)hipErrorInvalidValue;
-    if (a.lens != 0u) {
-        if (ln != 0u || a.n_frames != 1u) return (int)hipErrorInvalidValue;
-        with_scene_fold<FOLD_NONE>(a.scene_flags, [&](auto sf) {
-            launch_tile_rays_schedule(march_tile_rays_pose_lens_kernel<decltype(sf)::value>, a, dirs, s);
+    if (a.lens != 0u ? (ln != 0u || a.n_frames != 1u) : (ln > shutter::MAX_LOG2 || (a.n_frames & ((1u << ln) - 1u)) != 0u))
+        return (int)hipErrorInvalidValue;
+    return with_tile_form<FOLD_NONE>(
+        a, [&](auto sf) { launch_tile_schedule(march_tile_rays_pose_lens_kernel<decltype(sf)::value>, a, s, dirs); },
+        [&](auto fmt, auto sf, auto ss) {
+            constexpr uint32_t FMT = decltype(fmt)::value, SF = decltype(sf)::value;
+            if (ln != 0u) launch_shutter_schedule<FMT, march_tile_shutter_rays_kernel<FMT, SF>>(a, ln, s, dirs);
+            else launch_tile_schedule(march_tile_rays_pose_kernel<FMT, SF, decltype(ss)::value != 0u>, a, s, dirs);
         });
-        return (int)hipGetLastError();
-    }
-    if (ln > shutter::MAX_LOG2 || (a.n_frames & ((1u << ln) - 1u)) != 0u) return (int)hipErrorInvalidValue;
-    return with_format(a.format, [&](auto fmt) {
-        constexpr uint32_t FMT = decltype(fmt)::value;
-        with_scene_fold<FOLD_NONE>(a.scene_flags, [&](auto sf) {
-            constexpr uint32_t SF = decltype(sf)::value;
-            if (ln != 0u) launch_shutter_rays_schedule<FMT, SF>(a, dirs, ln, s);
-            else if (a.ss_log2 != 0u) launch_tile_rays_schedule(march_tile_rays_pose_kernel<FMT, SF, true>, a, dirs, s);
-            else launch_tile_rays_schedule(march_tile_rays_pose_kernel<FMT, SF, false>, a, dirs, s);
-        });
-        return (int)hipGetLastError();
-    });
 }
 // The posed ray-map march with an origin map (bh_render_frames_rays_origins, bh_render_lens_rays_origins; tile
 // schedule, no shutter form): any number of frames over one pair of camera-space maps.
 template <bool FOLD_NONE>
 __attribute__((visibility("hidden"))) inline int launch_rays_org(const MarchArgs& a, const float* dirs, const float* orgs, hipStream_t s) {
-    if (!dirs || !orgs || a.n_frames == 0u) return (int)hipErrorInvalidValue;
-    if (a.lens != 0u) {
-        if (a.n_frames != 1u) return (int)hipErrorInvalidValue;
-        with_scene_fold<FOLD_NONE>(a.scene_flags, [&](auto sf) {
-            launch_tile_rays_org_schedule(march_tile_rays_org_lens_kernel<decltype(sf)::value>, a, dirs, orgs, s);
+    if (!dirs || !orgs || a.n_frames == 0u || (a.lens != 0u && a.n_frames != 1u)) return (int)hipErrorInvalidValue;
+    return with_tile_form<FOLD_NONE>(
+        a, [&](auto sf) { launch_tile_schedule(march_tile_rays_org_lens_kernel<decltype(sf)::value>, a, s, dirs, orgs); },
+        [&](auto fmt, auto sf, auto ss) {
+            constexpr uint32_t FMT = decltype(fmt)::value, SF = decltype(sf)::value;
+            launch_tile_schedule(march_tile_rays_org_kernel<FMT, SF, decltype(ss)::value != 0u>, a, s, dirs, orgs);
         });
-        return (int)hipGetLastError();
-    }
-    return with_format(a.format, [&](auto fmt) {
-        constexpr uint32_t FMT = decltype(fmt)::value;
-        with_scene_fold<FOLD_NONE>(a.scene_flags, [&](auto sf) {
-            constexpr uint32_t SF = decltype(sf)::value;
-            if (a.ss_log2 != 0u) launch_tile_rays_org_schedule(march_tile_rays_org_kernel<FMT, SF, true>, a, dirs, orgs, s);
-            else launch_tile_rays_org_schedule(march_tile_rays_org_kernel<FMT, SF, false>, a, dirs, orgs, s);
-        });
-        return (int)hipGetLastError();
-    });
 }
 #endif
 // The shutter render's march (bh_render_shutter, n = 2^ln cameras per output frame; tile schedule): the same folds.
@@ -156,7 +151,8 @@ __attribute__((visibility("hidden"))) inline int launch_shutter(const MarchArgs&
     if (ln == 0u || ln > shutter::MAX_LOG2 || (a.n_frames & ((1u << ln) - 1u)) != 0u) return (int)hipErrorInvalidValue;
     return with_format(a.format, [&](auto fmt) {
         with_scene_fold<FOLD_NONE>(a.scene_flags, [&](auto sf) {
-            launch_shutter_schedule<decltype(fmt)::value, decltype(sf)::value>(a, ln, s);
+            constexpr uint32_t FMT = decltype(fmt)::value;
+            launch_shutter_schedule<FMT, march_tile_shutter_kernel<FMT, decltype(sf)::value>>(a, ln, s);
         });
         return (int)hipGetLastError();
     });

@@ -1,6 +1,8 @@
-// bh_march_tile.hpp -- the tile schedule (BH_SCHED_TILE, the default): one dispatch slot marched by one wave
-// (march_slot), the shader-clock probe, the plain, supersampled, shutter, lens, ray-map and work-list kernels, and their
-// launchers.
+// bh_march_tile.hpp -- the tile schedule (BH_SCHED_TILE, the default): the form mask (F_*), one dispatch slot marched
+// by one wave in a form (march_slot), the shader-clock probe, the tile-schedule wave (march_tile_wave) and the shutter
+// workgroup (shutter_workgroup) with the kernels that are their shells -- plain, supersampled, lens, ray-map, shutter --
+// the work-list kernel, and the three launchers (launch_tile_schedule, launch_shutter_schedule,
+// launch_refine_schedule).
 // Needs bh_march_ray.hpp, bh_march_shade.hpp, bh_march_resolve.hpp and bh_refine.hpp (the work list).
 #pragma once
 #include "bh_march_ray.hpp"
@@ -97,8 +99,9 @@ __device__ __forceinline__ SlotHead slot_head(const MarchArgs& A, uint32_t slot,
 // overlaps the others' bulk instead of ending the launch alone.  Only frame 0
 // records the tile costs for the next launch's order (the histogram must count each tile once).
 //
-// One dispatch slot, marched by one wave.  SS: the supersampled form (march_tile_ss_kernel).  ITEM (with SS):
-// a work item of the adaptive render (march_refine_kernel) -- `slot` is the frame and (item_tx, item_ty) the
+// One dispatch slot, marched by one wave in the form FORM: a mask of the bits F_SS ... F_ORG (below), named here
+// without the prefix, as march_slot_body unpacks them.  SS: the supersampled form (march_tile_ss_kernel).  ITEM (with
+// SS): a work item of the adaptive render (march_refine_kernel) -- `slot` is the frame and (item_tx, item_ty) the
 // tile of the virtual frame, both given by the caller's work list: no dispatch order, no cost feedback.
 // LENS (exact math, march_tile_lens_kernel): the epilogue stores the ray's lens record instead of shading it;
 // `lut` is not read.
@@ -119,6 +122,9 @@ __device__ __forceinline__ SlotHead slot_head(const MarchArgs& A, uint32_t slot,
 // (org_load, slot_frame): ro0 and cps live in VGPRs through the loop, in these kernels alone.  The Frame of every
 // other form comes from the same call, slot_frame<false>: a forced-inline template keeps their machine code byte for
 // byte, which a lambda around the choice did not.
+// A form is a mask of these bits, one template argument of march_slot_body, march_slot, march_tile_wave and
+// shutter_workgroup; march_slot_body's static_asserts say which masks are forms.
+constexpr uint32_t F_SS = 1u, F_ITEM = 2u, F_LENS = 4u, F_SHUT = 8u, F_RAYS = 16u, F_POSE = 32u, F_ORG = 64u;
 struct ShutterLane { uint32_t px, py; bool valid, ok; };
 // The ORG form's prologue.  org_load: both 12-byte loads of a valid lane issued before either is used (one wait), and
 //     d = (mx r + my u) + mz f,   ro0 = pos + ((ox r + oy u) + oz f)
@@ -158,11 +164,12 @@ __device__ __forceinline__ Frame slot_frame(const MarchArgs& a, const OrgRay& g)
 #endif
     return make_frame(a);
 }
-template <uint32_t FMT, uint32_t SF, bool SS = false, bool ITEM = false, bool LENS = false, bool SHUT = false,
-          bool RAYS = false, bool POSE = false, bool ORG = false>
+template <uint32_t FMT, uint32_t SF, uint32_t FORM>
 __device__ __forceinline__ void march_slot_body(const MarchArgs& A, const SlotHead& h, const float* lut,
                                                 uint32_t lane, ShutterLane* sl = nullptr, const float* dirs = nullptr,
                                                 const float* orgs = nullptr) {
+    constexpr bool SS = FORM & F_SS, ITEM = FORM & F_ITEM, LENS = FORM & F_LENS, SHUT = FORM & F_SHUT,
+                   RAYS = FORM & F_RAYS, POSE = FORM & F_POSE, ORG = FORM & F_ORG;
     static_assert(SS || !ITEM, "work items are supersampled tiles");
     static_assert(!LENS || (!SS && !BH_FAST), "a lens is one record per ray, in exact math");
     static_assert(!SHUT || (!SS && !ITEM && !LENS), "a shutter wave takes its ss from the argument");
@@ -273,14 +280,14 @@ __device__ __forceinline__ void march_slot_body(const MarchArgs& A, const SlotHe
     }
 }
 // Head and body back to back: the shutter workgroups' waves and the work-list march's items.
-template <uint32_t FMT, uint32_t SF, bool SS = false, bool ITEM = false, bool LENS = false, bool SHUT = false,
-          bool RAYS = false, bool POSE = false>
+template <uint32_t FMT, uint32_t SF, uint32_t FORM>
 __device__ __forceinline__ void march_slot(const MarchArgs& A, uint32_t slot, const float* lut,
                                            uint32_t lane, uint32_t item_tx = 0u, uint32_t item_ty = 0u,
-                                           ShutterLane* sl = nullptr, const float* dirs = nullptr) {
-    const SlotHead h = slot_head<ITEM>(A, slot, item_tx, item_ty);
+                                           ShutterLane* sl = nullptr, const float* dirs = nullptr,
+                                           const float* orgs = nullptr) {
+    const SlotHead h = slot_head<(FORM & F_ITEM) != 0u>(A, slot, item_tx, item_ty);
     if (!h.ok) return;
-    march_slot_body<FMT, SF, SS, ITEM, LENS, SHUT, RAYS, POSE>(A, h, lut, lane, sl, dirs);
+    march_slot_body<FMT, SF, FORM>(A, h, lut, lane, sl, dirs, orgs);
 }
 
 // Shader-clock probe (bh_set_clock_probe): a sampled wave reads both counters when it starts and adds
@@ -308,17 +315,20 @@ __device__ __forceinline__ void clock_end(unsigned long long* acc, const ClockSt
 }
 
 // One wave of the tile schedule: its dispatch slot (the grid covers every slot, WG_WAVES waves per workgroup),
-// marched with march_slot_body's SS / LENS / RAYS / POSE form, between the clock probe's two readings.
+// marched in march_slot_body's form FORM (of F_SS, F_LENS, F_RAYS, F_POSE, F_ORG), between the clock probe's two
+// readings.
 // The wave's start is one trip to memory deep where it can be: the table copy's loads (lut != null: 16 bytes of
 // each table per lane, srgb_fetch) are issued first and awaited last, and the slot's own chain -- kernel argument,
 // order entry and frame record, tile list -- runs on the scalar unit while they fly (slot_head); then the one LDS
 // store per table and the workgroup's barrier.  (The copy by four guarded loads, each awaited, then the barrier,
 // then the chain through vector loads put about eight dependent round trips in front of pixel_ray's first
 // multiply: DESIGN.md §5 item 32.)
-template <uint32_t FMT, uint32_t SF, bool SS, bool LENS = false, bool RAYS = false, bool POSE = false, bool ORG = false>
+template <uint32_t FMT, uint32_t SF, uint32_t FORM>
 __device__ __forceinline__ void march_tile_wave(const MarchArgs& A, float* lut, const float* dirs = nullptr,
                                                 const float* orgs = nullptr) {
     static_assert(WG_WAVES == 1u, "the table copy is one wave's: 64 lanes x 16 bytes per table");
+    static_assert(!(FORM & (F_ITEM | F_SHUT)), "work items and shutter waves have kernels of their own");
+    constexpr bool LENS = FORM & F_LENS;
     // every argument word the start branches on or indexes with, wanted here: one group of scalar loads and one
     // wait for them (left to their uses, each is loaded in the block of its use and waited for there in turn)
     asm volatile("" ::"s"(A.srgb_lut), "s"(A.n_tiles), "s"(A.n_frames), "s"(A.nf_magic), "s"(A.frame_table),
@@ -338,7 +348,7 @@ __device__ __forceinline__ void march_tile_wave(const MarchArgs& A, float* lut, 
     const bool probe = A.clk && ((slot + (slot >> 8)) & A.clk_mask) == 0u;
     ClockStart c0{0u, 0u};
     if (probe) c0 = clock_start();
-    if (h.ok) march_slot_body<FMT, SF, SS, false, LENS, false, RAYS, POSE, ORG>(A, h, lut, threadIdx.x & 63u, nullptr, dirs, orgs);
+    if (h.ok) march_slot_body<FMT, SF, FORM>(A, h, lut, threadIdx.x & 63u, nullptr, dirs, orgs);
     if (probe) clock_end(A.clk, c0);
 }
 
@@ -346,7 +356,7 @@ __device__ __forceinline__ void march_tile_wave(const MarchArgs& A, float* lut, 
 template <uint32_t FMT, uint32_t SF>
 __global__ void __launch_bounds__(64 * WG_WAVES) march_tile_kernel(MarchArgs A) {
     __shared__ __attribute__((aligned(16))) float lut[lds_tables<FMT>()];
-    march_tile_wave<FMT, SF, false>(A, lut);
+    march_tile_wave<FMT, SF, 0u>(A, lut);
 }
 
 // The tile schedule's supersampled form (bh_render_ss, ss > 1): the same waves over the virtual frame's
@@ -356,7 +366,7 @@ __global__ void __launch_bounds__(64 * WG_WAVES) march_tile_kernel(MarchArgs A) 
 template <uint32_t FMT, uint32_t SF>
 __global__ void __launch_bounds__(64 * WG_WAVES) march_tile_ss_kernel(MarchArgs A) {
     __shared__ __attribute__((aligned(16))) float lut[lds_tables<FMT>()];
-    march_tile_wave<FMT, SF, true>(A, lut);
+    march_tile_wave<FMT, SF, F_SS>(A, lut);
 }
 
 // The tile schedule's shutter form (bh_render_shutter): one workgroup of n = 2^ln waves per (output frame, tile)
@@ -375,6 +385,39 @@ __global__ void __launch_bounds__(64 * WG_WAVES) march_tile_ss_kernel(MarchArgs 
 // request, n = 8 1.03 to 1.05x in place of 1.07 to 1.08x, n = 4 unchanged.
 template <uint32_t FMT>
 constexpr uint32_t shutter_lds_bytes(uint32_t ln) { return (uint32_t)(sizeof(HistLds) << ln) + (uint32_t)(lds_tables<FMT>() * sizeof(float)); }
+// One wave of shutter workgroup g, from its wave index on: the march in the form FORM (F_SHUT, over a posed ray map
+// with F_RAYS | F_POSE and `dirs`), the workgroup's second barrier, the writer waves' resolve and store.  The kernels
+// are shells around it that keep what comes before: the table copy, its barrier and the early return.
+// Barrier discipline: every wave of the workgroup arrives at the barrier here, whatever its march did.  Between the
+// table copy's barrier and this one there is one return, the shell's, on blockIdx and kernel arguments alone (the
+// whole workgroup or none of it); march_slot's defensive return (a tile index out of range: the same order entry for
+// all n waves) only returns to this function, ahead of the barrier; and no code on the way sits under a lane- or
+// wave-dependent branch that holds a barrier -- the ray map is loaded inside march_slot without a branch or a return
+// of its own (a lane outside the frame reads pixel (0, 0) and a select drops what it read).  A wave whose lanes are
+// all outside the frame marches nothing and stages zeros.  The shell's return stays in the shells because the
+// compiler emits other code for it from here: with the whole kernel in this function the table copy's prologue comes
+// out in another order, with the return alone its compare and branch flip polarity, in all 42 shutter kernels.
+template <uint32_t FMT, uint32_t SF, uint32_t FORM>
+__device__ __forceinline__ void shutter_workgroup(const MarchArgs& A, uint32_t ln, uint32_t g, uint32_t n_out, float* lut,
+                                                  const float* dirs = nullptr) {
+    static_assert((FORM & F_SHUT) != 0u, "a shutter workgroup marches shutter waves");
+    const uint32_t w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63u;
+    const uint32_t slot = shutter::wave_slot(g, w, n_out, ln);
+    const bool probe = A.clk && ((slot + (slot >> 8)) & A.clk_mask) == 0u;  // as march_tile_wave
+    ClockStart c0{0u, 0u};
+    if (probe) c0 = clock_start();
+    ShutterLane sl{0u, 0u, false, false};
+    march_slot<FMT, SF, FORM>(A, slot, lut, lane, 0u, 0u, &sl, dirs);
+    if (probe) clock_end(A.clk, c0);
+    __syncthreads();
+    if (!sl.ok || w > 1u) return;
+    const BH_CONST_AS FrameArgs* F = frame_args_of(A, slot % A.n_frames);
+    void* out = w == 0u ? F->out_col : F->out_blackout;
+    if (!out) return;  // wave 1 of a frame without the second target: neither resolved nor written
+    const uint32_t lk = A.ss_log2;
+    if (sl.valid && ss::writer(lane, lk))
+        shutter_resolve_store<FMT>(out, w, ln, lane, ss::out_index(sl.px, sl.py, lk, A.ss_out_width), lut);
+}
 template <uint32_t FMT, uint32_t SF>
 __global__ void __launch_bounds__(64u << shutter::MAX_LOG2) __attribute__((amdgpu_waves_per_eu(8)))
 march_tile_shutter_kernel(MarchArgs A, uint32_t ln) {
@@ -388,36 +431,16 @@ march_tile_shutter_kernel(MarchArgs A, uint32_t ln) {
     const uint32_t n_out = A.n_frames >> ln;  // output frames
     const uint32_t g = blockIdx.x;
     if (g >= A.n_tiles * n_out) return;  // blockIdx and kernel arguments only: the whole workgroup or none of it
-    const uint32_t w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63u;
-    const uint32_t slot = shutter::wave_slot(g, w, n_out, ln);
-    const bool probe = A.clk && ((slot + (slot >> 8)) & A.clk_mask) == 0u;  // as march_tile_wave
-    ClockStart c0{0u, 0u};
-    if (probe) c0 = clock_start();
-    ShutterLane sl{0u, 0u, false, false};
-    march_slot<FMT, SF, false, false, false, true>(A, slot, lut, lane, 0u, 0u, &sl);
-    if (probe) clock_end(A.clk, c0);
-    // Every wave of the workgroup arrives here, whatever its march did.  Between the table load's barrier and
-    // this one there is one return in this kernel, on blockIdx and kernel arguments alone; march_slot's
-    // defensive return (a tile index out of range: the same order entry for all n waves) only returns to this
-    // kernel, ahead of this barrier; and no code on the way sits under a lane- or wave-dependent branch that
-    // holds a barrier.  A wave whose lanes are all outside the frame marches nothing and stages zeros.
-    __syncthreads();
-    if (!sl.ok || w > 1u) return;
-    const BH_CONST_AS FrameArgs* F = frame_args_of(A, slot % A.n_frames);
-    void* out = w == 0u ? F->out_col : F->out_blackout;
-    if (!out) return;  // wave 1 of a frame without the second target: neither resolved nor written
-    const uint32_t lk = A.ss_log2;
-    if (sl.valid && ss::writer(lane, lk))
-        shutter_resolve_store<FMT>(out, w, ln, lane, ss::out_index(sl.px, sl.py, lk, A.ss_out_width), lut);
+    shutter_workgroup<FMT, SF, F_SHUT>(A, ln, g, n_out, lut);
 }
 
-#if !BH_FAST
+// The kernels from here to the work-list march are the exact builds' alone (march_slot_body's static_asserts).
 // The tile schedule's lens form (bh_render_lens): march_tile_kernel's waves -- order, cost feedback, cycle
 // fast-forward -- with the lens record as the epilogue: no sky, no tables, no encode, one kernel per
 // scene-flag fold.
 template <uint32_t SF>
 __global__ void __launch_bounds__(64 * WG_WAVES) march_tile_lens_kernel(MarchArgs A) {
-    march_tile_wave<BH_OUT_RGBA32F, SF, false, true>(A, nullptr);
+    march_tile_wave<BH_OUT_RGBA32F, SF, F_LENS>(A, nullptr);
 }
 
 // The tile schedule's ray-map forms (bh_render_rays, bh_render_lens_rays): the plain, supersampled and lens kernels
@@ -427,11 +450,11 @@ __global__ void __launch_bounds__(64 * WG_WAVES) march_tile_lens_kernel(MarchArg
 template <uint32_t FMT, uint32_t SF, bool SS>
 __global__ void __launch_bounds__(64 * WG_WAVES) march_tile_rays_kernel(MarchArgs A, const float* dirs) {
     __shared__ __attribute__((aligned(16))) float lut[lds_tables<FMT>()];
-    march_tile_wave<FMT, SF, SS, false, true>(A, lut, dirs);
+    march_tile_wave<FMT, SF, (SS ? F_SS : 0u) | F_RAYS>(A, lut, dirs);
 }
 template <uint32_t SF>
 __global__ void __launch_bounds__(64 * WG_WAVES) march_tile_rays_lens_kernel(MarchArgs A, const float* dirs) {
-    march_tile_wave<BH_OUT_RGBA32F, SF, false, true, true>(A, nullptr, dirs);
+    march_tile_wave<BH_OUT_RGBA32F, SF, F_LENS | F_RAYS>(A, nullptr, dirs);
 }
 
 // The posed ray-map forms (bh_render_frames_rays, bh_render_lens_rays_posed): the ray-map kernels over a map in camera
@@ -440,11 +463,11 @@ __global__ void __launch_bounds__(64 * WG_WAVES) march_tile_rays_lens_kernel(Mar
 template <uint32_t FMT, uint32_t SF, bool SS>
 __global__ void __launch_bounds__(64 * WG_WAVES) march_tile_rays_pose_kernel(MarchArgs A, const float* dirs) {
     __shared__ __attribute__((aligned(16))) float lut[lds_tables<FMT>()];
-    march_tile_wave<FMT, SF, SS, false, true, true>(A, lut, dirs);
+    march_tile_wave<FMT, SF, (SS ? F_SS : 0u) | F_RAYS | F_POSE>(A, lut, dirs);
 }
 template <uint32_t SF>
 __global__ void __launch_bounds__(64 * WG_WAVES) march_tile_rays_pose_lens_kernel(MarchArgs A, const float* dirs) {
-    march_tile_wave<BH_OUT_RGBA32F, SF, false, true, true, true>(A, nullptr, dirs);
+    march_tile_wave<BH_OUT_RGBA32F, SF, F_LENS | F_RAYS | F_POSE>(A, nullptr, dirs);
 }
 
 // The posed ray-map forms with an origin map (bh_render_frames_rays_origins, bh_render_lens_rays_origins): the posed
@@ -453,18 +476,16 @@ __global__ void __launch_bounds__(64 * WG_WAVES) march_tile_rays_pose_lens_kerne
 template <uint32_t FMT, uint32_t SF, bool SS>
 __global__ void __launch_bounds__(64 * WG_WAVES) march_tile_rays_org_kernel(MarchArgs A, const float* dirs, const float* orgs) {
     __shared__ __attribute__((aligned(16))) float lut[lds_tables<FMT>()];
-    march_tile_wave<FMT, SF, SS, false, true, true, true>(A, lut, dirs, orgs);
+    march_tile_wave<FMT, SF, (SS ? F_SS : 0u) | F_RAYS | F_POSE | F_ORG>(A, lut, dirs, orgs);
 }
 template <uint32_t SF>
 __global__ void __launch_bounds__(64 * WG_WAVES) march_tile_rays_org_lens_kernel(MarchArgs A, const float* dirs, const float* orgs) {
-    march_tile_wave<BH_OUT_RGBA32F, SF, false, true, true, true, true>(A, nullptr, dirs, orgs);
+    march_tile_wave<BH_OUT_RGBA32F, SF, F_LENS | F_RAYS | F_POSE | F_ORG>(A, nullptr, dirs, orgs);
 }
 
-// The shutter form over a posed ray map (bh_render_frames_shutter_rays): march_tile_shutter_kernel, statement for
-// statement, with the map as the second argument and march_slot's RAYS and POSE switches -- the n waves of a
-// workgroup read the same 12 bytes per pixel and differ in their FrameArgs' pose.  Its barrier discipline is that
-// kernel's (the comment there): the map is loaded inside march_slot without a branch or a return of its own (a lane
-// outside the frame reads pixel (0, 0) and a select drops what it read), so nothing new stands between the barriers.
+// The shutter form over a posed ray map (bh_render_frames_shutter_rays): march_tile_shutter_kernel's shell with the
+// map as the second argument, and shutter_workgroup with the F_RAYS and F_POSE bits -- the n waves of a workgroup read
+// the same 12 bytes per pixel and differ in their FrameArgs' pose.
 template <uint32_t FMT, uint32_t SF>
 __global__ void __launch_bounds__(64u << shutter::MAX_LOG2) __attribute__((amdgpu_waves_per_eu(8)))
 march_tile_shutter_rays_kernel(MarchArgs A, const float* dirs, uint32_t ln) {
@@ -476,24 +497,8 @@ march_tile_shutter_rays_kernel(MarchArgs A, const float* dirs, uint32_t ln) {
     const uint32_t n_out = A.n_frames >> ln;  // output frames
     const uint32_t g = blockIdx.x;
     if (g >= A.n_tiles * n_out) return;  // blockIdx and kernel arguments only: the whole workgroup or none of it
-    const uint32_t w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63u;
-    const uint32_t slot = shutter::wave_slot(g, w, n_out, ln);
-    const bool probe = A.clk && ((slot + (slot >> 8)) & A.clk_mask) == 0u;  // as march_tile_wave
-    ClockStart c0{0u, 0u};
-    if (probe) c0 = clock_start();
-    ShutterLane sl{0u, 0u, false, false};
-    march_slot<FMT, SF, false, false, false, true, true, true>(A, slot, lut, lane, 0u, 0u, &sl, dirs);
-    if (probe) clock_end(A.clk, c0);
-    __syncthreads();  // every wave of the workgroup, whatever its march did (march_tile_shutter_kernel)
-    if (!sl.ok || w > 1u) return;
-    const BH_CONST_AS FrameArgs* F = frame_args_of(A, slot % A.n_frames);
-    void* out = w == 0u ? F->out_col : F->out_blackout;
-    if (!out) return;  // wave 1 of a frame without the second target: neither resolved nor written
-    const uint32_t lk = A.ss_log2;
-    if (sl.valid && ss::writer(lane, lk))
-        shutter_resolve_store<FMT>(out, w, ln, lane, ss::out_index(sl.px, sl.py, lk, A.ss_out_width), lut);
+    shutter_workgroup<FMT, SF, F_SHUT | F_RAYS | F_POSE>(A, ln, g, n_out, lut, dirs);
 }
-#endif
 
 // The adaptive render's second pass (bh_render_adaptive; bh_refine.hpp): the supersampled march over a work
 // list that the detect kernel (bh_tiles.hip) left on the device.  The host never learns the list's length, so
@@ -543,7 +548,7 @@ __global__ void __launch_bounds__(64 * WG_WAVES) march_refine_kernel(MarchArgs A
         if (fi >= A.n_frames ||
             !refine::item_tile(tile, refine::item_sub(item, lk), lk, R.tiles_x, R.tiles_y, A.tiles_x, A.tiles_y, &vtx, &vty))
             continue;
-        march_slot<FMT, SF, true, true>(A, fi, lut, lane, vtx, vty);
+        march_slot<FMT, SF, F_SS | F_ITEM>(A, fi, lut, lane, vtx, vty);
         __builtin_amdgcn_s_setprio(0);  // a tail wave raised it (march_ray); the next item starts as any wave does
     }
 }
@@ -553,52 +558,28 @@ __global__ void __launch_bounds__(64 * WG_WAVES) march_refine_kernel(MarchArgs A
 // out_col the lens).  (A persistent form -- resident
 // waves claiming slots in order from one device-scope counter -- measured 2.5x slower: a returning
 // atomic on one word is serialised across the 8 XCDs at ~85 M claims/s)
-template <class K>
-inline void launch_tile_schedule(K kernel, const MarchArgs& a, hipStream_t s) {
+// The ray-map forms take the same grid; `maps`: their direction map, then their origin map, the kernel's arguments
+// after the first.
+template <class K, class... Maps>
+inline void launch_tile_schedule(K kernel, const MarchArgs& a, hipStream_t s, Maps... maps) {
     const uint32_t waves = a.n_tiles * a.n_frames;
     const uint32_t blocks = (waves + (WG_WAVES - 1u)) / WG_WAVES;
-    hipLaunchKernelGGL(kernel, dim3(blocks), dim3(64u * WG_WAVES), 0, s, a);
+    hipLaunchKernelGGL(kernel, dim3(blocks), dim3(64u * WG_WAVES), 0, s, a, maps...);
 }
-// ... its ray-map forms: the same grid, the map as the second argument
-template <class K>
-inline void launch_tile_rays_schedule(K kernel, const MarchArgs& a, const float* dirs, hipStream_t s) {
-    const uint32_t waves = a.n_tiles * a.n_frames;
-    const uint32_t blocks = (waves + (WG_WAVES - 1u)) / WG_WAVES;
-    hipLaunchKernelGGL(kernel, dim3(blocks), dim3(64u * WG_WAVES), 0, s, a, dirs);
-}
-// ... with an origin map: the two maps as the second and third arguments
-template <class K>
-inline void launch_tile_rays_org_schedule(K kernel, const MarchArgs& a, const float* dirs, const float* orgs, hipStream_t s) {
-    const uint32_t waves = a.n_tiles * a.n_frames;
-    const uint32_t blocks = (waves + (WG_WAVES - 1u)) / WG_WAVES;
-    hipLaunchKernelGGL(kernel, dim3(blocks), dim3(64u * WG_WAVES), 0, s, a, dirs, orgs);
-}
-// ... its shutter form: one workgroup of 2^ln waves per (output frame, tile); a.n_frames counts cameras
-template <uint32_t FMT, uint32_t SF>
-inline void launch_shutter_schedule(const MarchArgs& a, uint32_t ln, hipStream_t s) {
+// ... its shutter form: one workgroup of 2^ln waves per (output frame, tile); a.n_frames counts cameras.  KERNEL is
+// march_tile_shutter_kernel<FMT, SF> or, with the map (its second argument), march_tile_shutter_rays_kernel<FMT, SF>:
+// a template argument, so that each kernel has its own `raised`.
+template <uint32_t FMT, auto KERNEL, class... Map>
+inline void launch_shutter_schedule(const MarchArgs& a, uint32_t ln, hipStream_t s, Map... map) {
     const uint32_t blocks = a.n_tiles * (a.n_frames >> ln), lds = shutter_lds_bytes<FMT>(ln);
     if (lds > 64u * 1024u) {  // above the default limit of a launch's dynamic LDS: once per kernel
-        static const hipError_t raised = hipFuncSetAttribute(reinterpret_cast<const void*>(&march_tile_shutter_kernel<FMT, SF>),
+        static const hipError_t raised = hipFuncSetAttribute(reinterpret_cast<const void*>(KERNEL),
                                                               hipFuncAttributeMaxDynamicSharedMemorySize,
                                                               (int)shutter_lds_bytes<FMT>(shutter::MAX_LOG2));
         (void)raised;
     }
-    hipLaunchKernelGGL((march_tile_shutter_kernel<FMT, SF>), dim3(blocks), dim3(64u << ln), lds, s, a, ln);
+    hipLaunchKernelGGL(KERNEL, dim3(blocks), dim3(64u << ln), lds, s, a, map..., ln);
 }
-#if !BH_FAST
-// ... the shutter form over a posed ray map: the same grid and LDS, the map as the second argument
-template <uint32_t FMT, uint32_t SF>
-inline void launch_shutter_rays_schedule(const MarchArgs& a, const float* dirs, uint32_t ln, hipStream_t s) {
-    const uint32_t blocks = a.n_tiles * (a.n_frames >> ln), lds = shutter_lds_bytes<FMT>(ln);
-    if (lds > 64u * 1024u) {  // as launch_shutter_schedule: once per kernel
-        static const hipError_t raised = hipFuncSetAttribute(reinterpret_cast<const void*>(&march_tile_shutter_rays_kernel<FMT, SF>),
-                                                              hipFuncAttributeMaxDynamicSharedMemorySize,
-                                                              (int)shutter_lds_bytes<FMT>(shutter::MAX_LOG2));
-        (void)raised;
-    }
-    hipLaunchKernelGGL((march_tile_shutter_rays_kernel<FMT, SF>), dim3(blocks), dim3(64u << ln), lds, s, a, dirs, ln);
-}
-#endif
 // ... and the adaptive render's work-list march: `waves` resident waves that pull (march_refine_kernel)
 template <uint32_t FMT, uint32_t SF>
 inline void launch_refine_schedule(const MarchArgs& a, const RefineArgs& r, uint32_t waves, hipStream_t s) {

@@ -1,9 +1,10 @@
 """The derived march kernels on the GPU across the scenario table of tests/_scenarios.py: every form built on
-march_slot -- supersampled, adaptive, shutter, lens, ray map, ray-map lens -- at the scene-flag folds, caps and
-uniform gates that the plain march is already held to, against the references of tests/_ss_ref.py, _adaptive_ref.py,
-_shutter_ref.py, _lens_ref.py, _lens_mip_ref.py and _rays_ref.py at that scenario: the CPU oracle's rays, resolved and
-encoded in numpy -- bit for bit.  The reference is never the GPU's own output, except in the fast-math tests, which
-say why.  What each scenario aims at is asserted from the oracle alone in tests/test_scenarios_host.py.
+march_slot -- supersampled, adaptive, shutter, lens, ray map, ray-map lens, posed ray map, origin map -- at the
+scene-flag folds, caps and uniform gates that the plain march is already held to, against the references of
+tests/_ss_ref.py, _adaptive_ref.py, _shutter_ref.py, _lens_ref.py, _lens_mip_ref.py, _rays_ref.py, _rays_pose_ref.py and
+_rays_origins_ref.py at that scenario: the CPU oracle's rays, resolved and encoded in numpy -- bit for bit.  The
+reference is never the GPU's own output, except in the fast-math tests, which say why.  What each scenario aims at is
+asserted from the oracle alone in tests/test_scenarios_host.py.
 
 Every scenario renders in a fresh Scene of its cap and flags, four times: in the order of a fresh state, in the order
 learned from that call's tile costs, and on each build of the exact kernels."""
@@ -12,7 +13,7 @@ import pytest
 
 import black_hole_ray_marching_amd as bh
 from black_hole_ray_marching_amd import _abi
-from tests import _adaptive_ref, _lens_ref, _rays_ref, _shutter_ref
+from tests import _adaptive_ref, _lens_ref, _rays_origins_ref, _rays_pose_ref, _rays_ref, _shutter_ref
 from tests import _scenarios as S
 from tests._cases import camera_uniform
 from tests._gpu_common import FAST_TOL, gpu_render
@@ -308,6 +309,85 @@ def test_formats(torch_cuda, sid, fmt):
         check_adaptive(torch, sc, s, fmt)
         check_rays(torch, sc, s, _rays_ref.pinhole_map(s.camera, W, H), camera_uniform(s.camera, W, H).pos, W, H,
                    _lens_ref.frame(s.camera, W, H, "ctx", 1, s.key), "pinhole map", fmt=fmt)
+
+
+# ---- posed ray maps and origin maps: every fold and format ----------------------------------------------------------
+FOLDS = ["none_F2", "far_off", "disc_F2"]  # Const<0>, Const<BH_SCENE_DEFAULT>, SF_DYN
+POSED = ("axesD", "rotH")                  # tests/_rays_pose_ref.py: far outside the unit sphere, and just outside it
+
+
+def posed_traces(s, k, origins, W=13, H=7):
+    """Per pose of POSED: (col, blackout_col, records) of the camera-space map of the virtual frame kW x kH turned by
+    the pose -- with `origins`, from the scatter of tests/_rays_origins_ref.py -- resolved when k > 1."""
+    kind = "general" if k == 1 else "equirect"
+    out = []
+    for name in POSED:
+        t = (_rays_origins_ref.traced(name, kind, "scatter", k * W, k * H, s.key) if origins
+             else _rays_pose_ref.posed(name, kind, k * W, k * H, s.key))
+        out.append(t[:3] if k == 1 else (resolve_np(t[0], k), resolve_np(t[1], k), None))
+    return kind, out
+
+
+def check_posed(torch, sc, s, fmt, k, origins, W=13, H=7):
+    """render_frames_rays of the two poses in one launch, each frame against its own trace."""
+    kind, want = posed_traces(s, k, origins)
+    d = upload(torch, _rays_pose_ref.camera_map(kind, k * W, k * H))
+    o = upload(torch, _rays_origins_ref.origins("scatter", k * W, k * H)) if origins else None
+    for what, schedule in PASSES:
+        cols, bos = [pixels(torch, W, H, fmt) for _ in POSED], [pixels(torch, W, H, fmt) for _ in POSED]
+        sc.render_frames_rays(d, [t.ptr for t in cols], [t.ptr for t in bos], poses=[_rays_pose_ref.rows(n) for n in POSED],
+                              origins=o, fmt=fmt, ss=k, width=W, height=H, schedule=schedule)
+        torch.cuda.synchronize()
+        for i, name in enumerate(POSED):
+            assert_pair(cols[i], bos[i], want[i], fmt,
+                        f"{s.id} pose {name}{' with origins' if origins else ''} ss={k} fmt {fmt}, {what}")
+
+
+def check_shutter_rays(torch, sc, s, fmt, W=13, H=7):
+    """render_shutter_rays with the two poses as one exposure: the time tree over their traces."""
+    kind, frames = posed_traces(s, 1, False)
+    ref = tuple(_shutter_ref.time_tree_np(np.stack([f[t] for f in frames])) for t in (0, 1))
+    d = upload(torch, _rays_pose_ref.camera_map(kind, W, H))
+    for what, schedule in PASSES:
+        col, bo = pixels(torch, W, H, fmt), pixels(torch, W, H, fmt)
+        sc.render_shutter_rays(d, col.ptr, bo.ptr, poses=[_rays_pose_ref.rows(n) for n in POSED], fmt=fmt, width=W,
+                               height=H, schedule=schedule or T)
+        torch.cuda.synchronize()
+        assert_pair(col, bo, ref, fmt, f"{s.id} shutter over a posed map fmt {fmt}, {what}")
+
+
+@pytest.mark.parametrize("fmt", [F32, F16, BGRA8])
+@pytest.mark.parametrize("sid", FOLDS)
+def test_map_forms_by_fold_and_format(torch_cuda, sid, fmt):
+    """Every kernel that the ray-map launchers choose by format, fold and ss, at 13x7: the supersampled ray map, the
+    posed map and the posed map with origins, plain and supersampled, and the shutter over a posed map."""
+    torch = torch_cuda
+    s = S.BY_ID[sid]
+    W, H, k = 13, 7, 2
+    with Scene(s) as sc:
+        check_rays(torch, sc, s, _rays_ref.equirect_map(k * W, k * H), _rays_ref.position("F2"), W, H,
+                   _rays_ref.equirect_ss("F2", W, H, k, s.key), "equirect map from F2", k=k, fmt=fmt)
+        for origins in (False, True):
+            check_posed(torch, sc, s, fmt, 1, origins)
+            check_posed(torch, sc, s, fmt, k, origins)
+        check_shutter_rays(torch, sc, s, fmt)
+
+
+@pytest.mark.parametrize("sid", FOLDS)
+def test_lens_of_a_posed_map(torch_cuda, sid):
+    """render_lens(dirs=, pose=) and render_lens(dirs=, pose=, origins=) at 13x7: the records of the traces."""
+    torch = torch_cuda
+    s = S.BY_ID[sid]
+    W, H = 13, 7
+    with Scene(s) as sc:
+        for origins in (False, True):
+            kind, want = posed_traces(s, 1, origins)
+            d = upload(torch, _rays_pose_ref.camera_map(kind, W, H))
+            o = upload(torch, _rays_origins_ref.origins("scatter", W, H)) if origins else None
+            for i, name in enumerate(POSED):
+                for what, schedule in PASSES:
+                    lens = lens_records(torch, sc, W, H, schedule, dirs=d, pose=_rays_pose_ref.rows(name), origins=o)
+                    assert_records(lens, want[i][2], f"{sid} lens of pose {name}{' with origins' if origins else ''}, {what}")
 
 
 # ---- several frames in one launch ---------------------------------------------------------------------------------
