@@ -187,6 +187,8 @@ SIGNATURES = {
                                                  C.c_uint32, C.c_uint32, C.c_void_p]),
     "bh_srgb_encode_table": (C.c_int, [C.c_void_p]),
     "bh_div_magic_misses": (C.c_int64, [C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32)]),
+    "bh_first_step_host": (C.c_int, [C.POINTER(bh_camera_uniform), C.POINTER(bh_uniforms), C.c_uint32, C.c_uint32,
+                                     C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float)]),
     "bh_controller_update": (C.c_int, [C.POINTER(bh_controller), C.POINTER(bh_camera), C.c_float, C.c_int,
                                        C.POINTER(C.c_int)]),
     "bh_bloom": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,

@@ -41,6 +41,12 @@ struct FrameArgs {
     uint16_t* dbg_steps;
 };
 
+// A frame's first-step record (bh_host.cpp, first_step_record): what iteration 0 of the march computes from
+// ro = camera.pos alone, the same number in every lane of the frame -- dt0 = the step's dt, Q0 = (r^2 r^2) r and
+// rq0 = RN(1 / Q0) of k1's rd_derivative -- formed once on the host in IEEE f32.  Q0 == 0 marks a frame whose
+// record is not valid: its waves run iteration 0 themselves.
+struct FirstStep { float dt0, Q0, rq0; };
+
 // Everything one launch needs, passed by value as the kernel argument (lives in SGPRs / kernarg).
 // The per-frame fields (pos, c0..c2, cps, outputs) are frame 0's; a multi-frame launch (n_frames > 1,
 // tile schedule) also carries every frame's in `frames` and each wave selects its own.
@@ -105,6 +111,10 @@ struct MarchArgs {
     uint32_t clk_mask;
     uint32_t tx_magic;
     FrameArgs frames[BH_INLINE_FRAMES];
+    // the frames' first-step records, behind everything the kernels were compiled against: read by the exact builds'
+    // tile-schedule kernels alone (bh_march_tile.hpp, slot_head).  A launch of more than BH_INLINE_FRAMES frames has
+    // them behind its staged table instead, at frame_table + n_frames (MarchArgs has no free pointer word)
+    FirstStep first[BH_INLINE_FRAMES];
 };
 // The multiply-high form of a wave-uniform division by a launch constant: m with (n * m) >> 32 == n / d for every
 // n <= n_max, or 0 when no 32-bit m does that.  m = floor(2^32 / d) + 1 overshoots 2^32 / d by e / (d 2^32) with
@@ -115,9 +125,10 @@ inline uint32_t div_magic(uint32_t d, uint32_t n_max) {
     const uint64_t m = (1ull << 32) / d + 1u, e = m * d - (1ull << 32);
     return (uint64_t)n_max * e < (1ull << 32) ? (uint32_t)m : 0u;
 }
-// passed by value: the kernel argument segment holds at most 4 KiB (with the persistent kernel's
-// extra pointer)
-static_assert(sizeof(MarchArgs) + 8 <= 4096, "MarchArgs must fit the kernel argument segment");
+// passed by value: the kernel argument segment holds at most 4 KiB, with the arguments some kernels take behind
+// it -- the persistent kernel's pointer (8 bytes), the ray-map kernels' map (8), the origin-map kernels' two (16), the
+// shutter kernels' map and log2 n (16 with padding); the work-list march's RefineArgs, the largest, is asserted below it
+static_assert(sizeof(MarchArgs) + 16 <= 4096, "MarchArgs must fit the kernel argument segment");
 // the layout the existing kernels were compiled against: the supersampling words took the place of three
 // unused ones and moved nothing
 static_assert(offsetof(MarchArgs, far_r2) == 72 && offsetof(MarchArgs, ss_log2) == 76 &&
@@ -126,7 +137,8 @@ static_assert(offsetof(MarchArgs, far_r2) == 72 && offsetof(MarchArgs, ss_log2) 
               "MarchArgs: the supersampling words must stay inside the former reserved_[3]");
 static_assert(offsetof(MarchArgs, order) == 144 && offsetof(MarchArgs, sky) == 200 && offsetof(MarchArgs, out_col) == 232 &&
                   offsetof(MarchArgs, n_frames) == 272 && offsetof(MarchArgs, frames) == 304 &&
-                  sizeof(FrameArgs) == 104 && sizeof(MarchArgs) == 304 + BH_INLINE_FRAMES * sizeof(FrameArgs),
+                  sizeof(FrameArgs) == 104 && offsetof(MarchArgs, first) == 304 + BH_INLINE_FRAMES * sizeof(FrameArgs) &&
+                  sizeof(FirstStep) == 12 && sizeof(MarchArgs) == 304 + BH_INLINE_FRAMES * (sizeof(FrameArgs) + sizeof(FirstStep)),
               "MarchArgs: kernel argument layout changed");
 
 // The adaptive render's device-side work (bh_render_adaptive; bh_refine.hpp), a second kernel argument of
@@ -148,6 +160,7 @@ struct RefineArgs {
     uint32_t n_heads;    // 1..REFINE_HEADS head words in use (bh_march_tile.hpp, march_refine_kernel)
     float thr;           // refine::threshold(format, T)
 };
+static_assert(sizeof(MarchArgs) + sizeof(RefineArgs) <= 4096, "march_refine_kernel's arguments must fit the kernel argument segment");
 
 // One bh_shade_lens launch (bh_lens.hip): the lens of the virtual frame ss*width x ss*height, the sky to
 // sample and the row-major targets of width x height.

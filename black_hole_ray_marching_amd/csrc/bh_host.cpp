@@ -309,8 +309,8 @@ static void free_frame_table(bh_ctx::FrameTable& t) {
 // Stage the n frames' arguments in the device table of stream s (created at its first use): a pinned
 // ring slot is filled once its previous copy has executed, then copied in on the stream, ahead of the
 // order and march kernels that read it.  *dev receives the table.
-static int stage_frame_table(bh_ctx* c, hipStream_t s, const bh::FrameArgs* frames, uint32_t n,
-                             const bh::FrameArgs** dev) {
+static int stage_frame_table(bh_ctx* c, hipStream_t s, const bh::FrameArgs* frames, const bh::FirstStep* first,
+                             uint32_t n, const bh::FrameArgs** dev) {
     if (stream_capturing(s)) {
         g_last_error = "bh_render_frames: more than 32 frames per call cannot be captured into a graph";
         return BH_ERR_UNSUPPORTED;
@@ -321,7 +321,7 @@ static int stage_frame_table(bh_ctx* c, hipStream_t s, const bh::FrameArgs* fram
     if (!t) {
         bh_ctx::FrameTable n_t;
         n_t.stream = (void*)s;
-        const size_t bytes = sizeof(bh::FrameArgs) * BH_MAX_FRAMES;
+        const size_t bytes = (sizeof(bh::FrameArgs) + sizeof(bh::FirstStep)) * BH_MAX_FRAMES;
         hipError_t he = hipMalloc(&n_t.dev, bytes);
         for (uint32_t k = 0; he == hipSuccess && k < bh_ctx::FRAME_RING; ++k) {
             he = hipHostMalloc(&n_t.host[k], bytes, hipHostMallocDefault);
@@ -337,13 +337,18 @@ static int stage_frame_table(bh_ctx* c, hipStream_t s, const bh::FrameArgs* fram
     *dev = t->dev;
     // the same frames as the stream's previous table (a re-rendered camera path): nothing to copy,
     // the stream's earlier copy precedes this launch
-    if (t->last.size() == n && std::memcmp(t->last.data(), frames, sizeof(bh::FrameArgs) * n) == 0) return BH_OK;
+    // (the frames' first-step records stand behind the n frames, where the kernels look for them: frame_table + n)
+    const size_t fb = sizeof(bh::FrameArgs) * n, rb = sizeof(bh::FirstStep) * n;
+    if (t->last.size() == n && std::memcmp(t->last.data(), frames, fb) == 0 &&
+        std::memcmp(t->last_first.data(), first, rb) == 0)
+        return BH_OK;
     const uint32_t k = t->next;
     t->next = (k + 1u) % bh_ctx::FRAME_RING;
     hipError_t he = hipEventSynchronize(t->done[k]);  // a never-recorded event is complete
     if (he == hipSuccess) {
-        std::memcpy(t->host[k], frames, sizeof(bh::FrameArgs) * n);
-        he = hipMemcpyAsync(t->dev, t->host[k], sizeof(bh::FrameArgs) * n, hipMemcpyHostToDevice, s);
+        std::memcpy(t->host[k], frames, fb);
+        std::memcpy(reinterpret_cast<unsigned char*>(t->host[k]) + fb, first, rb);
+        he = hipMemcpyAsync(t->dev, t->host[k], fb + rb, hipMemcpyHostToDevice, s);
     }
     if (he == hipSuccess) he = hipEventRecord(t->done[k], s);
     if (he != hipSuccess) {
@@ -351,6 +356,7 @@ static int stage_frame_table(bh_ctx* c, hipStream_t s, const bh::FrameArgs* fram
         return hip_fail(he, "frame table upload");
     }
     t->last.assign(frames, frames + n);
+    t->last_first.assign(first, first + n);
     return BH_OK;
 }
 
@@ -426,6 +432,72 @@ static void frame_args(const bh_camera_uniform* cam, float rs, const bh_render_d
     for (int k = 0; k < 3; ++k) F->cps[k] = (-n[k] * 1.5f) * rs;
     F->out_col = d->out_col; F->out_blackout = d->out_blackout;
     F->dbg_n_rk = d->dbg_n_rk; F->dbg_fate = d->dbg_fate; F->dbg_steps = d->dbg_steps;
+}
+
+// A/B switch (diagnostics): BH_NO_FIRST_STEP set => no frame has a first-step record, every wave runs iteration 0
+static bool first_step_disabled() {
+    static const bool off = std::getenv("BH_NO_FIRST_STEP") != nullptr;
+    return off;
+}
+
+// The frame's first-step record (bh_common.hpp, FirstStep): iteration 0 of the march loop up to k1's denominator, for
+// ro = camera.pos, restated from bh_march_step.hpp's step_bf in its XOps<false> form -- IEEE f32, one rounding per op,
+// in the device's association (this unit is built without contraction); tests/test_first_step_host.py ties it to the
+// oracle's own iteration 0.  The record is valid (true) only where every guard of step_bf whose operands are
+// frame-uniform holds and no exit of iteration 0 can fire, each comparison written so that a NaN fails it:
+//   finite inputs, dtm > 0, rs > 0;  1.01 < r^2 <= 2^24 (the camera outside the unit sphere: no blackout at
+//   iteration 0, `outside` becomes 1; and Q0 = r^5 <= 2^60 >= 2^-40, the division core's denominator domain);
+//   sdf >= MIN_DIST (no surface);  2^-25 <= dt0 <= 2^13 (rd_half's and add2's premises);  dt0 <= max_dist (no
+//   escape: travelled = 0 + dt0);  max_iters >= 2 (no cap).
+// An invalid record is all zeros: Q0 == 0 is the mark the waves test.
+static bool first_step_record(const float pos[3], const float cps[3], float rs, float dtm, float max_dist,
+                              uint32_t scene_flags, uint32_t max_iters, bh::FirstStep* out) {
+    *out = bh::FirstStep{0.0f, 0.0f, 0.0f};
+    const float x = pos[0], y = pos[1], z = pos[2];
+    const float in[8] = {x, y, z, cps[0], cps[1], cps[2], rs, dtm};
+    for (float v : in)
+        if (!std::isfinite(v)) return false;
+    if (!(dtm > 0.0f) || !(rs > 0.0f) || !(max_iters >= 2u)) return false;
+    const float r2 = (x * x + y * y) + z * z;                          // dot(ro, ro)
+    if (!(r2 > 1.01f && r2 <= 0x1p24f)) return false;
+    const float r0 = std::sqrt(r2);                                    // :271
+    const float dtr = dtm * r0;
+    // sdf (:119-123), as XOps::sdf_args / sdf_from form it; sdf_of_terms' rule for a disabled term
+    const float rho = std::sqrt(x * x + z * z);
+    const float disc = std::fmax(std::fmax(rho - 6.0f * rs, -(rho - 3.0f * rs)), std::fabs(y - 0.0f) - 0.02f);
+    const float xx = x * x, yy = y * y;
+    const float dz = -10.0f - z, zz = dz * dz;
+    const float ty = 10.0f - std::fabs(y), tx = 10.0f - std::fabs(x);
+    const float qy = (xx + ty * ty) + zz, qx = (tx * tx + yy) + zz;
+    const float m = std::sqrt(std::fmin(qy, qx)) - 0.5f;
+    float ds;
+    if (!(scene_flags & BH_SCENE_MARKERS)) ds = (scene_flags & BH_SCENE_DISC) ? disc : INFINITY;
+    else ds = (scene_flags & BH_SCENE_DISC) ? std::fmin(disc, m) : m;
+    if (!(ds >= 0.001f)) return false;                                 // :286-288 (MIN_DIST)
+    const float dx = cps[0] - x, dy = cps[1] - y, dzp = cps[2] - z;    // :294
+    const float dps = std::sqrt((dx * dx + dy * dy) + dzp * dzp) - 0.075f;
+    const float dist = std::fmin(ds, dps);                             // :299
+    const float dt0 = std::fmin(dist * 0.9f, dtr);                     // :307-310
+    if (!(dt0 >= 0x1p-25f && dt0 <= 0x1p13f) || !(dt0 <= max_dist)) return false;
+    const float Q0 = (r2 * r2) * r0;                                   // pow(r2, 2.5) (:126)
+    const float rq0 = 1.0f / Q0;
+    if (!(Q0 >= 0x1p-40f && Q0 <= 0x1p60f)) return false;              // implied by r2's range; kept as the core states it
+    *out = bh::FirstStep{dt0, Q0, rq0};
+    return true;
+}
+
+int bh_first_step_host(const bh_camera_uniform* cam, const bh_uniforms* U, uint32_t scene_flags, uint32_t max_iters,
+                       float* dt0, float* Q0, float* rq0) {
+    if (!cam || !U) return 0;
+    bh::FrameArgs F;
+    bh_render_desc d{};
+    frame_args(cam, U->rs, &d, &F);
+    bh::FirstStep fs;
+    const bool ok = first_step_record(F.pos, F.cps, U->rs, U->delta_time_mult, U->max_dist, scene_flags, max_iters, &fs);
+    if (dt0) *dt0 = fs.dt0;
+    if (Q0) *Q0 = fs.Q0;
+    if (rq0) *rq0 = fs.rq0;
+    return ok ? 1 : 0;
 }
 
 // What a frame's per-tile costs (the march's step counts) depend on: the camera, the shader uniforms and the
@@ -531,6 +603,7 @@ struct Launch {
     bh_render_desc d;                  // the launch's desc: the virtual frame's (per-frame outputs stay in descs[i])
     bh::MarchArgs a;                   // the kernel argument
     std::vector<bh::FrameArgs> table;  // more than BH_INLINE_FRAMES frames: staged in the stream's device table
+    std::vector<bh::FirstStep> first_table;  // ... and their first-step records, staged behind the table
     uint64_t n_tiles = 0;              // the shard's tiles
     uint32_t shutter_log2 = 0;         // bh_render_shutter: log2 of the cameras per output frame (a.n_frames counts cameras)
     const float* ray_map = nullptr;    // bh_render_rays, bh_render_lens_rays: the device map the rays come from
@@ -622,6 +695,13 @@ static void fill_args(const bh_ctx* c, uint32_t n_frames, const bh_camera_unifor
     if (n_frames > bh::BH_INLINE_FRAMES) L->table.resize(n_frames);
     bh::FrameArgs* fa = L->table.empty() ? a.frames : L->table.data();
     for (uint32_t i = 0; i < n_frames; ++i) frame_args(&cams[i], a.rs, &descs[i], &fa[i]);
+    // the frames' first-step records, for the exact builds' tile-schedule kernels (the others never read them); the
+    // records of a staged launch ride behind its table
+    if (!L->table.empty()) L->first_table.assign(n_frames, bh::FirstStep{0.0f, 0.0f, 0.0f});
+    bh::FirstStep* fs = L->table.empty() ? a.first : L->first_table.data();
+    if (d->math == BH_MATH_EXACT && (d->schedule & 0xFFu) == BH_SCHED_TILE && !first_step_disabled())
+        for (uint32_t i = 0; i < n_frames; ++i)
+            (void)first_step_record(fa[i].pos, fa[i].cps, a.rs, a.dtm, a.max_dist, a.scene_flags, a.max_iters, &fs[i]);
     // frame 0's fields again in the argument itself: what the kernels of a one-frame launch read
     const bh::FrameArgs& F = fa[0];
     for (int k = 0; k < 3; ++k) {
@@ -634,7 +714,7 @@ static void fill_args(const bh_ctx* c, uint32_t n_frames, const bh_camera_unifor
 // The frames' table of a launch of more than BH_INLINE_FRAMES frames, staged on the stream
 static int stage_frames(bh_ctx* c, hipStream_t s, Launch* L) {
     if (L->table.empty()) return BH_OK;
-    return stage_frame_table(c, s, L->table.data(), L->a.n_frames, &L->a.frame_table);
+    return stage_frame_table(c, s, L->table.data(), L->first_table.data(), L->a.n_frames, &L->a.frame_table);
 }
 
 // The dispatch order the tile schedule learned from this (geometry, shard, stream)'s last frame: a.order, and

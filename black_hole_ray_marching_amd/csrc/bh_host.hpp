@@ -79,11 +79,12 @@ struct bh_ctx {
     static constexpr uint32_t FRAME_RING = 4;
     struct FrameTable {
         void* stream = nullptr;
-        bh::FrameArgs* dev = nullptr;                 // BH_MAX_FRAMES entries
-        bh::FrameArgs* host[FRAME_RING] = {};         // pinned, BH_MAX_FRAMES entries each
+        bh::FrameArgs* dev = nullptr;                 // BH_MAX_FRAMES entries, and room for as many FirstStep records
+        bh::FrameArgs* host[FRAME_RING] = {};         // pinned, the same size each
         hipEvent_t done[FRAME_RING] = {};             // the slot's copy has executed
         uint32_t next = 0;
         std::vector<bh::FrameArgs> last;              // what the table holds once the stream's copies ran
+        std::vector<bh::FirstStep> last_first;        // ... and the first-step records behind its frames
     };
     std::vector<FrameTable> frame_tables;
     // post-processing (bh_bloom) scratch: one set of textures per (width, height, levels), with the

@@ -116,9 +116,15 @@ __device__ __forceinline__ uint32_t march_cycles(const MarchArgs& a, const Frame
 }
 
 // March one ray to its end (the tile schedule's loop): `fate` and `steps` (RK updates executed).
-template <uint32_t SF, bool SHUT = false>
+// PEEL (the exact builds' forms that take iteration 0 from the frame's first-step record, march_slot_body): the loop
+// starts at iteration it0 = st.n_rk, 0 or 1 (wave-uniform), and *prev is the other state of the ping-pong -- st itself
+// before step_first when it0 is 1 (n_rk 0: the roles the comment below describes), any copy of st when it is 0.  The
+// PRIO_ITERS iterations then end at PRIO_ITERS + it0, where the priority is raised and the cycle search begins: it reads
+// n_rk and is valid from any iteration.
+template <uint32_t SF, bool SHUT = false, bool PEEL = false>
 __device__ __forceinline__ void march_ray(const MarchArgs& a, const Frame& f, RayState& st, uint32_t& fate,
-                                          uint32_t& steps, uint32_t lane) {
+                                          uint32_t& steps, uint32_t lane, [[maybe_unused]] const RayState* prev = nullptr,
+                                          [[maybe_unused]] uint32_t it0 = 0u) {
     // Two iterations per trip, ping-ponging the state between st and sb (march_step_io never
     // writes its input, so no per-step register copies).  The lane's final state is the output
     // of its last iteration, or its input for the fates decided before the RK update: the one of
@@ -132,12 +138,14 @@ __device__ __forceinline__ void march_ray(const MarchArgs& a, const Frame& f, Ra
     // iteration.  (390 -> 370 VALU per step; with the flag template and the guard pooling
     // 0.842 -> 0.837 ms headline, 0.99 -> 0.92 ms at cap 1000, A/B r01.)
     RayState sb = st;
+    if constexpr (PEEL) sb = *prev;
+    const uint32_t first = PEEL ? it0 : 0u;
     bool alive = true;
     // TRIP_PAIRS ping-pong pairs per trip of the wave-uniform loop (1 / 2 / 3 pairs: 0.689 / 0.688
     // / 0.686 ms, A/B r01): fewer trip tests and their ballot materialisation per step.
     constexpr uint32_t TRIP_PAIRS = 3;
     static_assert(PRIO_ITERS % (2u * TRIP_PAIRS) == 0u, "whole trips");
-    for (uint32_t it = 0; it < PRIO_ITERS && __builtin_amdgcn_ballot_w64(alive) != 0ull; it += 2u * TRIP_PAIRS) {
+    for (uint32_t it = first; it < PRIO_ITERS + first && __builtin_amdgcn_ballot_w64(alive) != 0ull; it += 2u * TRIP_PAIRS) {
 #pragma unroll
         for (uint32_t j = 0; j < TRIP_PAIRS; ++j) {
             if (alive) {

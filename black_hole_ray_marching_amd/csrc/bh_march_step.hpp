@@ -520,6 +520,49 @@ __device__ __forceinline__ bool step_tail(const MarchArgs& a, const Frame& f, co
 }
 #endif
 
+#if !BH_FAST
+// Iteration 0 of a frame whose first-step record is valid (bh_common.hpp FirstStep; bh_host.cpp, first_step_record),
+// from `in` -- the ray at the camera: ro = ro0, travelled 0, n_rk 0 -- into `out`.  Every ray of the frame starts at
+// ro0 (:363), so what step_bf forms from ro alone before the RK update is one number per frame and the host holds
+// it: dt = fs.dt0, and k1's denominator Q = fs.Q0 with RN(1 / Q) = fs.rq0 (rcp_refined's value for a normal Q).  The
+// host's gate rules out every exit of this iteration (blackout, surface, escape, cap: no fate) and every guard whose
+// operands are the frame's (Q's range, dt's); what is left is step_bf's RK update in its XOps<true> form -- the same
+// ops in the same order -- with its per-lane guards.  Returns their verdict: true when an operand of this lane left
+// a core's domain, and `out` is then not to be used -- the wave runs iteration 0 by the loop's own step instead.
+__device__ __forceinline__ bool step_first(const RayState& in, RayState& out, const FirstStep& fs) {
+    XOps<true> X;
+    const v3 ro = in.ro, rd = in.rd;
+    const float s = in.s, dt = fs.dt0;
+    // k1 = rd_derivative(ro0): accel_qs<1> with the frame's reciprocal
+    const float nx = s * ro.x, ny = s * ro.y, nz = s * ro.z;
+    X.kmin = crm::kmin3(crm::key(nx), crm::key(ny), crm::key(nz));
+    const crm::Rcp R{fs.Q0, fs.rq0};
+    const v3 ro_k1 = smul(dt, rd);
+    const v3 rd_k1 = smul(dt, mk(crm::div_core(nx, R), crm::div_core(ny, R), crm::div_core(nz, R)));
+    const v3 ro_k2 = smul(dt, X.rd_half(rd, rd_k1));
+    const v3 rd_k2 = smul(dt, X.template accel<2>(X.ro_half(ro, ro_k1), s));
+    const v3 ro_k3 = smul(dt, X.rd_half(rd, rd_k2));
+    const v3 rd_k3 = smul(dt, X.template accel<3>(X.ro_half(ro, ro_k2), s));
+    const v3 ro_k4 = smul(dt, add(rd, rd_k3));
+    const v3 rd_k4 = smul(dt, X.template accel<4>(add(ro, ro_k3), s));
+    const v3 sro = add(X.add2(X.add2(ro_k1, ro_k2), ro_k3), ro_k4);
+    const v3 srd = add(X.add2(X.add2(rd_k1, rd_k2), rd_k3), rd_k4);
+    const v3 dro = X.template div6<0>(sro);
+    const v3 drd = X.template div6<1>(srd);
+    X.bad |= X.kmin < crm::KEY_ACC_MIN;
+    X.bad |= !(X.amin >= crm::ACC_N_MIN);
+    X.bad |= !(X.amin6 >= crm::DIV_N_MIN);  // dt0 != 0
+    X.bad |= !(fabsf(s) <= 0x1p30f);
+    out.ro = add(ro, dro);
+    out.rd = add(rd, drd);
+    out.travelled = in.travelled + dt;
+    out.s = s;
+    out.n_rk = in.n_rk + 1u;
+    out.outside = 1u;  // r0 > 1
+    return X.bad;
+}
+#endif
+
 // One iteration for one ray from `in` into `out` (step_bf<true> contract: `out` is not written for
 // fates before the RK update), with the exact mode's guarded fast path and its rare IEEE re-run.
 template <uint32_t SF = SF_DYN, bool UNI = false, bool TINY = false>

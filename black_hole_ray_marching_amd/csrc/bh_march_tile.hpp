@@ -54,12 +54,21 @@ __device__ __forceinline__ void select_outputs(MarchArgs& a, const BH_CONST_AS F
 // this launch) so that a kernel can have them in flight while its table copy is (march_tile_wave).  The two
 // divisions by launch constants are multiply-highs by the host's magics (bh_host.cpp, div_magic; 0: none, divide).
 // ok == false: the order entry is out of range (defensive: a corrupt order must not address outside the shard).
+// FS: the frame's first-step record too (bh_common.hpp FirstStep), three more words of the same trip -- behind the
+// inline frames in the argument, or behind the n_frames entries of the staged table.  form_first_step says which forms
+// ask for it: the exact builds', except the origin-map forms, whose rays do not start at the frame's position.
 struct SlotHead {
     uint32_t fi, t, tx, ty;
     FrameCamera cam;
+    FirstStep fs;
     bool ok;
 };
-template <bool ITEM>
+__device__ __forceinline__ FirstStep load_first_step(const MarchArgs& A, uint32_t fi) {
+    const BH_CONST_AS FirstStep* p = A.frame_table ? (const BH_CONST_AS FirstStep*)(const_as(A.frame_table) + A.n_frames)
+                                                   : const_as(&A.first[0]);
+    return {p[fi].dt0, p[fi].Q0, p[fi].rq0};
+}
+template <bool ITEM, bool FS = false>
 __device__ __forceinline__ SlotHead slot_head(const MarchArgs& A, uint32_t slot, uint32_t item_tx = 0u, uint32_t item_ty = 0u) {
     SlotHead h{};
     const uint32_t nf = A.n_frames;
@@ -72,6 +81,7 @@ __device__ __forceinline__ SlotHead slot_head(const MarchArgs& A, uint32_t slot,
     }
     h.fi = fi;
     h.cam = load_camera(frame_args_of(A, fi));
+    if constexpr (FS) h.fs = load_first_step(A, fi);
     if constexpr (ITEM) {
         h.tx = item_tx;
         h.ty = item_ty;
@@ -125,6 +135,7 @@ __device__ __forceinline__ SlotHead slot_head(const MarchArgs& A, uint32_t slot,
 // A form is a mask of these bits, one template argument of march_slot_body, march_slot, march_tile_wave and
 // shutter_workgroup; march_slot_body's static_asserts say which masks are forms.
 constexpr uint32_t F_SS = 1u, F_ITEM = 2u, F_LENS = 4u, F_SHUT = 8u, F_RAYS = 16u, F_POSE = 32u, F_ORG = 64u;
+constexpr bool form_first_step(uint32_t form) { return !BH_FAST && !(form & F_ORG); }
 struct ShutterLane { uint32_t px, py; bool valid, ok; };
 // The ORG form's prologue.  org_load: both 12-byte loads of a valid lane issued before either is used (one wait), and
 //     d = (mx r + my u) + mz f,   ro0 = pos + ((ox r + oy u) + oz f)
@@ -220,19 +231,46 @@ __device__ __forceinline__ void march_slot_body(const MarchArgs& A, const SlotHe
     st.n_rk = 0;
     st.outside = 0u;
     uint32_t fate = 0xFFu, steps = 0;
+    constexpr bool PEEL = form_first_step(FORM);
     if (valid) {
+        // Iteration 0 from the frame's first-step record where it is valid (Q0 != 0: a scalar branch), ahead of the
+        // choice of the step below: st becomes the ray after one RK update and s0 keeps the ray at the camera, the
+        // loop's other state.  A lane whose operands leave a core's domain (step_first) sends the whole wave to the
+        // loop's own iteration 0, which re-runs such lanes in IEEE ops.
+        [[maybe_unused]] RayState s0 = st;
+        [[maybe_unused]] uint32_t it0 = 0u;
+#if !BH_FAST
+        if constexpr (PEEL) {
+            if (h.fs.Q0 != 0.0f) {
+                RayState s1;
+                const bool bad = step_first(st, s1, h.fs);
+                if (__builtin_amdgcn_ballot_w64(bad) == 0ull) {
+                    st = s1;
+                    it0 = 1u;
+                }
+            }
+        }
+#endif
         // the camera outside the unit sphere (1.01 leaves room for any rounding of |ro0|^2 against the
         // step's own r^2 > 1 + 2^-23 at iteration 0) and |s| <= 2^30 on every lane: the step without the
         // ingoing test and the |s| guard (wave-uniform: a scalar branch)
         if constexpr (SF != SF_DYN) {
             // ORG: the origin is the lane's, so the choice is a property of the wave's valid lanes -- every one of
             // them outside, in the one ballot; any other mix takes the general step, which covers each lane
+            // (a wave that took iteration 0 from the record has both: the record's gate and step_first's guard)
             const bool out = ORG ? __builtin_amdgcn_ballot_w64(!((dot(f.ro0, f.ro0) > 1.01f) & (fabsf(st.s) <= 0x1p30f))) == 0ull
-                                 : (dot(f.ro0, f.ro0) > 1.01f) && (__builtin_amdgcn_ballot_w64(!(fabsf(st.s) <= 0x1p30f)) == 0ull);
-            if (__builtin_amdgcn_readfirstlane((int)out)) march_ray<SF | SF_CAM_OUT, SHUT>(a, f, st, fate, steps, lane);
-            else march_ray<SF, SHUT>(a, f, st, fate, steps, lane);
+                                 : (PEEL && it0 != 0u) ||
+                                   ((dot(f.ro0, f.ro0) > 1.01f) && (__builtin_amdgcn_ballot_w64(!(fabsf(st.s) <= 0x1p30f)) == 0ull));
+            if (__builtin_amdgcn_readfirstlane((int)out)) {
+                march_ray<SF | SF_CAM_OUT, SHUT, PEEL>(a, f, st, fate, steps, lane, &s0, it0);
+            } else {
+                // it0 == 0 here: the ray at the camera, named as such -- this arm then needs nothing of step_first's,
+                // which the camera-outside arm ahead of it would otherwise hold in registers through its loop
+                if constexpr (PEEL) st = s0;
+                march_ray<SF, SHUT>(a, f, st, fate, steps, lane);
+            }
         } else {
-            march_ray<SF, SHUT>(a, f, st, fate, steps, lane);
+            march_ray<SF, SHUT, PEEL>(a, f, st, fate, steps, lane, &s0, it0);
         }
     }
     if constexpr (SHUT) {
@@ -285,7 +323,7 @@ __device__ __forceinline__ void march_slot(const MarchArgs& A, uint32_t slot, co
                                            uint32_t lane, uint32_t item_tx = 0u, uint32_t item_ty = 0u,
                                            ShutterLane* sl = nullptr, const float* dirs = nullptr,
                                            const float* orgs = nullptr) {
-    const SlotHead h = slot_head<(FORM & F_ITEM) != 0u>(A, slot, item_tx, item_ty);
+    const SlotHead h = slot_head<(FORM & F_ITEM) != 0u, form_first_step(FORM)>(A, slot, item_tx, item_ty);
     if (!h.ok) return;
     march_slot_body<FMT, SF, FORM>(A, h, lut, lane, sl, dirs, orgs);
 }
@@ -338,7 +376,7 @@ __device__ __forceinline__ void march_tile_wave(const MarchArgs& A, float* lut, 
     if constexpr (!LENS) rows = srgb_fetch<FMT>(A);
     const uint32_t slot = __builtin_amdgcn_readfirstlane(blockIdx.x * WG_WAVES + (threadIdx.x >> 6));
     if (slot >= A.n_tiles * A.n_frames) return;  // wave-uniform, and the wave is its workgroup: nobody waits for it
-    const SlotHead h = slot_head<false>(A, slot);
+    const SlotHead h = slot_head<false, form_first_step(FORM)>(A, slot);
     if constexpr (!LENS) {
         srgb_store<FMT>(rows, lut);
         __syncthreads();

@@ -179,6 +179,16 @@ def srgb_encode_table() -> np.ndarray:
     return out
 
 
+def first_step_host(camera_uniform: "CameraUniform", uniforms: "Uniforms", scene_flags: int = BH_SCENE_DEFAULT,
+                    max_iters: int = 512) -> tuple[bool, np.float32, np.float32, np.float32]:
+    """bh_first_step_host: (valid, dt0, Q0, rq0) -- iteration 0 of the march as the host forms it once per frame for
+    the exact tile-schedule kernels; an invalid record is (False, 0, 0, 0) and the waves run iteration 0 themselves."""
+    dt0, q0, rq0 = C.c_float(), C.c_float(), C.c_float()
+    ok = load().bh_first_step_host(C.byref(camera_uniform.c), C.byref(uniforms.to_c()), scene_flags, max_iters,
+                                   C.byref(dt0), C.byref(q0), C.byref(rq0))
+    return bool(ok), np.float32(dt0.value), np.float32(q0.value), np.float32(rq0.value)
+
+
 def shard_tile_count(width: int, height: int, shard_index: int, shard_count: int) -> int:
     n = load().bh_shard_tile_count(width, height, shard_index, shard_count)
     if n < 0:

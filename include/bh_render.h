@@ -778,6 +778,16 @@ int bh_srgb_encode_table(float* out257);
  * which (n * magic) >> 32 differs from n / d (0 when magic is 0), or a negative status. */
 int64_t bh_div_magic_misses(uint32_t d, uint32_t n_max, uint32_t* magic);
 
+/* Diagnostics of a launch's host-side constants: the first-step record of a frame -- what iteration 0 of the march
+ * loop computes from the camera's position alone, the same in every ray of the frame: *dt0 = the step's dt,
+ * *Q0 = (r^2 r^2) r and *rq0 = RN(1 / Q0) of the first rd_derivative, in IEEE f32.  Returns 1 when the record is valid
+ * (the exact tile-schedule kernels then take iteration 0 from it), 0 when it is not (the outputs are then 0 and the
+ * waves run iteration 0 themselves: non-finite inputs, delta_time_mult <= 0, rs <= 0, a camera at r^2 <= 1.01 or
+ * > 2^24, a camera on a surface, dt0 outside [2^-25, 2^13] or above max_dist, max_iters < 2).  Output pointers may
+ * be NULL.  Additive: BH_ABI_VERSION unchanged, callers probe for the symbol. */
+int bh_first_step_host(const bh_camera_uniform* camera, const bh_uniforms* uniforms, uint32_t scene_flags,
+                       uint32_t max_iters, float* dt0, float* Q0, float* rq0);
+
 /* Diagnostics: check the correctly rounded division/sqrt cores the exact kernel uses against IEEE
  * results on `device` (op 0: sqrt over float bit patterns [base, base+count); op 1: x/6 over bit
  * patterns [base, base+count); op 2: n/d on `count` random pairs seeded by base; op 3: n/d near exact
