@@ -128,11 +128,14 @@ __device__ __forceinline__ void march_ray(const MarchArgs& a, const Frame& f, Ra
     // Two iterations per trip, ping-ponging the state between st and sb (march_step_io never
     // writes its input, so no per-step register copies).  The lane's final state is the output
     // of its last iteration, or its input for the fates decided before the RK update: the one of
-    // st / sb with the larger n_rk, once a lane leaving before the RK update has zeroed the
-    // other's n_rk (it may hold a discarded output of the guarded first pass).  The input of
-    // iteration i holds n_rk = i and the other register i - 1 or (i = 0) the same state, so no
-    // per-step flag records where the state is (-6 VALU per step: headline -0.5 %, A/B r02,
-    // profiles/r02c/ab_inb/).  The trip condition is wave-uniform and each lane's iteration is
+    // st / sb with the larger n_rk.  The steps of this loop keep no n_rk (step_bf, UNI): the two
+    // registers hold what they held at the loop's start -- st 0 or (after step_first) 1, sb 0 --
+    // until the lane ends at iteration i, where lane_end writes the one that names the final state:
+    // i into the step's input for a fate before the RK update (i >= the input's old value, and a
+    // tie goes to st, which is the input at i = 0), i + 1 into its output otherwise (> 1).  So no
+    // per-step flag records where the state is, and no per-step count.  (The flag: -6 VALU per step,
+    // headline -0.5 %, A/B r02, profiles/r02c/ab_inb/; the count and the late fate: round 24.)
+    // The trip condition is wave-uniform and each lane's iteration is
     // predicated: with a divergent loop exit the state would be live out of the loop at a
     // different iteration per lane, which costs a register copy of every state value per
     // iteration.  (390 -> 370 VALU per step; with the flag template and the guard pooling
@@ -141,6 +144,26 @@ __device__ __forceinline__ void march_ray(const MarchArgs& a, const Frame& f, Ra
     if constexpr (PEEL) sb = *prev;
     const uint32_t first = PEEL ? it0 : 0u;
     bool alive = true;
+    // iteration i of a live lane, from `in` into `out`, and the lane's end if it ends there: e is the step's StepEnd,
+    // pf the fate it wrote if before_rk (both this step's own: nothing of them is carried from step to step)
+    auto iterate = [&](RayState& in, RayState& out, uint32_t i) {
+        StepEnd e;
+        uint32_t pf;
+        if (march_step_io<SF, true>(a, f, in, out, pf, i, &e)) {
+            alive = false;
+            if (e.before_rk) {
+                in.n_rk = i;
+                fate = pf;
+            } else {
+                out.n_rk = i + 1u;
+                // the select stays here, behind an opaque operand: as a plain zext of the step's compare it is
+                // formed in the step's own block, on every step
+                uint32_t esc = (uint32_t)BH_FATE_ESCAPE;
+                asm volatile("" : "+v"(esc));
+                fate = e.escape ? esc : (uint32_t)BH_FATE_CAP;
+            }
+        }
+    };
     // TRIP_PAIRS ping-pong pairs per trip of the wave-uniform loop (1 / 2 / 3 pairs: 0.689 / 0.688
     // / 0.686 ms, A/B r01): fewer trip tests and their ballot materialisation per step.
     constexpr uint32_t TRIP_PAIRS = 3;
@@ -148,21 +171,17 @@ __device__ __forceinline__ void march_ray(const MarchArgs& a, const Frame& f, Ra
     for (uint32_t it = first; it < PRIO_ITERS + first && __builtin_amdgcn_ballot_w64(alive) != 0ull; it += 2u * TRIP_PAIRS) {
 #pragma unroll
         for (uint32_t j = 0; j < TRIP_PAIRS; ++j) {
-            if (alive) {
-                if (march_step_io<SF, true>(a, f, st, sb, fate, it + 2u * j)) {
-                    alive = false;
-                    if (fate_before_rk(fate)) sb.n_rk = 0u;
-                }
-            }
-            if (alive) {
-                if (march_step_io<SF, true>(a, f, sb, st, fate, it + 2u * j + 1u)) {
-                    alive = false;
-                    if (fate_before_rk(fate)) st.n_rk = 0u;
-                }
-            }
+            if (alive) iterate(st, sb, it + 2u * j);
+            if (alive) iterate(sb, st, it + 2u * j + 1u);
         }
     }
     if (sb.n_rk > st.n_rk) st = sb;
+    if (alive) {
+        // still marching: the whole trips ended in st, at iteration PRIO_ITERS + first; the tail's steps keep the
+        // books themselves (n_rk, and `outside`, which a camera-outside step of the loop above never wrote)
+        st.n_rk = PRIO_ITERS + first;
+        if constexpr (sf_cam_out(SF)) st.outside = 1u;
+    }
     steps = st.n_rk;
     if (alive) {
         // A wave still marching after PRIO_ITERS iterations (~4x the mean step count) holds a

@@ -95,6 +95,9 @@ constexpr float R2_GT1 = 0x1.000002p0f;
 
 __device__ __forceinline__ bool fate_before_rk(uint32_t fate) { return fate >= BH_FATE_SURFACE; }
 
+// The lanes (of those active) where p holds.  For p a single compare this is the compare's result as it stands.
+__device__ __forceinline__ uint64_t lane_mask(bool p) { return __builtin_amdgcn_ballot_w64(p); }
+
 // (Measured and not kept, DESIGN.md §5: a "sticky" root-free test that skips the test after a step that took
 // the roots; per-term ballots deciding the all-terms test too, 0.5189 vs 0.5193 ms, profiles/r05/sdf_terms3/;
 // terms cleared by the lane's radius alone, 0.5217 -> 0.5261 ms, profiles/r05/sdf_radii/, §5 item 29.)
@@ -164,20 +167,28 @@ __device__ __forceinline__ SdfSlack sdf_term_slacks(const MarchArgs& a, uint32_t
 __device__ __forceinline__ float sdf_skip_slack(const SdfSlack& t) { return fminf(fminf(t.disc, t.mark), t.ps); }
 #endif
 
-// UNI: every active lane of the wave is at loop iteration `it` (n_rk == it: the ping-pong loop), so the
-// cap test is a wave-uniform (scalar) compare.
+// How a lane's step ended, where step_bf returned true under the UNI contract: before the RK update (`fate` written)
+// or after it, by escape or by the cap.  Lane masks.
+struct StepEnd { bool before_rk, escape; };
+// UNI: every active lane of the wave is at loop iteration `it` (the ping-pong loop, march_ray), so the cap test is a
+// wave-uniform (scalar) compare -- and the step keeps no books that only a lane's end reads: it neither reads nor
+// writes n_rk (the caller knows `it`), and it writes `fate` only where a lane ends before the RK update; *end says
+// which end it was (StepEnd), and for a lane that ends after the update the caller's done-block forms the fate from
+// it, so no step that ends nothing pays for a fate (-2 VALU on every step).
+// SF_CAM_OUT steps do not write `outside` either: nothing in them reads it (march_ray sets it where the tail begins).
 // TINY (the tail's steps): rd + 0.5 k unfused -- the WGSL's own op order, exact for any dt -- where the fused
 // form's premise (|dt| >= 2^-25) would send a step with a tiny dt to the IEEE re-run.  The photon-sphere rays whose steps shrink below 2^-25 without
 // settling into an exact cycle take hundreds of such steps (camera B: 42 rays, ~210 tiny steps each).
 template <bool BRANCHY, class Ops, uint32_t SF = SF_DYN, bool UNI = false, bool TINY = false>
 __device__ __forceinline__ bool step_bf(const MarchArgs& a, const Frame& f, const RayState& in, RayState& out, Ops& X,
-                                        uint32_t& fate, uint32_t it = 0u) {
+                                        uint32_t& fate, uint32_t it = 0u, [[maybe_unused]] StepEnd* end = nullptr) {
     constexpr uint32_t SFS = sf_scene(SF);
     constexpr bool CO = sf_cam_out(SF);
+    static_assert(!UNI || BRANCHY, "the uniform-iteration contract is the single-ray step's");
     const uint32_t scene_flags = (SFS == SF_DYN) ? a.scene_flags : SFS;
     const v3 ro = in.ro, rd = in.rd;
     const float travelled = in.travelled, s = in.s;
-    const uint32_t n_rk = in.n_rk;
+    const uint32_t n_rk = UNI ? it : in.n_rk;
     const float r2 = dot(ro, ro);
     const float r = X.sqrt(r2);                                        // :271
     // :272-283: blackout if (r < 1 and rd.ro < 0), or if !(r > 1) and the ray was outside before;
@@ -189,15 +200,27 @@ __device__ __forceinline__ bool step_bf(const MarchArgs& a, const Frame& f, cons
     // guard on it.
     const bool bo_on = a.blackout_eh != 0u;
     const bool not_out = !(r2 > R2_GT1);                               // NaN: "else" branch, as the WGSL
-    // rd.ro < 0 only matters for lanes inside r < 1 (the black hole's interior: rare).  Written
-    // behind a wave-uniform test; the compiler still speculates the product into the step and
-    // selects on the test (s_cselect), but the resulting schedule measured 0.7 % faster than the
-    // unconditional form (A/B r01, two pairs).  Forcing a real branch materialises the predicates as
-    // integers in VGPRs (+8 VALU): slower.
+    // Lane masks (MASKS: the exact builds' single-ray step, whose wave-uniform tests below read them): 64-bit masks,
+    // each the ballot of ONE compare -- that is the compare's own SGPR pair -- combined by scalar ops.  (The ballot
+    // of an and/or of predicates goes through a VGPR instead: v_cndmask 0,1 + v_cmp_ne, 2 VALU each, on every step.)
+    // bo_all: all lanes when the blackout test is on; m_bo: the lanes that leave by it, which no test below waits for.
+    constexpr bool MASKS = BRANCHY && !BH_FAST;
+    [[maybe_unused]] const uint64_t bo_all = bo_on ? ~0ull : 0ull;
     bool blackout;
+    [[maybe_unused]] uint64_t m_bo = 0ull;
     if constexpr (CO) {
         blackout = bo_on & not_out;  // `outside` is 1 from iteration 0 on (SF_CAM_OUT)
+        if constexpr (MASKS) m_bo = lane_mask(not_out) & bo_all;
+    } else if constexpr (MASKS) {
+        // rd.ro < 0 only matters for lanes inside r < 1; formed on every step all the same (behind a wave-uniform
+        // test the compiler speculates the product into the step anyway, and the test's own ballot costs 2 VALU)
+        const bool ingoing = dot(rd, ro) < 0.0f, was_out = in.outside != 0u;
+        blackout = bo_on & (((r2 < 1.0f) & ingoing) | (not_out & was_out));
+        m_bo = ((lane_mask(r2 < 1.0f) & lane_mask(ingoing)) | (lane_mask(not_out) & lane_mask(was_out))) & bo_all;
     } else {
+        // The pair schedule's block and the fast build keep the form their code was measured and, in fast math,
+        // contracted with: rd.ro < 0 behind a wave-uniform test.  (The pair kernel inlines the step once per ray of a
+        // lane; in fast math the two copies must contract alike, or a pixel's bytes depend on which of the two it is.)
         bool ingoing = false;
         if (__builtin_amdgcn_ballot_w64(bo_on & (r2 < 1.0f)) != 0ull) ingoing = dot(rd, ro) < 0.0f;
         blackout = bo_on & (((r2 < 1.0f) & ingoing) | (not_out & (in.outside != 0u)));
@@ -212,10 +235,11 @@ __device__ __forceinline__ bool step_bf(const MarchArgs& a, const Frame& f, cons
     // test's threshold by construction (proof at sdf_far_r2, bh_host.cpp): when every lane that stays is
     // there, the wave forms no SDF argument at all.  (r^2 = +inf is excluded: there dtm r is +inf while a
     // distance term may stay finite.)
-    if (BRANCHY && __builtin_amdgcn_ballot_w64(!(r2 >= a.far_r2 && r2 <= 0x1.fffffep127f) & !blackout) == 0ull) {
+    if (BRANCHY && ((lane_mask(!(r2 >= a.far_r2)) | lane_mask(!(r2 <= 0x1.fffffep127f))) & ~m_bo) == 0ull) {
         BH_DIAG_FAR_COUNT();
         if (blackout) {
             fate = (uint32_t)BH_FATE_BLACKOUT;
+            if constexpr (UNI) end->before_rk = true;
             return true;
         }
         dt = dtr;
@@ -233,17 +257,16 @@ __device__ __forceinline__ bool step_bf(const MarchArgs& a, const Frame& f, cons
     if constexpr (BRANCHY) {
         const v3 dc = sub(f.cps, ro);
         const float qps = dot(dc, dc);
-        // lanes that need the roots: slack < 0 or NaN, except those that leave by the blackout exit.  (The
-        // blackout select becomes a branch around the test.  Taking the lane mask straight from the compare,
-        // llvm.amdgcn.fcmp, and masking the blackout lanes as integers is 4 VALU fewer and measured 0.9 %
-        // slower: profiles/r04/ab_skip_forms/.)
+        // lanes that need the roots: slack < 0 or NaN, except those that leave by the blackout exit (masked as
+        // integers: m_bo).  (Round 4 measured this form 0.9 % slower, profiles/r04/ab_skip_forms/, before the kernel
+        // was issue-bound; DESIGN.md §10 round 24 has the measurement that replaced it.)
         const SdfSlack terms = sdf_term_slacks(a, scene_flags, dtr, rho2, yy, qm, qps);
-        const float slack = blackout ? __builtin_inff() : sdf_skip_slack(terms);
-        const bool fast = a.skip_sdf != 0u && __builtin_amdgcn_ballot_w64(!(slack >= 0.0f)) == 0ull;
+        const bool fast = a.skip_sdf != 0u && (lane_mask(!(sdf_skip_slack(terms) >= 0.0f)) & ~m_bo) == 0ull;
         if (fast) {
             BH_DIAG_SKIP_COUNT();
             if (blackout) {
                 fate = (uint32_t)BH_FATE_BLACKOUT;
+                if constexpr (UNI) end->before_rk = true;
                 return true;
             }
             dt = dtr;
@@ -252,10 +275,9 @@ __device__ __forceinline__ bool step_bf(const MarchArgs& a, const Frame& f, cons
             // per term: a root only where some lane that stays needs it (sdf_term_slacks); where the disc
             // and markers both clear, the photon sphere alone keeps the wave here (about 98 % of these
             // wave-steps clear it, and 80 % one of the other two: tools/skip_sim.py)
-            const bool stay = !blackout;
-            const bool nd = __builtin_amdgcn_ballot_w64(stay & !(terms.disc >= 0.0f)) != 0ull;
-            const bool nm = __builtin_amdgcn_ballot_w64(stay & !(terms.mark >= 0.0f)) != 0ull;
-            const bool np = __builtin_amdgcn_ballot_w64(stay & !(terms.ps >= 0.0f)) != 0ull;
+            const bool nd = (lane_mask(!(terms.disc >= 0.0f)) & ~m_bo) != 0ull;
+            const bool nm = (lane_mask(!(terms.mark >= 0.0f)) & ~m_bo) != 0ull;
+            const bool np = (lane_mask(!(terms.ps >= 0.0f)) & ~m_bo) != 0ull;
             float dv = __builtin_inff(), mv = __builtin_inff();
             if (nd) {
                 dv = X.disc_from(ro, a.rs, rho2);
@@ -268,6 +290,7 @@ __device__ __forceinline__ bool step_bf(const MarchArgs& a, const Frame& f, cons
             const float ds = sdf_of_terms(scene_flags, dv, mv);          // :285
             if (blackout | (ds < MIN_DIST)) {                            // :286-288
                 fate = blackout ? (uint32_t)BH_FATE_BLACKOUT : (uint32_t)BH_FATE_SURFACE;
+                if constexpr (UNI) end->before_rk = true;
                 return true;
             }
             float dps = __builtin_inff();
@@ -293,6 +316,7 @@ __device__ __forceinline__ bool step_bf(const MarchArgs& a, const Frame& f, cons
         if constexpr (BRANCHY) {
             if (blackout | surface) {
                 fate = blackout ? (uint32_t)BH_FATE_BLACKOUT : (uint32_t)BH_FATE_SURFACE;
+                if constexpr (UNI) end->before_rk = true;
                 return true;
             }
         }
@@ -345,15 +369,19 @@ __device__ __forceinline__ bool step_bf(const MarchArgs& a, const Frame& f, cons
     const v3 nro = add(ro, dro), nrd = add(rd, drd);                   // :315, :322
     const float ntr = travelled + dt;                                  // :324
     out.s = s;
-    out.outside = CO ? 1u : (not_out ? in.outside : 1u);               // only read when bo_on
+    if constexpr (!CO) out.outside = not_out ? in.outside : 1u;        // only read when bo_on
     const bool escape = ntr > a.max_dist;                              // :325-327
-    const bool capped = (UNI ? it : n_rk) + 1u >= a.max_iters;         // loop end (:266)
+    const bool capped = n_rk + 1u >= a.max_iters;                      // loop end (:266)
     if constexpr (BRANCHY) {
         out.ro = nro;
         out.rd = nrd;
         out.travelled = ntr;
-        out.n_rk = n_rk + 1u;
-        fate = escape ? (uint32_t)BH_FATE_ESCAPE : (uint32_t)BH_FATE_CAP;
+        if constexpr (UNI) {
+            *end = StepEnd{false, escape};
+        } else {
+            out.n_rk = n_rk + 1u;
+            fate = escape ? (uint32_t)BH_FATE_ESCAPE : (uint32_t)BH_FATE_CAP;
+        }
         return escape | capped;
     }
     const bool pre = blackout | surface;
@@ -565,19 +593,20 @@ __device__ __forceinline__ bool step_first(const RayState& in, RayState& out, co
 
 // One iteration for one ray from `in` into `out` (step_bf<true> contract: `out` is not written for
 // fates before the RK update), with the exact mode's guarded fast path and its rare IEEE re-run.
+// UNI: step_bf's contract for the ping-pong loop (*end).
 template <uint32_t SF = SF_DYN, bool UNI = false, bool TINY = false>
 __device__ __forceinline__ bool march_step_io(const MarchArgs& a, const Frame& f, const RayState& in, RayState& out,
-                                              uint32_t& fate, uint32_t it = 0u) {
+                                              uint32_t& fate, uint32_t it = 0u, StepEnd* end = nullptr) {
 #if BH_FAST
     FOps X;
-    return step_bf<true, FOps, SF, UNI>(a, f, in, out, X, fate, it);
+    return step_bf<true, FOps, SF, UNI>(a, f, in, out, X, fate, it, end);
 #else
     XOps<true> X;
 #ifdef BH_DIAG_SLOW
     if ((threadIdx.x & 63u) == (uint32_t)__builtin_ctzll(__builtin_amdgcn_ballot_w64(true)))
         atomicAdd(&g_diag_all_wave_steps, 1u);
 #endif
-    bool done = step_bf<true, XOps<true>, SF, UNI, TINY>(a, f, in, out, X, fate, it);
+    bool done = step_bf<true, XOps<true>, SF, UNI, TINY>(a, f, in, out, X, fate, it, end);
 #ifdef BH_DIAG_SLOW
     const uint64_t badm = __builtin_amdgcn_ballot_w64(X.bad);
     if (badm != 0ull && (threadIdx.x & 63u) == 0u) {
@@ -589,7 +618,7 @@ __device__ __forceinline__ bool march_step_io(const MarchArgs& a, const Frame& f
     // ballot here costs a v_cndmask + v_cmp per step to materialise the mask)
     if (__builtin_expect(X.bad, 0)) {
         XOps<false> Y;
-        done = step_bf<true, XOps<false>, SF, UNI>(a, f, in, out, Y, fate, it);
+        done = step_bf<true, XOps<false>, SF, UNI>(a, f, in, out, Y, fate, it, end);
     }
     return done;
 #endif
