@@ -113,6 +113,11 @@ __device__ __forceinline__ float div12(float x) { return __builtin_fmaf(x, R12_H
 // 0 < |n| < DIV_N_MIN; a running v_min3_u32 over keys needs one compare per step.  (A float
 // min of |n| would be one op cheaper but cannot tell 0 from tiny: measured 2x slower overall,
 // because every camera-A ray starts on two coordinate planes and its first step then re-runs.)
+// That holds where a step may be a ray's iteration 0: step_first, the tail's, the pair and the persistent steps keep
+// the key.  The loop behind the peeled first step checks k1's numerators as a float min with the other stages'
+// (XOps<true, true>): after iteration 0 a numerator is exactly zero only for a ray that lies in a coordinate plane
+// for good -- whose k2..k4 numerators are zero too, so it re-ran before -- or where a component cancels to zero in
+// flight (4 of the headline frame's 1e8 lane-steps); the step then re-runs in IEEE ops -- the same bytes.
 constexpr uint32_t KEY_MIN = (0x21800000u << 1) - 1u;  // key(2^-60)
 // The march's acceleration numerators s * p_i are held to the stricter 0 or >= 2^-40 (ACC_N_MIN): then
 // every acceleration component is 0 or >= 2^-100 (Q <= 2^60), which the fma form of the RK stage

@@ -74,6 +74,23 @@ __device__ __forceinline__ float sdf_of_terms(uint32_t flags, float disc, float 
     return (flags & BH_SCENE_DISC) ? fminf(disc, m) : m;
 }
 
+#if !BH_FAST
+// fminf(a, b) for operands that are never signalling NaNs -- results of arithmetic ops, or +inf: the one v_min_f32,
+// without the v_max_f32 x, x, x that fminf spends on quieting each operand it cannot trace to an op (a value merged
+// from two arms).  The same result for every such pair, a quiet NaN operand dropped as fminf drops it.
+// (-0.5 % on the headline alone, three times just below the rule; kept with the K1F loop)
+__device__ __forceinline__ float fmin_quiet(float a, float b) {
+    float m;
+    asm("v_min_f32 %0, %1, %2" : "=v"(m) : "v"(a), "v"(b));
+    return m;
+}
+// sdf_of_terms on such operands (the per-term arm of step_bf: each term a root's distance or +inf)
+__device__ __forceinline__ float sdf_of_terms_quiet(uint32_t flags, float disc, float m) {
+    if (!(flags & BH_SCENE_MARKERS)) return (flags & BH_SCENE_DISC) ? disc : __builtin_inff();
+    return (flags & BH_SCENE_DISC) ? fmin_quiet(disc, m) : m;
+}
+#endif
+
 #if BH_FAST
 struct FOps {
     bool bad = false;  // no guard in fast mode
@@ -113,15 +130,25 @@ struct FOps {
 // square roots with the cheap correctly rounded cores of bh_crmath.hpp and raises `bad` for any
 // operand outside their proven domain; CR = false is plain IEEE ops (hipcc's expansions).  Both
 // produce identical bits wherever `bad` stays false.
-template <bool CR>
+// K1F (with CR): the form of the loop behind the peeled first step (march_ray, PEEL), see below.
+template <bool CR, bool K1F = false>
 struct XOps {
     static constexpr bool kCR = CR;
+    static constexpr bool kK1F = CR && K1F;
     bool bad = false;
     // Numerator domain of the division cores: 0 or >= DIV_N_MIN in magnitude, held to the stricter
     // ACC_N_MIN for the acceleration numerators (rd_half's premise).  Zeros are legal (the
     // cores are exact for them) and occur in two places:
-    //  * k1's numerators s*ro: camera-A rays start on two coordinate planes.  Checked through
-    //    crm::key (zeros map high, tiny values low): one v_lshl_add per value + v_min3_u32;
+    //  * k1's numerators s*ro at a ray's iteration 0: camera-A rays start on two coordinate planes.
+    //    Checked through crm::key (zeros map high, tiny values low): one v_lshl_add per value +
+    //    v_min3_u32 + its compare.  K1F -- the loop that follows the peeled first step, whose steps
+    //    are iterations >= 1 unless the wave could not take the record -- drops the key: k1's
+    //    numerators start the float chain `amin` (kmin is unused) and a zero takes the IEEE path
+    //    like any other stage's, -3 VALU per step.  The float test fires wherever the key test fires
+    //    (0 < |n| < ACC_N_MIN) and on zeros besides, and the re-run is exact for any input, so
+    //    the bytes are the same.  What it costs: a ray with a component of ro and rd exactly zero --
+    //    in a coordinate plane for good: the centre column of an odd-width frame from camera A, a
+    //    ray map's row with d.y = 0 -- re-runs every step of that loop;
     //  * the x/6 numerators when dt == 0 exactly (a ray frozen on the photon-sphere marker): all RK
     //    sums are then +-0.
     // Everywhere else a zero numerator needs an exact cancellation, so those are checked as a float
@@ -139,9 +166,13 @@ struct XOps {
     // the marker and photon-sphere arguments and the k-point q's, range [2^-16, 2^24] (implies every
     // root's and Q's domain), 286 -> 280 VALU per step and the same re-run count
     // (tools/diag_slow.py), measured 3.5 % slower on the headline and 11 % on cap 1000 at one frame
-    // per launch (packed tail); a float pool the same; profiles/r03/ab_pool/.)
-    uint32_t kmin;  // k1 numerators (keys)
-    float amin;     // k2..k4 numerators
+    // per launch (packed tail); a float pool the same; profiles/r03/ab_pool/.  Round 25, issue-bound
+    // kernel: the three stage denominators Q2..Q4 alone as one v_min3_u32 / v_max3_u32 pool over their
+    // bit patterns, two unsigned compares -- exactly div_d_bad of each, 4 VALU for 6 -- measured
+    // 0.7 % slower with the test beside k4's v_rcp (+2 VGPRs) and 2.2 % slower with it at the block's
+    // end; profiles/r25/step_guards/ab.txt.  Each Q keeps its two compares beside its producer.)
+    uint32_t kmin;  // k1 numerators (keys; not K1F)
+    float amin;     // k2..k4 numerators (K1F: k1..k4)
     float amin6;    // x/6 numerators
     __device__ __forceinline__ static float absmin3(float m, float x, float y, float z) {
         return fminf(fminf(fminf(m, fabsf(x)), fabsf(y)), fabsf(z));
@@ -214,7 +245,7 @@ struct XOps {
     }
     // rd_derivative (:125-127): (s * p) / pow(dot(p,p), 2.5), pow(q, 2.5) := (q*q)*sqrt(q);
     // q and sqrt(q) passed in when already known (k1: q = r^2, sqrt(q) = r).
-    // K = 1..4: the RK stage (k1's numerators may be zeros, see above)
+    // K = 1..4: the RK stage (k1's numerators may be zeros unless K1F, see above)
     // (a v_rcp of Q seeds RN(1/Q), not the root's own v_rsq: see the top of the file)
     template <int K>
     __device__ __forceinline__ v3 accel_qs(v3 p, float s, float q, float sq) {
@@ -223,8 +254,8 @@ struct XOps {
         const float nx = s * p.x, ny = s * p.y, nz = s * p.z;
         if constexpr (CR) {
             bad |= crm::div_d_bad(Q);
-            if constexpr (K == 1) kmin = crm::kmin3(crm::key(nx), crm::key(ny), crm::key(nz));
-            else if constexpr (K == 2) amin = absmin3(nx, ny, nz);
+            if constexpr (K == 1 && !kK1F) kmin = crm::kmin3(crm::key(nx), crm::key(ny), crm::key(nz));
+            else if constexpr (K == (kK1F ? 1 : 2)) amin = absmin3(nx, ny, nz);
             else amin = absmin3(amin, nx, ny, nz);
             const crm::Rcp R = crm::rcp_refined(Q);
             return mk(crm::div_core(nx, R), crm::div_core(ny, R), crm::div_core(nz, R));

@@ -120,7 +120,9 @@ __device__ __forceinline__ uint32_t march_cycles(const MarchArgs& a, const Frame
 // starts at iteration it0 = st.n_rk, 0 or 1 (wave-uniform), and *prev is the other state of the ping-pong -- st itself
 // before step_first when it0 is 1 (n_rk 0: the roles the comment below describes), any copy of st when it is 0.  The
 // PRIO_ITERS iterations then end at PRIO_ITERS + it0, where the priority is raised and the cycle search begins: it reads
-// n_rk and is valid from any iteration.
+// n_rk and is valid from any iteration.  The PEEL loop's steps check k1's numerators as floats (march_step_io, K1F): a
+// wave with it0 = 0 runs its iteration 0 through them, and a lane whose ray starts on a coordinate plane then re-runs
+// that one step in IEEE ops.
 template <uint32_t SF, bool SHUT = false, bool PEEL = false>
 __device__ __forceinline__ void march_ray(const MarchArgs& a, const Frame& f, RayState& st, uint32_t& fate,
                                           uint32_t& steps, uint32_t lane, [[maybe_unused]] const RayState* prev = nullptr,
@@ -149,7 +151,7 @@ __device__ __forceinline__ void march_ray(const MarchArgs& a, const Frame& f, Ra
     auto iterate = [&](RayState& in, RayState& out, uint32_t i) {
         StepEnd e;
         uint32_t pf;
-        if (march_step_io<SF, true>(a, f, in, out, pf, i, &e)) {
+        if (march_step_io<SF, true, false, PEEL>(a, f, in, out, pf, i, &e)) {
             alive = false;
             if (e.before_rk) {
                 in.n_rk = i;

@@ -287,7 +287,8 @@ __device__ __forceinline__ bool step_bf(const MarchArgs& a, const Frame& f, cons
                 mv = X.mark_from(qm);
                 X.sq_arg(qm);
             }
-            const float ds = sdf_of_terms(scene_flags, dv, mv);          // :285
+            // (the mins of this arm: fmin_quiet -- dv, mv and dps are a root's distance or +inf, never signalling)
+            const float ds = sdf_of_terms_quiet(scene_flags, dv, mv);    // :285
             if (blackout | (ds < MIN_DIST)) {                            // :286-288
                 fate = blackout ? (uint32_t)BH_FATE_BLACKOUT : (uint32_t)BH_FATE_SURFACE;
                 if constexpr (UNI) end->before_rk = true;
@@ -298,8 +299,8 @@ __device__ __forceinline__ bool step_bf(const MarchArgs& a, const Frame& f, cons
                 dps = X.sqrt(qps) - 0.075f;
                 X.sq_arg(qps);
             }
-            const float dist = fminf(ds, dps);                           // :299
-            dt = fminf(dist * 0.9f, dtr);                                // :307-310
+            const float dist = fmin_quiet(ds, dps);                      // :299
+            dt = fmin_quiet(dist * 0.9f, dtr);                           // :307-310
             full = false;
         }
         // else the root-free step is off (the host's skip_sdf gate): every root, below
@@ -353,7 +354,7 @@ __device__ __forceinline__ bool step_bf(const MarchArgs& a, const Frame& f, cons
         if constexpr (Ops::kCR) {
             // Domain of the division cores: every numerator is 0 or >= 2^-60 in magnitude, and
             // |s| <= 2^30, which with Q <= 2^60 (|p| <= 2^12) bounds every |s*p_i| <= 2^42.
-            X.bad |= X.kmin < crm::KEY_ACC_MIN;
+            if constexpr (!Ops::kK1F) X.bad |= X.kmin < crm::KEY_ACC_MIN;  // K1F: k1's numerators are in amin
             X.bad |= !(X.amin >= crm::ACC_N_MIN);
             if constexpr (!UNF) X.bad |= (fabsf(dt) < 0x1p-25f) & (dt != 0.0f);  // rd_half's premise
             X.bad |= !(X.amin6 >= crm::DIV_N_MIN) & (dt != 0.0f);
@@ -593,20 +594,22 @@ __device__ __forceinline__ bool step_first(const RayState& in, RayState& out, co
 
 // One iteration for one ray from `in` into `out` (step_bf<true> contract: `out` is not written for
 // fates before the RK update), with the exact mode's guarded fast path and its rare IEEE re-run.
-// UNI: step_bf's contract for the ping-pong loop (*end).
-template <uint32_t SF = SF_DYN, bool UNI = false, bool TINY = false>
+// UNI: step_bf's contract for the ping-pong loop (*end).  K1F: the guarded pass checks k1's numerators on the float
+// chain (XOps), for the loop whose steps follow a peeled iteration 0.
+template <uint32_t SF = SF_DYN, bool UNI = false, bool TINY = false, bool K1F = false>
 __device__ __forceinline__ bool march_step_io(const MarchArgs& a, const Frame& f, const RayState& in, RayState& out,
                                               uint32_t& fate, uint32_t it = 0u, StepEnd* end = nullptr) {
 #if BH_FAST
     FOps X;
     return step_bf<true, FOps, SF, UNI>(a, f, in, out, X, fate, it, end);
 #else
-    XOps<true> X;
+    using GOps = XOps<true, K1F>;
+    GOps X;
 #ifdef BH_DIAG_SLOW
     if ((threadIdx.x & 63u) == (uint32_t)__builtin_ctzll(__builtin_amdgcn_ballot_w64(true)))
         atomicAdd(&g_diag_all_wave_steps, 1u);
 #endif
-    bool done = step_bf<true, XOps<true>, SF, UNI, TINY>(a, f, in, out, X, fate, it, end);
+    bool done = step_bf<true, GOps, SF, UNI, TINY>(a, f, in, out, X, fate, it, end);
 #ifdef BH_DIAG_SLOW
     const uint64_t badm = __builtin_amdgcn_ballot_w64(X.bad);
     if (badm != 0ull && (threadIdx.x & 63u) == 0u) {
