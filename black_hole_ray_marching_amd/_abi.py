@@ -84,6 +84,11 @@ class bh_shade_desc(C.Structure):
                 ("lens", C.c_void_p), ("sky", C.c_void_p), ("out_col", C.c_void_p), ("out_blackout", C.c_void_p)]
 
 
+class bh_disc_desc(C.Structure):
+    _fields_ = [("hits", C.c_void_p), ("disc", C.c_void_p), ("rs", C.c_float), ("scene_flags", C.c_uint32),
+                ("spin", C.c_float), ("gain", C.c_float)]
+
+
 class bh_ray_pose(C.Structure):
     _fields_ = [("pos", C.c_float * 3), ("r", C.c_float * 3), ("u", C.c_float * 3), ("f", C.c_float * 3)]
 
@@ -167,6 +172,17 @@ SIGNATURES = {
                                               C.POINTER(bh_render_desc), C.c_void_p, C.c_void_p, C.c_void_p,
                                               C.c_void_p]),
     "bh_ray_origins_apply_host": (C.c_int, [C.POINTER(bh_ray_pose), C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p]),
+    "bh_render_lens_hits": (C.c_int, [C.c_void_p, C.POINTER(bh_camera_uniform), C.POINTER(bh_uniforms),
+                                      C.POINTER(bh_render_desc), C.c_void_p, C.c_void_p, C.c_void_p]),
+    "bh_render_lens_rays_posed_hits": (C.c_int, [C.c_void_p, C.POINTER(bh_ray_pose), C.POINTER(bh_uniforms),
+                                                 C.POINTER(bh_render_desc), C.c_void_p, C.c_void_p, C.c_void_p,
+                                                 C.c_void_p]),
+    "bh_disc_create": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(C.c_void_p)]),
+    "bh_disc_destroy": (C.c_int, [C.c_void_p]),
+    "bh_shade_lens_disc": (C.c_int, [C.c_void_p, C.POINTER(bh_shade_desc), C.POINTER(bh_disc_desc), C.c_void_p]),
+    "bh_lens_shade_disc_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p,
+                                          C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint32, C.c_uint32, C.c_float,
+                                          C.c_uint32, C.c_float, C.c_float, C.c_void_p, C.c_void_p]),
     "bh_shard_tile_count": (C.c_int64, [C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32]),
     "bh_tiles_unpack": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32,
                                   C.c_uint64, C.c_uint32, C.c_void_p]),

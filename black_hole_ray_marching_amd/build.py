@@ -64,9 +64,14 @@ TU_FLAGS = {
     "bh_march_rays_pose_lat.hip": EXACT,
     "bh_march_rays_org.hip": EXACT_ISSUE_ORDER,
     "bh_march_rays_org_lat.hip": EXACT,
+    # the lens march with a hit map (bh_render_lens_hits, bh_render_lens_rays_posed_hits): the same two builds
+    "bh_march_hits.hip": EXACT_ISSUE_ORDER,
+    "bh_march_hits_lat.hip": EXACT,
     "bh_tiles.hip": [],
     # the lens shades and the sky chain: the march kernels' shading arithmetic, one rounding per op (bh_lens.hpp)
     "bh_lens.hip": EXACT,
+    # the disc shade (bh_shade_lens_disc): the same contract, in a unit of its own beside the shades it extends
+    "bh_disc.hip": EXACT,
     # post-RA scheduling off: fused bloom chain 0.556 -> 0.548 ms (A/B r01; pre-RA off too: 0.561)
     # no SLP vectorisation: packed-FP32 forms of the filter's adjacent channel ops cost more than the
     # scalar ops on gfx950 (a v_pk op issues slower than two scalar ones, plus the shuffles and hazard

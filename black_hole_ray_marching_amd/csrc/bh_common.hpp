@@ -183,6 +183,17 @@ struct LensMipArgs : LensShadeArgs {
     uint32_t level_off[16];
 };
 
+// One bh_shade_lens_disc launch (bh_disc.hip): the same, the lens's hit map (three floats per record) and the disc
+// with its scene and its turn (include/bh_render.h, bh_disc_desc).
+struct LensDiscArgs : LensShadeArgs {
+    const float* hits;
+    const uint32_t* disc;      // n_phi x n_r Rgba8UnormSrgb texels
+    uint32_t n_phi, n_r;
+    float rs;
+    uint32_t scene_flags;
+    float spin, gain;
+};
+
 constexpr uint32_t REFINE_HEADS = 8, REFINE_HEAD_STRIDE = 32, REFINE_HEAD0 = 32;  // 128-byte lines
 constexpr uint32_t REFINE_CTR_WORDS = REFINE_HEAD0 + REFINE_HEADS * REFINE_HEAD_STRIDE;
 

@@ -270,6 +270,10 @@ int bh_destroy(bh_ctx* c) {
         if (k->chain) (void)hipFree(k->chain);
         delete k;
     }
+    for (bh_disc* k : c->discs) {
+        (void)hipFree(k->texels);
+        delete k;
+    }
     delete c;
     return BH_OK;
 }
@@ -506,10 +510,11 @@ int bh_first_step_host(const bh_camera_uniform* cam, const bh_uniforms* U, uint3
 // address enters the key (its contents cannot: a map rewritten in place may meet a stale order, never other bytes),
 // and so does every pose of a posed launch (after a marker: a posed launch is never taken for an unposed one), and
 // an origin map's address beside the direction map's (after a marker of its own: a launch with origins is never
-// taken for one without).
+// taken for one without).  A hit map's address enters the same way: the march's step counts do not depend on it, but
+// a launch that writes one is another launch of the frame, as one into another lens is not.
 static uint64_t frame_cost_key(const bh_camera_uniform* cam, const bh_uniforms* U, const bh_render_desc* d,
                                const float* ray_map = nullptr, const bh_ray_pose* poses = nullptr, uint32_t n_poses = 0u,
-                               const float* origin_map = nullptr) {
+                               const float* origin_map = nullptr, const float* hit_map = nullptr) {
     uint64_t h = 1469598103934665603ull;
     auto mix = [&](const void* p, size_t n) {
         const unsigned char* b = static_cast<const unsigned char*>(p);
@@ -534,6 +539,11 @@ static uint64_t frame_cost_key(const bh_camera_uniform* cam, const bh_uniforms* 
         const uint32_t marker = 0x4F524947u;  // "ORIG"
         mix(&marker, sizeof marker);
         mix(&origin_map, sizeof origin_map);
+    }
+    if (hit_map) {
+        const uint32_t marker = 0x48495453u;  // "HITS"
+        mix(&marker, sizeof marker);
+        mix(&hit_map, sizeof hit_map);
     }
     return h | 1u;  // never 0: 0 marks the fresh state's all-zero costs
 }
@@ -609,6 +619,7 @@ struct Launch {
     const float* ray_map = nullptr;    // bh_render_rays, bh_render_lens_rays: the device map the rays come from
     const bh_ray_pose* poses = nullptr;  // the posed ray-map forms: one pose per camera (a.n_frames of them), else null
     const float* origin_map = nullptr;   // bh_render_frames_rays_origins, bh_render_lens_rays_origins: the rays' origins
+    float* hit_map = nullptr;            // bh_render_lens_hits, bh_render_lens_rays_posed_hits: where surface rays ended
 };
 
 // Every argument check of a launch; no HIP call.  Leaves the launch's desc and tile count in L.
@@ -748,7 +759,7 @@ static int learned_order(bh_ctx* c, Launch* L, const bh_camera_uniform* cam0, co
     // buffers behind them costs at most a stale order, never a disagreement.  BH_ORDER_ALWAYS (A/B):
     // build and write on every launch, as before round 5.
     static const bool always = std::getenv("BH_ORDER_ALWAYS") != nullptr;
-    const uint64_t key = frame_cost_key(cam0, U, d, L->ray_map, L->poses, a.n_frames, L->origin_map);
+    const uint64_t key = frame_cost_key(cam0, U, d, L->ray_map, L->poses, a.n_frames, L->origin_map, L->hit_map);
     const bool repeat = !always && os->order_key == os->cost_key && os->cost_key == key;
     if (!repeat) {
         int oe = bh_launch_build_order(os->tile_cost, a.n_tiles, a.order_block, a.order_centre, os->counters,
@@ -771,7 +782,10 @@ static int launch_march(bh_ctx* c, const Launch& L, bh_ctx::OrderState* os, hipS
     const uint32_t sched = d->schedule & 0xFFu;
     const bool issue = march_variant_issue_order(d, a.n_tiles, a.n_frames, c->cus);  // every camera's tiles
     int e;
-    if (L.origin_map)  // exact math, tile schedule, no shutter form (render_rays_posed with an origin map)
+    if (L.hit_map)  // exact math, tile schedule, one frame's lens (bh_render_lens_hits; posed: L.ray_map)
+        e = issue ? bh_launch_lens_hits_exact(a, L.ray_map, L.hit_map, s)
+                  : bh_launch_lens_hits_exact_lat(a, L.ray_map, L.hit_map, s);
+    else if (L.origin_map)  // exact math, tile schedule, no shutter form (render_rays_posed with an origin map)
         e = issue ? bh_launch_rays_org_exact(a, L.ray_map, L.origin_map, s)
                   : bh_launch_rays_org_exact_lat(a, L.ray_map, L.origin_map, s);
     else if (L.poses)  // exact math, tile schedule (render_rays_posed); the shutter form when shutter_log2 != 0
@@ -916,14 +930,15 @@ int bh_render_frames_shutter(bh_ctx* c, uint32_t n_frames, uint32_t n_sub, const
 }
 
 // ---- lens maps (include/bh_render.h; the shading of a record: bh_lens.hpp) ---------------------------------
-int bh_render_lens(bh_ctx* c, const bh_camera_uniform* cam, const bh_uniforms* U, const bh_render_desc* d,
-                   bh_lens_px* out_lens, void* stream) {
-    if (!c || !cam || !U || !d || !out_lens || (reinterpret_cast<uintptr_t>(out_lens) & 7u)) return bad_arg(__func__, __LINE__);
+// bh_render_lens (out_hits null) and bh_render_lens_hits
+static int render_lens(const char* fn, bh_ctx* c, const bh_camera_uniform* cam, const bh_uniforms* U,
+                       const bh_render_desc* d, bh_lens_px* out_lens, float* out_hits, void* stream) {
+    if (!c || !cam || !U || !d || !out_lens || (reinterpret_cast<uintptr_t>(out_lens) & 7u)) return bad_arg(fn, __LINE__);
     const char* why = d->math != BH_MATH_EXACT ? "exact math (BH_MATH_EXACT): fast math has no defined bits to promise"
                       : (d->out_col || d->out_blackout) ? "no out_col or out_blackout (it writes only the lens)"
                                                         : ss_needs(d, 1u);
     if (why) {
-        g_last_error = std::string("bh_render_lens: a lens render needs ") + why + ".";
+        g_last_error = std::string(fn) + ": a lens render needs " + why + ".";
         return BH_ERR_UNSUPPORTED;
     }
     // bh_render's launch of this frame -- the same geometry, order state and repeated-frame key -- with the
@@ -936,7 +951,20 @@ int bh_render_lens(bh_ctx* c, const bh_camera_uniform* cam, const bh_uniforms* U
     if (st != BH_OK) return st;
     fill_args(c, 1u, cam, U, &ld, 1u, &L);
     L.a.lens = 1u;
+    L.hit_map = out_hits;
     return march_in_order(c, &L, cam, U, stream);
+}
+
+int bh_render_lens(bh_ctx* c, const bh_camera_uniform* cam, const bh_uniforms* U, const bh_render_desc* d,
+                   bh_lens_px* out_lens, void* stream) {
+    return render_lens(__func__, c, cam, U, d, out_lens, nullptr, stream);
+}
+
+// ---- hit maps (include/bh_render.h): the lens march also stores where its surface rays ended ----------------
+int bh_render_lens_hits(bh_ctx* c, const bh_camera_uniform* cam, const bh_uniforms* U, const bh_render_desc* d,
+                        bh_lens_px* out_lens, float* out_hits, void* stream) {
+    if (!out_hits || (reinterpret_cast<uintptr_t>(out_hits) & 3u)) return bad_arg(__func__, __LINE__);
+    return render_lens(__func__, c, cam, U, d, out_lens, out_hits, stream);
 }
 
 // ---- ray maps (include/bh_render.h): the caller's direction per pixel, one origin per frame -----------------
@@ -1005,7 +1033,7 @@ int bh_render_lens_rays(bh_ctx* c, const float pos[3], const bh_uniforms* U, con
 static int render_rays_posed(const char* fn, bh_ctx* c, uint32_t n_frames, uint32_t n_sub, const bh_ray_pose* poses,
                              const bh_uniforms* U, const bh_render_desc* descs, const float* dirs, uint32_t ss,
                              bh_lens_px* out_lens, void* stream, bool with_origins = false,
-                             const float* origins = nullptr) {
+                             const float* origins = nullptr, float* out_hits = nullptr) {
     if (!c || !poses || !U || !descs || !dirs || (reinterpret_cast<uintptr_t>(dirs) & 3u)) return bad_arg(fn, __LINE__);
     if (with_origins && (!origins || (reinterpret_cast<uintptr_t>(origins) & 3u) || n_sub != 1u)) return bad_arg(fn, __LINE__);
     const uint32_t ln = bh::shutter::log2_n(n_sub);
@@ -1054,6 +1082,7 @@ static int render_rays_posed(const char* fn, bh_ctx* c, uint32_t n_frames, uint3
     L.ray_map = dirs;
     L.poses = poses;
     L.origin_map = with_origins ? origins : nullptr;
+    L.hit_map = out_hits;  // with out_lens, one frame, no origin map (bh_render_lens_rays_posed_hits)
     return march_in_order(c, &L, cams.data(), U, stream);
 }
 
@@ -1073,6 +1102,13 @@ int bh_render_lens_rays_posed(bh_ctx* c, const bh_ray_pose* pose, const bh_unifo
                               const float* dirs_dev, bh_lens_px* out_lens, void* stream) {
     if (!out_lens || (reinterpret_cast<uintptr_t>(out_lens) & 7u)) return bad_arg(__func__, __LINE__);
     return render_rays_posed(__func__, c, 1u, 1u, pose, U, d, dirs_dev, 1u, out_lens, stream);
+}
+
+int bh_render_lens_rays_posed_hits(bh_ctx* c, const bh_ray_pose* pose, const bh_uniforms* U, const bh_render_desc* d,
+                                   const float* dirs_dev, bh_lens_px* out_lens, float* out_hits, void* stream) {
+    if (!out_lens || (reinterpret_cast<uintptr_t>(out_lens) & 7u)) return bad_arg(__func__, __LINE__);
+    if (!out_hits || (reinterpret_cast<uintptr_t>(out_hits) & 3u)) return bad_arg(__func__, __LINE__);
+    return render_rays_posed(__func__, c, 1u, 1u, pose, U, d, dirs_dev, 1u, out_lens, stream, false, nullptr, out_hits);
 }
 
 int bh_render_frames_rays_origins(bh_ctx* c, uint32_t n_frames, const bh_ray_pose* poses, const bh_uniforms* U,
@@ -1209,6 +1245,63 @@ int bh_shade_lens_mip(bh_ctx* c, const bh_shade_desc* d, void* stream) {
     if (dev.err != hipSuccess) return hip_fail(dev.err, "hipSetDevice");
     const int e = bh_launch_lens_shade_mip(a, d->ss, d->format, reinterpret_cast<hipStream_t>(stream));
     if (e != 0) return hip_fail((hipError_t)e, "filtered lens shade kernel launch");
+    return BH_OK;
+}
+
+// ---- disc shades (include/bh_render.h; the colour of a record: bh_lens.hpp, shade_disc) -------------------
+int bh_disc_create(bh_ctx* c, const uint8_t* rgba8, uint32_t n_phi, uint32_t n_r, bh_disc** out) {
+    if (!c || !rgba8 || !out || n_phi == 0 || n_r == 0 || n_phi > 32768u || n_r > 32768u) return bad_arg(__func__, __LINE__);
+    *out = nullptr;
+    DeviceScope dev(c->device);
+    if (dev.err != hipSuccess) return hip_fail(dev.err, "hipSetDevice");
+    bh_disc* k = new (std::nothrow) bh_disc();
+    if (!k) return BH_ERR_OUT_OF_MEMORY;
+    k->ctx = c;
+    k->n_phi = n_phi;
+    k->n_r = n_r;
+    const size_t bytes = (size_t)n_phi * n_r * 4u;
+    hipError_t e = hipMalloc(&k->texels, bytes);
+    if (e == hipSuccess) e = hipMemcpy(k->texels, rgba8, bytes, hipMemcpyHostToDevice);
+    if (e != hipSuccess) {
+        if (k->texels) (void)hipFree(k->texels);
+        delete k;
+        return alloc_fail(e, __func__);
+    }
+    c->discs.push_back(k);
+    *out = k;
+    return BH_OK;
+}
+
+int bh_disc_destroy(bh_disc* k) {
+    if (!k) return BH_OK;
+    bh_ctx* c = k->ctx;
+    DeviceScope dev(c->device);
+    c->discs.erase(std::remove(c->discs.begin(), c->discs.end(), k), c->discs.end());
+    (void)hipFree(k->texels);
+    delete k;
+    return BH_OK;
+}
+
+// bh_shade_lens's contract: validation and one kernel launch.
+int bh_shade_lens_disc(bh_ctx* c, const bh_shade_desc* d, const bh_disc_desc* dd, void* stream) {
+    if (!shade_desc_ok(c, d) || !dd) return bad_arg(__func__, __LINE__);
+    if (!dd->hits || (reinterpret_cast<uintptr_t>(dd->hits) & 3u) || !dd->disc || dd->disc->ctx != c) return bad_arg(__func__, __LINE__);
+    if (dd->scene_flags & ~BH_SCENE_DEFAULT) return bad_arg(__func__, __LINE__);
+    if (!std::isfinite(dd->spin) || !std::isfinite(dd->gain) || !(dd->gain >= 0.0f)) return bad_arg(__func__, __LINE__);
+    bh::LensDiscArgs a;
+    fill_shade_args(c, d, &a);
+    a.hits = dd->hits;
+    a.disc = dd->disc->texels;
+    a.n_phi = dd->disc->n_phi;
+    a.n_r = dd->disc->n_r;
+    a.rs = dd->rs;
+    a.scene_flags = dd->scene_flags;
+    a.spin = dd->spin;
+    a.gain = dd->gain;
+    DeviceScope dev(c->device);
+    if (dev.err != hipSuccess) return hip_fail(dev.err, "hipSetDevice");
+    const int e = bh_launch_lens_shade_disc(a, d->ss, d->format, reinterpret_cast<hipStream_t>(stream));
+    if (e != 0) return hip_fail((hipError_t)e, "disc shade kernel launch");
     return BH_OK;
 }
 

@@ -121,6 +121,8 @@ struct bh_ctx {
     uint32_t clk_mask = 0;
     // the skies of bh_sky_create that are still alive (bh_destroy frees what is left)
     std::vector<bh_sky*> skies;
+    // ... and the discs of bh_disc_create
+    std::vector<bh_disc*> discs;
 };
 
 // A sky beside the context's own (include/bh_render.h, bh_sky_create): immutable device texels.
@@ -131,6 +133,13 @@ struct bh_sky {
     // bh_sky_create_mips: the levels >= 1 (csrc/bh_lens.hpp, mip_offsets), n_levels != 0; both unset otherwise
     void* chain = nullptr;
     uint32_t n_levels = 0;
+};
+
+// A disc texture (include/bh_render.h, bh_disc_create): immutable device texels, n_phi around and n_r outwards.
+struct bh_disc {
+    bh_ctx* ctx = nullptr;
+    uint32_t* texels = nullptr;
+    uint32_t n_phi = 0, n_r = 0;
 };
 
 // A weighted tile partition (include/bh_render.h, bh_partition_create).
@@ -212,6 +221,9 @@ BH_INTERNAL int bh_launch_rays_org_exact(const bh::MarchArgs& a, const float* di
 BH_INTERNAL int bh_launch_rays_org_exact_lat(const bh::MarchArgs& a, const float* dirs, const float* orgs, hipStream_t s);
 BH_INTERNAL int bh_launch_rays_pose_exact_lat(const bh::MarchArgs& a, const float* dirs, uint32_t shutter_log2,
                 hipStream_t s);
+// the lens march with a hit map (bh_march_hits.hip): one frame; dirs null: the pinhole form, else the posed ray-map form
+BH_INTERNAL int bh_launch_lens_hits_exact(const bh::MarchArgs& a, const float* dirs, float* hits, hipStream_t s);
+BH_INTERNAL int bh_launch_lens_hits_exact_lat(const bh::MarchArgs& a, const float* dirs, float* hits, hipStream_t s);
 // the shutter render's march: 2^ln cameras per output frame, a.n_frames cameras in all (ln in 1..4)
 BH_INTERNAL int bh_launch_shutter_exact(const bh::MarchArgs& a, uint32_t ln, hipStream_t s);
 BH_INTERNAL int bh_launch_shutter_exact_lat(const bh::MarchArgs& a, uint32_t ln, hipStream_t s);
@@ -226,6 +238,8 @@ BH_INTERNAL int bh_launch_refine_detect(const bh::MarchArgs& a, const bh::Refine
 BH_INTERNAL int bh_launch_lens_shade(const bh::LensShadeArgs& a, uint32_t ss, uint32_t format, hipStream_t s);
 // the filtered lens shade and the chain it reads (bh_lens.hip): ss in {1, 2, 4}; the chain's kernels on `s`
 BH_INTERNAL int bh_launch_lens_shade_mip(const bh::LensMipArgs& a, uint32_t ss, uint32_t format, hipStream_t s);
+// the disc shade (bh_disc.hip): ss in {1, 2, 4, 8}
+BH_INTERNAL int bh_launch_lens_shade_disc(const bh::LensDiscArgs& a, uint32_t ss, uint32_t format, hipStream_t s);
 BH_INTERNAL int bh_launch_sky_mips(const uint32_t* sky, uint32_t w0, uint32_t h0, const float* srgb_lut, void* chain,
                 hipStream_t s);
 BH_INTERNAL int bh_march_blocks_per_cu_exact(void);

@@ -10,6 +10,9 @@
 #include <string.h>
 
 #include "../../include/bh_render.h"
+#if defined(__HIPCC__)
+#include "bh_crmath.hpp"  // the disc shade's angle on the device (crm::atan2_core)
+#endif
 
 // BH_LENS_FI: the cursor form of the resolve tree, its cursors and the pixel entry points, inlined whatever their
 // size -- left to the inliner, the filtered shade's K = 4 tree becomes a called function of 87 KB.
@@ -384,6 +387,105 @@ struct MipLens {
     template <int K, bool BO>
     BH_LENS_FI Acc pixel(uint32_t x, uint32_t y) const {
         return scaled<K, BO>(sum_y<K, K, BO>(Cursor{*this, width * K, height * K, x * K, y * K}));
+    }
+};
+
+// ---- the disc shade (include/bh_render.h, "Disc shades"): bh_shade_lens with the surface records looked up in a
+// disc texture at the place the hit map names.  bh_disc.hip runs these per output pixel, bh_lens_shade_disc_host
+// (bh_mirror.cpp) the same functions in a loop.  The header's rule, op for op: fp32, one rounding per op (both
+// units are built without contraction, the device one with correctly rounded fp32 division and square root).
+struct DiscView {
+    const uint32_t* texels;  // n_phi x n_r, r | g << 8 | b << 16 | a << 24 per texel
+    uint32_t n_phi, n_r;
+    float rs;
+    uint32_t scene_flags;
+    float spin, gain;
+};
+constexpr float DISC_TWO_PI = 6.28318530718f, DISC_ONE_PI = 3.14159265359f;  // the sky's u (:82-83)
+
+// RN_f32 of the f64 atan2(z, x): on the device the short f64 core with the library call for the lanes it cannot
+// decide (sky_uv's pair, bh_march_shade.hpp), on the host the library call.
+// (BH_DISC_ANGLE_F32, a measurement switch of variant builds only: the fp32 library atan2 in its place, not the
+// rule's bits -- tools/bench_disc.py takes the share of the f64 angle in the shade's time from such a build.)
+BH_LENS_HD float disc_angle(float z, float x) {
+#if defined(BH_DISC_ANGLE_F32)
+    return atan2f(z, x);
+#elif defined(__HIP_DEVICE_COMPILE__)
+    const crm::Atan2 at = crm::atan2_core(z, x);
+    float az = at.f;
+    if (__builtin_expect(at.near, 0)) az = (float)atan2((double)z, (double)x);
+    return az;
+#else
+    return (float)atan2((double)z, (double)x);
+#endif
+}
+
+// Steps 3 to 5 of the rule: the colour of a surface record whose ray ended at p = (x, y, z), disc enabled.
+BH_LENS_HD Rgb disc_colour(float x, float y, float z, const DiscView& d, const float* lut) {
+    const float rho = sqrtf(x * x + z * z);
+    const float ri = 3.0f * d.rs, ro = 6.0f * d.rs;
+    const float sd = fmaxf(fmaxf(rho - ro, -(rho - ri)), fabsf(y) - 0.02f);
+    if (!(sd < 0.001f)) return {1.0f, 1.0f, 1.0f};  // a marker
+    const float a = (rho - ri) / ri;
+    const float k = ri / rho;
+    const float w = k * sqrtf(k);
+    const float t0 = (disc_angle(z, x) + DISC_ONE_PI) / DISC_TWO_PI;
+    const float t1 = t0 - d.spin * w;
+    float t = t1 - floorf(t1);
+    if (!(t >= 0.0f)) t = 0.0f;  // a NaN t (a NaN hit component, or rs at which w is not finite)
+    // bilinear's arithmetic, the x axis wrapping: t in [0, 1], so floor(tx) in [-1, n_phi - 1]
+    const float tx = t * (float)d.n_phi - 0.5f;
+    float ty = a * (float)d.n_r - 0.5f;
+    ty = fminf(fmaxf(ty, -1.0f), (float)d.n_r);
+    const float fx0 = floorf(tx), fy0 = floorf(ty);
+    const float fa = tx - fx0, fb = ty - fy0;
+    int32_t x0 = (int32_t)fx0, y0 = (int32_t)fy0;
+    const int32_t np = (int32_t)d.n_phi, hm = (int32_t)d.n_r - 1;
+    x0 = x0 < 0 ? x0 + np : x0;
+    const int32_t x1 = x0 + 1 == np ? 0 : x0 + 1, y1 = clampi(y0 + 1, 0, hm);
+    y0 = clampi(y0, 0, hm);
+    const uint32_t w00 = d.texels[(uint32_t)y0 * d.n_phi + (uint32_t)x0], w10 = d.texels[(uint32_t)y0 * d.n_phi + (uint32_t)x1];
+    const uint32_t w01 = d.texels[(uint32_t)y1 * d.n_phi + (uint32_t)x0], w11 = d.texels[(uint32_t)y1 * d.n_phi + (uint32_t)x1];
+    const Rgb t00 = decode(lut, w00), t10 = decode(lut, w10), t01 = decode(lut, w01), t11 = decode(lut, w11);
+    const float ia = 1.0f - fa, ib = 1.0f - fb;
+    const Rgb top = {t00.r * ia + t10.r * fa, t00.g * ia + t10.g * fa, t00.b * ia + t10.b * fa};
+    const Rgb bot = {t01.r * ia + t11.r * fa, t01.g * ia + t11.g * fa, t01.b * ia + t11.b * fa};
+    const Rgb c = {top.r * ib + bot.r * fb, top.g * ib + bot.g * fb, top.b * ib + bot.b * fb};
+    return {c.r * d.gain, c.g * d.gain, c.b * d.gain};
+}
+// col of one record and its hit (three floats, read for a surface record of a scene with the disc only)
+BH_LENS_HD Rgb shade_disc(float u, float v, const float* hit, const DiscView& d, const SkyView& s, const float* lut) {
+    if (u != BH_LENS_SURFACE) return shade(u, v, s, lut);
+    if (!(d.scene_flags & BH_SCENE_DISC)) return {1.0f, 1.0f, 1.0f};
+    return disc_colour(hit[0], hit[1], hit[2], d, lut);
+}
+
+// The disc shade's lens: the plain shade's records, each beside its 12 bytes of the hit map, through the cursor
+// form of the tree.
+struct DiscLens {
+    const bh_lens_px* lens;
+    const float* hits;
+    uint32_t width;
+    SkyView s;
+    DiscView d;
+    const float* lut;
+    struct Cursor {
+        const DiscLens& f;
+        size_t vw, at;  // the virtual frame's width and the record's index
+        BH_LENS_FI Rgb col() const {
+            const bh_lens_px r = load_px(f.lens + at);
+            return shade_disc(r.u, r.v, f.hits + at * 3u, f.d, f.s, f.lut);
+        }
+        BH_LENS_FI Cursor right(int n) const { return {f, vw, at + (size_t)n}; }
+        BH_LENS_FI Cursor down(int n) const { return {f, vw, at + (size_t)n * vw}; }
+        // K = 8: four samples in flight at a time, as the plain tree holds them
+        template <int K>
+        static constexpr int barrier_at() { return K == 8 ? 4 : 0; }
+    };
+    template <int K, bool BO>
+    BH_LENS_FI Acc pixel(uint32_t x, uint32_t y) const {
+        const size_t vw = (size_t)width * K;
+        return scaled<K, BO>(sum_y<K, K, BO>(Cursor{*this, vw, (size_t)y * K * vw + (size_t)x * K}));
     }
 };
 

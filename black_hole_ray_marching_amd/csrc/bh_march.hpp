@@ -5,7 +5,8 @@
 //       same op sequence as the normative arithmetic of oracle/bh_oracle.c -> bit-exact parity
 //       (bh_march_exact_lat.hip and bh_march_refine_lat.hip build the same file again; bh_march_rays.hip and
 //       bh_march_rays_lat.hip hold the ray-map kernels alone, with the same two sets of flags, bh_march_rays_pose*.hip
-//       the posed ones and bh_march_rays_org*.hip those with an origin map);
+//       the posed ones, bh_march_rays_org*.hip those with an origin map and bh_march_hits*.hip the lens kernels with a
+//       hit map);
 //   bh_march_fast.hip   (BH_FAST 1; built -ffp-contract=fast, hardware rcp/rsq/sqrt):
 //       algebraically identical reformulation for throughput -> tolerance parity.
 //
@@ -143,6 +144,18 @@ __attribute__((visibility("hidden"))) inline int launch_rays_org(const MarchArgs
             constexpr uint32_t FMT = decltype(fmt)::value, SF = decltype(sf)::value;
             launch_tile_schedule(march_tile_rays_org_kernel<FMT, SF, decltype(ss)::value != 0u>, a, s, dirs, orgs);
         });
+}
+// The lens march with a hit map (bh_render_lens_hits: dirs null, the pinhole form; bh_render_lens_rays_posed_hits: the
+// posed ray-map form; tile schedule, one frame): one kernel per form and scene-flag fold.
+template <bool FOLD_NONE>
+__attribute__((visibility("hidden"))) inline int launch_lens_hits(const MarchArgs& a, const float* dirs, float* hits, hipStream_t s) {
+    if (!hits || a.lens == 0u || a.n_frames != 1u) return (int)hipErrorInvalidValue;
+    with_scene_fold<FOLD_NONE>(a.scene_flags, [&](auto sf) {
+        constexpr uint32_t SF = decltype(sf)::value;
+        if (dirs) launch_tile_schedule(march_tile_rays_pose_lens_hits_kernel<SF>, a, s, dirs, hits);
+        else launch_tile_schedule(march_tile_lens_hits_kernel<SF>, a, s, hits);
+    });
+    return (int)hipGetLastError();
 }
 #endif
 // The shutter render's march (bh_render_shutter, n = 2^ln cameras per output frame; tile schedule): the same folds.

@@ -215,6 +215,27 @@ int bh_lens_shade_host(const bh_lens_px* lens, uint32_t width, uint32_t height, 
     return BH_OK;
 }
 
+// bh_shade_lens_disc on the host: the disc shade's lens (bh_lens.hpp, DiscLens) through the same loop.
+int bh_lens_shade_disc_host(const bh_lens_px* lens, const float* hits, uint32_t width, uint32_t height, uint32_t ss,
+                            const uint8_t* sky, uint32_t sky_w, uint32_t sky_h, const uint8_t* disc, uint32_t n_phi,
+                            uint32_t n_r, float rs, uint32_t scene_flags, float spin, float gain, float* out_col,
+                            float* out_bo) {
+    if (!lens || !hits || !sky || !disc || !out_col || bh::ss::log2_k(ss) > 3u || !frame_shape_ok(width, height, ss)) return bad_arg(__func__, __LINE__);
+    if (sky_w == 0 || sky_h == 0 || sky_w > 32768u || sky_h > 32768u) return bad_arg(__func__, __LINE__);
+    if (n_phi == 0 || n_r == 0 || n_phi > 32768u || n_r > 32768u || (scene_flags & ~BH_SCENE_DEFAULT)) return bad_arg(__func__, __LINE__);
+    if (!std::isfinite(spin) || !std::isfinite(gain) || !(gain >= 0.0f)) return bad_arg(__func__, __LINE__);
+    HostSky k, dk;  // the disc's texels travel as a sky's do
+    if (!host_sky(sky, sky_w, sky_h, &k) || !host_sky(disc, n_phi, n_r, &dk)) return BH_ERR_OUT_OF_MEMORY;
+    const bh::lens::DiscLens l{lens, hits, width, k.view, {dk.texels.data(), n_phi, n_r, rs, scene_flags, spin, gain}, k.lut};
+    switch (ss) {
+        case 1u: lens_shade_rows<1>(l, width, height, out_col, out_bo); break;
+        case 2u: lens_shade_rows<2>(l, width, height, out_col, out_bo); break;
+        case 4u: lens_shade_rows<4>(l, width, height, out_col, out_bo); break;
+        default: lens_shade_rows<8>(l, width, height, out_col, out_bo); break;
+    }
+    return BH_OK;
+}
+
 // The chain kernels' per-texel functions (bh_lens.hpp, mip_down0 and mip_down) level after level: levels 1 ..
 // `upto` of the sky, back to back at mip_offsets' places.
 static void build_chain(const bh::lens::SkyView& s, const float* lut, uint32_t upto, const uint32_t* off, bh::lens::Half4* chain) {

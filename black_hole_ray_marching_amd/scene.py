@@ -279,6 +279,53 @@ def lens_shade_host(lens: np.ndarray, sky: np.ndarray, ss: int = 1, mip: bool = 
     return col, bo
 
 
+def lens_shade_disc_host(lens: np.ndarray, hits: np.ndarray, sky: np.ndarray, disc: np.ndarray, *, rs: float,
+                         scene_flags: int = BH_SCENE_DEFAULT, spin: float = 0.0, gain: float = 1.0, ss: int = 1):
+    """bh_lens_shade_disc_host (host only): what the disc shade kernel runs, on the CPU.  `lens`: (ss*H, ss*W, 2)
+    float32 records; `hits`: (ss*H, ss*W, 3) float32, the lens's hit map; `sky`: (h, w, 4) and `disc`: (n_r, n_phi, 4)
+    uint8 RGBA8 sRGB -> (col, blackout_col), fp32 (H, W, 4)."""
+    ln = np.ascontiguousarray(lens, np.float32)
+    ht = np.ascontiguousarray(hits, np.float32)
+    s = np.ascontiguousarray(sky, np.uint8)
+    dc = np.ascontiguousarray(disc, np.uint8)
+    k = _ss_arg(ss)
+    if ln.ndim != 3 or ln.shape[2] != 2 or ht.shape != ln.shape[:2] + (3,):
+        raise BhError(_abi.BH_ERR_INVALID_ARG, "lens_shade_disc_host: lens must be (ss*H, ss*W, 2), hits (ss*H, ss*W, 3)")
+    if s.ndim != 3 or s.shape[2] != 4 or dc.ndim != 3 or dc.shape[2] != 4:
+        raise BhError(_abi.BH_ERR_INVALID_ARG, "lens_shade_disc_host: sky must be (h, w, 4), disc (n_r, n_phi, 4)")
+    if k == 0 or ln.shape[0] % k or ln.shape[1] % k:
+        raise BhError(_abi.BH_ERR_INVALID_ARG, "lens_shade_disc_host: the lens sides must be multiples of ss")
+    h, w = ln.shape[0] // k, ln.shape[1] // k
+    col, bo = np.empty((h, w, 4), np.float32), np.empty((h, w, 4), np.float32)
+    check(load().bh_lens_shade_disc_host(ln.ctypes.data, ht.ctypes.data, w, h, k, s.ctypes.data, s.shape[1], s.shape[0],
+                                         dc.ctypes.data, dc.shape[1], dc.shape[0], rs, scene_flags, spin, gain,
+                                         col.ctypes.data, bo.ctypes.data), "bh_lens_shade_disc_host")
+    return col, bo
+
+
+def synthetic_disc(n_phi: int = 1024, n_r: int = 128, seed: int = 0x0D15C) -> np.ndarray:
+    """A deterministic disc texture for Disc(): (n_r, n_phi, 4) uint8 RGBA8 sRGB.  A radial temperature ramp --
+    white-hot and bright at the inner edge (row 0), dim red at the outer edge -- multiplied by seeded azimuthal
+    streaks: a sum of a few sinusoids around the disc whose phases drift with the radius, so the streaks shear as a
+    Keplerian flow would have left them.  The same (n_phi, n_r, seed) gives the same bytes."""
+    if not (1 <= n_phi <= 32768 and 1 <= n_r <= 32768):
+        raise ValueError("synthetic_disc: each side must be in 1..32768")
+    rng = np.random.Generator(np.random.PCG64(seed))
+    r = ((np.arange(n_r, dtype=np.float64) + 0.5) / n_r)[:, None]        # 0 inner .. 1 outer
+    phi = ((np.arange(n_phi, dtype=np.float64) + 0.5) / n_phi)[None, :]  # turns
+    heat = (1.0 + r) ** -3.0                                             # ~ r^-3 between 3 rs and 6 rs
+    streaks = np.zeros((n_r, n_phi))
+    for m in (3, 7, 13, 29, 61):
+        amp, phase, shear = rng.uniform(0.5, 1.0) / np.sqrt(m), rng.uniform(0.0, 1.0), rng.uniform(0.5, 2.0)
+        streaks += amp * np.cos(2.0 * np.pi * (m * phi + phase + shear * m * r))
+    lum = heat * (0.65 + 0.35 * streaks / np.abs(streaks).max())
+    rgb = np.stack([lum ** 0.45, lum ** 0.9 * (1.0 - 0.35 * r), lum ** 1.6 * (1.0 - 0.7 * r)], axis=2)
+    out = np.empty((n_r, n_phi, 4), np.uint8)
+    out[..., :3] = np.clip(np.rint(rgb * 255.0), 0, 255).astype(np.uint8)
+    out[..., 3] = 255
+    return out
+
+
 def sky_mips_host(sky: np.ndarray, level: int) -> np.ndarray:
     """bh_sky_mips_host (host only): level `level` >= 1 of the mip chain of `sky` ((h, w, 4) uint8 RGBA8 sRGB), by
     the chain kernels' own functions -> float16 (h_l, w_l, 4)."""
@@ -718,14 +765,17 @@ class Scene:
               "bh_render_frames_shutter_rays")
 
     def render_lens(self, lens, *, width: int | None = None, height: int | None = None, schedule: int = 0,
-                    stream=None, dirs=None, pos=None, pose=None, origins=None) -> None:
+                    stream=None, dirs=None, pos=None, pose=None, origins=None, hits=None) -> None:
         """bh_render_lens: march this scene's camera once into `lens`, a device buffer of height x width records
         (u, v) of 8 bytes (e.g. a float32 tensor (H, W, 2)) -- the view, without any sky.  Exact math, whatever
         the scene's math mode.  Shade it with shade(), as often and with as many skies as wanted.
         `dirs` (a ray map as render_rays takes it, (height, width, 3)): bh_render_lens_rays, the view of that map
         from `pos` (default: the scene camera's position); with `pose` (raymap.pose) instead of `pos`,
         bh_render_lens_rays_posed: the view of the camera-space map `dirs` turned by that pose; with `origins` (an
-        origin map of `dirs`' shape) beside the pose, bh_render_lens_rays_origins."""
+        origin map of `dirs`' shape) beside the pose, bh_render_lens_rays_origins.
+        `hits` (a float32 device tensor (height, width, 3)): bh_render_lens_hits, or with `dirs` bh_render_lens_rays_posed_hits
+        (`pose` defaults to the unit axes at the scene camera's position or at `pos`) -- the march also stores where
+        each surface ray ended, for shade(hits=, disc=).  Not with `origins`."""
         d = _abi.bh_render_desc()
         d.width, d.height = width or self.width, height or self.height
         d.max_iters, d.scene_flags = self.max_iters, self.scene_flags
@@ -733,6 +783,28 @@ class Scene:
         if lens is None:
             raise BhError(_abi.BH_ERR_INVALID_ARG, "render_lens: lens is required")
         _check_size(lens, d.width * d.height * 8, "lens", "render_lens")
+        if hits is not None:
+            if origins is not None:
+                raise BhError(_abi.BH_ERR_INVALID_ARG, "render_lens: a hit map is not built with an origin map")
+            _check_dirs(hits, d.height, d.width, "render_lens", "hits")
+            if dirs is None:
+                if pos is not None or pose is not None:
+                    raise BhError(_abi.BH_ERR_INVALID_ARG, "render_lens: pos and pose belong to a ray-map render (give dirs)")
+                check(self.lib.bh_render_lens_hits(self._ctx, C.byref(self.camera_uniform.c), C.byref(self.uniforms.to_c()),
+                                                   C.byref(d), _ptr(lens), _ptr(hits), _stream_handle(stream)),
+                      "bh_render_lens_hits")
+                return
+            if pose is not None and pos is not None:
+                raise BhError(_abi.BH_ERR_INVALID_ARG, "render_lens: give pos or pose, not both (a pose holds its position)")
+            _check_dirs(dirs, d.height, d.width, "render_lens")
+            if pose is None:  # a world-space map: the unit axes at the position
+                from . import raymap
+                pose = raymap.pose(self.camera_uniform.pos if pos is None else pos)
+            ps = _poses_arg([pose], 1, "render_lens")
+            check(self.lib.bh_render_lens_rays_posed_hits(self._ctx, ps, C.byref(self.uniforms.to_c()), C.byref(d),
+                                                          _ptr(dirs), _ptr(lens), _ptr(hits), _stream_handle(stream)),
+                  "bh_render_lens_rays_posed_hits")
+            return
         if origins is not None and pose is None:
             raise BhError(_abi.BH_ERR_INVALID_ARG, "render_lens: origins are in camera space and need a pose: give "
                                                    "pose=raymap.pose(pos) for the unit axes at pos")
@@ -763,12 +835,18 @@ class Scene:
                                       C.byref(d), _ptr(lens), _stream_handle(stream)), "bh_render_lens")
 
     def shade(self, lens, output, blackout_output=None, *, fmt: int = BH_OUT_RGBA32F, sky: "Sky | None" = None,
-              ss: int = 1, width: int | None = None, height: int | None = None, stream=None, mip: bool = False) -> None:
+              ss: int = 1, width: int | None = None, height: int | None = None, stream=None, mip: bool = False,
+              hits=None, disc: "Disc | None" = None, spin: float = 0.0, gain: float = 1.0, rs: float | None = None,
+              scene_flags: int | None = None) -> None:
         """bh_shade_lens: `lens` (render_lens of ss*width x ss*height) and a sky -> the bytes render() -- with
         ss > 1, render(ss=ss) -- writes for that view with that sky.  `sky`: a Sky of this scene, or None for the
         scene's own.  Asynchronous on `stream`; allocates nothing (capturable from the first call).
         mip=True: bh_shade_lens_mip, the sky filtered through its mip chain, the level taken from the lens; `sky`
-        must be a Sky(..., mips=True), ss 1, 2 or 4."""
+        must be a Sky(..., mips=True), ss 1, 2 or 4.
+        hits= and disc= (render_lens(hits=) of the same lens and a Disc of this scene): bh_shade_lens_disc, the surface
+        records that lie on the accretion disc coloured from the disc texture, turned by `spin` turns of its inner
+        edge (Keplerian: slower further out) and scaled by `gain`; `rs` and `scene_flags` default to the scene's, which
+        the lens was marched with.  Not with mip=True."""
         k = _ss_arg(ss)
         d = _abi.bh_shade_desc()
         d.width, d.height, d.ss, d.format = width or self.width, height or self.height, k, fmt
@@ -780,6 +858,20 @@ class Scene:
         _check_size(blackout_output, need, "blackout_output", "shade")
         d.lens, d.sky = _ptr(lens), None if sky is None else sky.handle
         d.out_col, d.out_blackout = _ptr(output), _ptr(blackout_output)
+        if hits is not None or disc is not None:
+            if hits is None or disc is None or mip:
+                raise BhError(_abi.BH_ERR_INVALID_ARG, "shade: a disc shade takes hits= and disc= together, without mip")
+            if disc.scene is not self or not disc.handle:
+                raise BhError(_abi.BH_ERR_INVALID_ARG, "shade: disc must be an open Disc of this scene")
+            _check_dirs(hits, d.height * k, d.width * k, "shade", "hits")
+            dd = _abi.bh_disc_desc()
+            dd.hits, dd.disc = _ptr(hits), disc.handle
+            dd.rs = self.uniforms.rs if rs is None else rs
+            dd.scene_flags = self.scene_flags if scene_flags is None else scene_flags
+            dd.spin, dd.gain = spin, gain
+            check(self.lib.bh_shade_lens_disc(self._ctx, C.byref(d), C.byref(dd), _stream_handle(stream)),
+                  "bh_shade_lens_disc")
+            return
         name = "bh_shade_lens_mip" if mip else "bh_shade_lens"
         check(getattr(self.lib, name)(self._ctx, C.byref(d), _stream_handle(stream)), name)
 
@@ -849,6 +941,37 @@ class Sky:
         closed, by hand or by Scene.close()."""
         if getattr(self, "handle", None):
             self.scene.lib.bh_sky_destroy(self.handle)
+            self.handle = None
+            if self in self.scene._skies:
+                self.scene._skies.remove(self)
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class Disc:
+    """bh_disc (include/bh_render.h): a disc texture for Scene.shade(hits=, disc=).  `array`: (n_r, n_phi, 4) uint8
+    RGBA8 sRGB texels (synthetic_disc, load_sky of an image): columns run around the disc, rows from its inner edge
+    to its outer edge.  It belongs to `scene`; Scene.close() closes it."""
+
+    def __init__(self, scene: "Scene", array: np.ndarray) -> None:
+        a = np.ascontiguousarray(array, dtype=np.uint8)
+        if a.ndim != 3 or a.shape[2] != 4:
+            raise ValueError("disc must be (n_r, n_phi, 4) uint8 RGBA (Rgba8UnormSrgb texels)")
+        self.scene, self.n_phi, self.n_r = scene, a.shape[1], a.shape[0]
+        h = C.c_void_p()
+        check(scene.lib.bh_disc_create(scene._ctx, a.ctypes.data, a.shape[1], a.shape[0], C.byref(h)), "bh_disc_create")
+        self.handle = h.value
+        scene._skies.append(self)  # closed with the scene, as its skies are
+
+    def close(self) -> None:
+        """Free the device texels (after the shades that read them have completed).  A no-op when already
+        closed, by hand or by Scene.close()."""
+        if getattr(self, "handle", None):
+            self.scene.lib.bh_disc_destroy(self.handle)
             self.handle = None
             if self in self.scene._skies:
                 self.scene._skies.remove(self)

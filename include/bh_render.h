@@ -634,6 +634,75 @@ int bh_render_lens_rays_origins(bh_ctx* ctx, const bh_ray_pose* pose, const bh_u
 int bh_ray_origins_apply_host(const bh_ray_pose* pose, const float* origins, uint32_t width, uint32_t height,
                               float* out_origins);
 
+/* Hit maps: the lens march also stores where its surface rays ended (not in the reference, whose surfaces are white).
+ * A hit map (normative) is a device array of height x width x 3 fp32 values, row-major, 12 bytes per pixel, 4-byte
+ * aligned -- a ray map's layout: hits[(y * width + x) * 3 + c].  For a ray of fate BH_FATE_SURFACE the three values
+ * are the ray's final ro: the position the loop's SDF test (:285-286) saw when it returned the surface colour, the
+ * state before that iteration's RK update, bit for bit.  For every other fate they are (+0, +0, +0).
+ * bh_render_lens_hits: bh_render_lens, which also writes out_hits -- the same lens bytes, the same refusals, order
+ * state, repeated-frame key (which the hit map's address enters: a launch that writes one is not taken for one that
+ * does not) and graph contract.  bh_render_lens_rays_posed_hits: bh_render_lens_rays_posed likewise; a pose of
+ * unit axes (r, u, f = x, y, z) covers a plain world-space ray map, as far as that call promises.  BH_ERR_INVALID_ARG for a NULL or misaligned
+ * out_hits; every bh_last_error() sentence starts with the function's name.  A refused call launches nothing and
+ * writes nothing.  Not built: hit maps with an origin map, with ss resolved in the march (a hit map is per ray, as a
+ * lens is: march the virtual frame and let the shade resolve), in fast math, in the tiled layouts, with shards or
+ * partitions.  Additive, like the disc shades below: BH_ABI_VERSION unchanged, callers probe for the symbols. */
+int bh_render_lens_hits(bh_ctx* ctx, const bh_camera_uniform* camera, const bh_uniforms* uniforms,
+                        const bh_render_desc* desc, bh_lens_px* out_lens, float* out_hits, void* hip_stream);
+int bh_render_lens_rays_posed_hits(bh_ctx* ctx, const bh_ray_pose* pose, const bh_uniforms* uniforms,
+                                   const bh_render_desc* desc, const float* dirs_dev, bh_lens_px* out_lens,
+                                   float* out_hits, void* hip_stream);
+
+/* Disc shades: bh_shade_lens with the surface records looked up in a disc texture (not in the reference).  The disc
+ * is an immutable object beside bh_sky: n_phi x n_r RGBA8-sRGB texels (n_phi * n_r * 4 bytes, each side 1..32768),
+ * x running around the disc and y from its inner edge to its outer edge, decoded through the 256-entry table the sky
+ * uses, uploaded before bh_disc_create returns.  A bh_disc belongs to its context and is destroyed as a bh_sky is;
+ * bh_destroy frees any that are left.
+ * The colour of one record (u, v) whose entry of the hit map is p = (x, y, z) (normative; fp32, one rounding per op,
+ * no FMA, except the angle):
+ *   1. u != BH_LENS_SURFACE: bh_shade_lens's colour of the record, bit for bit.
+ *   2. scene_flags without BH_SCENE_DISC: (1, 1, 1).
+ *   3. rho = sqrtf(x*x + z*z); ri = 3.0f * rs; ro = 6.0f * rs;
+ *      sd = fmaxf(fmaxf(rho - ro, -(rho - ri)), fabsf(y) - 0.02f)   -- sdf_accretion_disk (:103-105, :120) on p;
+ *      unless sd < 0.001f is true the colour is (1, 1, 1): a marker hit, and every hit with a non-finite component
+ *      that sd keeps.  fmaxf drops a NaN operand, as the march's own test does: a hit whose x or z is NaN and whose
+ *      |y| < 0.021 classifies as disc and goes on.
+ *   4. a = (rho - ri) / ri; k = ri / rho; w = k * sqrtf(k)   -- Keplerian: one turn of `spin` at the inner edge;
+ *      t0 = (RN_f32(atan2_f64(z, x)) + ONE_PI) / TWO_PI   -- the constants and the division of the lens record's u;
+ *      t1 = t0 - spin * w; t = t1 - floorf(t1); a t that is not >= 0 (NaN: a NaN component of p, or an rs at which
+ *      w or a is not finite, rs = 0 among them) is taken as 0.  So t is in [0, 1] (1 when t1 is a tiny negative).
+ *   5. the bilinear sample of :341's arithmetic (see bh_shade_lens) with the x axis wrapping:
+ *      tx = t * (float)n_phi - 0.5f; x0 = floorf(tx) modulo n_phi (floorf(tx) is in [-1, n_phi - 1]); x1 = (x0 + 1)
+ *      modulo n_phi; weight tx - floorf(tx).  ty = a * (float)n_r - 0.5f clamped to [-1, n_r] by fminf(fmaxf(ty,
+ *      -1.0f), (float)n_r) (a NaN becomes -1), y0 = floorf(ty), y1 = y0 + 1, both clamped to [0, n_r - 1]; weight
+ *      ty - floorf(ty).  top = t00 * (1 - fa) + t10 * fa, bot likewise, c = top * (1 - fb) + bot * fb per channel;
+ *      then each channel is multiplied once by gain.  The c * sqrt(c) step of the sky sample is not applied.
+ * blackout_col, ss and the encode are bh_shade_lens's: the blackout test per sample on this colour, the same tree.
+ * Identity: a 1 x 1 disc of (255, 255, 255) with gain 1 gives bh_shade_lens's bytes for any spin. */
+typedef struct bh_disc bh_disc;
+int bh_disc_create(bh_ctx* ctx, const uint8_t* rgba8_srgb, uint32_t n_phi, uint32_t n_r, bh_disc** out);
+int bh_disc_destroy(bh_disc* disc);
+typedef struct {
+    const float* hits;        /* the lens's hit map: (ss*height) x (ss*width) x 3 floats, device, 4-byte aligned */
+    const bh_disc* disc;
+    float rs;                 /* the uniforms' rs the lens was marched with */
+    uint32_t scene_flags;     /* the desc's scene flags the lens was marched with */
+    float spin;               /* turns of the inner edge, subtracted from the hit's angle; finite */
+    float gain;               /* finite, >= 0 */
+} bh_disc_desc;
+/* bh_shade_lens's contract (asynchronous, allocates nothing, keeps no state, capturable from its first call; ss in
+ * {1, 2, 4, 8}, the three formats, one or two targets).  BH_ERR_INVALID_ARG for everything bh_shade_lens refuses, and
+ * for a NULL disc desc, a NULL or misaligned hits, a NULL disc or one of another context, unknown scene flags, a
+ * non-finite spin, a gain that is negative or non-finite. */
+int bh_shade_lens_disc(bh_ctx* ctx, const bh_shade_desc* desc, const bh_disc_desc* disc_desc, void* hip_stream);
+/* Host only: bh_lens_shade_host for bh_shade_lens_disc -- hits: (ss*height) x (ss*width) x 3 floats; disc_rgba8:
+ * n_phi x n_r texels.  BH_ERR_INVALID_ARG as above. */
+int bh_lens_shade_disc_host(const bh_lens_px* lens, const float* hits, uint32_t width, uint32_t height, uint32_t ss,
+                            const uint8_t* sky_rgba8, uint32_t sky_w, uint32_t sky_h,
+                            const uint8_t* disc_rgba8, uint32_t n_phi, uint32_t n_r,
+                            float rs, uint32_t scene_flags, float spin, float gain,
+                            float* out_col_rgba, float* out_blackout_rgba_or_NULL);
+
 /* Bloom::render (src/bloom.rs:53-71): the reference's Kawase bloom + remix chain over the scene's two
  * targets, on BGRA8-sRGB images (bh_render with BH_OUT_BGRA8_SRGB): `col` (full_image_input),
  * `blackout` (blackout_input) -> `out` (the surface), all width x height (1..65536 each, as bh_render),

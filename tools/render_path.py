@@ -29,7 +29,13 @@ bh_render_frames_rays_origins).
 
     python tools/render_path.py --projection perspective:60 --ss 4 --aperture 0.05 --focus 20
 Depth of field: the ss x ss samples of a pixel start on a thin lens of radius A and meet at distance D
-(raymap.thin_lens).  The direction and origin maps are uploaded once per path."""
+(raymap.thin_lens).  The direction and origin maps are uploaded once per path.
+
+    python tools/render_path.py --disc synthetic --disc-spin 0.01 --script "" --frames 120
+A textured, turning accretion disc: each view is marched into a lens map and a hit map (bh_render_lens_hits) and
+shaded with the disc texture turned by TURNS_PER_FRAME * frame turns of its inner edge (bh_shade_lens_disc).  A frame
+whose camera did not move re-uses the last march: with a still camera (an empty --script) the path is one march and
+one shade per frame."""
 import argparse
 import dataclasses
 import json
@@ -77,7 +83,22 @@ p.add_argument("--projection", default=None, metavar="{pinhole,equirect,fisheye:
                     "per-frame map of the library's helper (bh_render_rays: the same bytes); DEG: the full field of "
                     "view of a fisheye (up to 360), the vertical one of a perspective lens (below 180); ods:IPD: "
                     "omnidirectional stereo, two frame sets (left, right) with the eyes IPD apart (world units)")
+p.add_argument("--disc", default=None, metavar="{synthetic,IMAGE}",
+               help="texture the accretion disc: bh.synthetic_disc(), or an image file whose columns run around the disc "
+                    "and whose rows run from its inner to its outer edge; every frame is a lens march with a hit map "
+                    "(only when the camera moved) and a disc shade")
+p.add_argument("--disc-spin", type=float, default=0.0, metavar="TURNS_PER_FRAME",
+               help="with --disc: turns of the disc's inner edge per frame (Keplerian: slower further out)")
+p.add_argument("--disc-gain", type=float, default=1.0, metavar="G", help="with --disc: the disc colour's multiplier")
 args = p.parse_args()
+if args.disc and (args.projection or args.shutter > 1 or args.adaptive is not None or args.sky_frames
+                  or args.sky_filter != "none" or args.aperture is not None):
+    sys.exit("render_path: --disc takes the camera's own rays and --ss only (no --projection, --shutter, --adaptive, "
+             "--sky-frames, --sky-filter or --aperture)")
+if not args.disc and (args.disc_spin != 0.0 or args.disc_gain != 1.0):
+    p.error("--disc-spin and --disc-gain go with --disc")
+if not (abs(args.disc_spin) < float("inf") and 0.0 <= args.disc_gain < float("inf")):
+    p.error("--disc-spin must be finite and --disc-gain finite and 0 or more")
 mip = args.sky_filter == "mip"
 proj, proj_deg = None, None
 if args.projection is not None:
@@ -225,6 +246,26 @@ if args.sky_frames:
         frame_sky.close()
         log.append({"frame": f, "sky": path.name, "pos": cam.pos, "dir": cam.dir, "moved": False})
     args.frames = len(images)
+marches = None
+if args.disc:  # a lens and a hit map per view, a disc shade per frame
+    disc = bh.Disc(scene, bh.synthetic_disc() if args.disc == "synthetic" else bh.load_sky(args.disc))
+    k, marches = args.ss, 0
+    lens = torch.empty((k * H, k * W, 2), dtype=torch.float32, device="cuda")
+    hits = torch.empty((k * H, k * W, 3), dtype=torch.float32, device="cuda")
+    for f in range(args.frames):
+        for key, a, b in keys:
+            ctrl.process_key(key, a <= f <= b)
+        cam, moved = ctrl.update_camera(cam, args.dt)
+        if f == 0 or moved:
+            scene.update(cam)
+            scene.render_lens(lens, width=k * W, height=k * H, hits=hits)
+            marches += 1
+        scene.shade(lens, col, bo, fmt=bh.BH_OUT_BGRA8_SRGB, ss=k, hits=hits, disc=disc, spin=args.disc_spin * f,
+                    gain=args.disc_gain)
+        scene.bloom(col, bo, surf)
+        if not args.no_png:
+            write_png(out_dir / f"frame_{f:04d}.png", surf.cpu().numpy())
+        log.append({"frame": f, "pos": cam.pos, "dir": cam.dir, "moved": moved})
 if mip and not args.sky_frames:  # the path's own sky with its chain, and the lens every frame marches into
     path_sky = bh.Sky(scene, sky, mips=True)
     path_lens = torch.empty((args.ss * H, args.ss * W, 2), dtype=torch.float32, device="cuda")
@@ -255,7 +296,7 @@ while posed and f0 < args.frames:
                 (out_dir / sub).mkdir(parents=True, exist_ok=True)
                 write_png(out_dir / sub / f"frame_{f0 + i:04d}.png", surf.cpu().numpy())
     f0 += nb
-for f in range(0 if args.sky_frames or posed else args.frames):
+for f in range(0 if args.sky_frames or posed or args.disc else args.frames):
     for k, a, b in keys:
         ctrl.process_key(k, a <= f <= b)
     cam, moved = ctrl.update_camera(cam, args.dt)
@@ -276,5 +317,5 @@ for f in range(0 if args.sky_frames or posed else args.frames):
 torch.cuda.synchronize()
 dt = time.perf_counter() - t0
 (out_dir / "path.json").write_text(json.dumps(log, indent=0))
-print(json.dumps({"frames": args.frames, "width": W, "height": H, "ss": args.ss, "adaptive": args.adaptive, "shutter": args.shutter, "sky_filter": args.sky_filter, "projection": args.projection, "map_uploads": map_uploads, "seconds": round(dt, 3),
+print(json.dumps({"frames": args.frames, "width": W, "height": H, "ss": args.ss, "adaptive": args.adaptive, "shutter": args.shutter, "sky_filter": args.sky_filter, "projection": args.projection, "map_uploads": map_uploads, "disc": args.disc, "marches": marches, "seconds": round(dt, 3),
                   "frames_per_s_incl_png": round(args.frames / dt, 2), "out": str(out_dir)}))
