@@ -9,16 +9,20 @@ A variant of the product for an A/B (other flags for some units, or another revi
 directory of its own, from the same list of units and flags:
     python -m black_hole_ray_marching_amd.build --out DIR [--extra bh_march_exact.hip="-mllvm -amdgpu-..."]... [--csrc DIR]
 writes DIR/libbh_render.so and its objects (DIR/*.o, what tools/kernel_text_cmp.py compares).
+
+The units are the rows of UNITS: a name, a source, flags and defines.  A unit's name is its object's stem
+(bh_march_exact_lat); --extra takes it with or without the source's suffix (bh_march_exact_lat.hip too).  Two rows may
+build one source: a march source's second build is a row with -DBH_LAT=1, not a file.
 """
 from __future__ import annotations
 
 import os
-import re
 import shutil
 import subprocess
 import sys
 from concurrent.futures import ThreadPoolExecutor
 from pathlib import Path
+from typing import NamedTuple
 
 PKG = Path(__file__).resolve().parent
 ROOT = PKG.parent
@@ -47,48 +51,79 @@ EXACT = ["-ffp-contract=off", "-fhip-fp32-correctly-rounded-divide-sqrt", "-fno-
 # LICM).
 EXACT_ISSUE_ORDER = EXACT + ["-mllvm", "-enable-misched=0", "-mllvm", "-enable-post-misched=0",
                              "-mllvm", "-disable-machine-licm"]
-# per-translation-unit floating-point contracts (DESIGN.md "Math modes")
-TU_FLAGS = {
-    "bh_march_exact.hip": EXACT_ISSUE_ORDER,
-    "bh_march_exact_lat.hip": EXACT,
+# The second build of a march source: the machine schedulers' build (EXACT alone), its namespace and its packed tail
+# step chosen in the source by BH_LAT (csrc/bh_march.hpp).
+LAT = ["-DBH_LAT=1"]
+
+
+class Unit(NamedTuple):
+    """One translation unit of the product: a compile command.  name: the object's stem, what --extra takes and what
+    tools/kernel_text_cmp.py and tools/kernel_resources.py report; src: its source in csrc/ (several rows may build
+    one source); flags: its floating-point contract and scheduling options (DESIGN.md "Math modes"); defines: the
+    -D options that pick a second build of the source."""
+    name: str
+    src: str
+    flags: list[str]
+    defines: list[str] = []
+
+
+UNITS = [
+    # the march (bh_render and its forms): the issue-order build, and the scheduled one over the same source
+    Unit("bh_march_exact", "bh_march_exact.hip", EXACT_ISSUE_ORDER),
+    Unit("bh_march_exact_lat", "bh_march_exact.hip", EXACT, LAT),
     # the fast (tolerance) kernels: no machine scheduling either (0.468 -> 0.440 ms headline, A/B r01)
-    "bh_march_fast.hip": ["-ffp-contract=fast", "-fno-hip-fp32-correctly-rounded-divide-sqrt",
-                          "-mllvm", "-enable-misched=0", "-mllvm", "-enable-post-misched=0"],
-    # the scheduled build of the adaptive render's work-list march alone, without machine LICM (see the file)
-    "bh_march_refine_lat.hip": EXACT + ["-mllvm", "-disable-machine-licm"],
+    Unit("bh_march_fast", "bh_march_fast.hip", ["-ffp-contract=fast", "-fno-hip-fp32-correctly-rounded-divide-sqrt",
+                                 "-mllvm", "-enable-misched=0", "-mllvm", "-enable-post-misched=0"]),
+    # the scheduled build of the adaptive render's work-list march alone, without machine LICM (see the source)
+    Unit("bh_march_refine_lat", "bh_march_exact.hip", EXACT + ["-mllvm", "-disable-machine-licm"],
+         LAT + ["-DBH_REFINE_ONLY=1"]),
     # the ray-map march (bh_render_rays), the posed one (bh_render_frames_rays, its shutter and lens forms) and the
-    # one with an origin map (bh_render_frames_rays_origins, its lens form): the two exact builds, in units of their own
-    "bh_march_rays.hip": EXACT_ISSUE_ORDER,
-    "bh_march_rays_lat.hip": EXACT,
-    "bh_march_rays_pose.hip": EXACT_ISSUE_ORDER,
-    "bh_march_rays_pose_lat.hip": EXACT,
-    "bh_march_rays_org.hip": EXACT_ISSUE_ORDER,
-    "bh_march_rays_org_lat.hip": EXACT,
+    # one with an origin map (bh_render_frames_rays_origins, its lens form): the two exact builds of a source each
+    Unit("bh_march_rays", "bh_march_rays.hip", EXACT_ISSUE_ORDER),
+    Unit("bh_march_rays_lat", "bh_march_rays.hip", EXACT, LAT),
+    Unit("bh_march_rays_pose", "bh_march_rays_pose.hip", EXACT_ISSUE_ORDER),
+    Unit("bh_march_rays_pose_lat", "bh_march_rays_pose.hip", EXACT, LAT),
+    Unit("bh_march_rays_org", "bh_march_rays_org.hip", EXACT_ISSUE_ORDER),
+    Unit("bh_march_rays_org_lat", "bh_march_rays_org.hip", EXACT, LAT),
     # the lens march with a hit map (bh_render_lens_hits, bh_render_lens_rays_posed_hits): the same two builds
-    "bh_march_hits.hip": EXACT_ISSUE_ORDER,
-    "bh_march_hits_lat.hip": EXACT,
-    "bh_tiles.hip": [],
+    Unit("bh_march_hits", "bh_march_hits.hip", EXACT_ISSUE_ORDER),
+    Unit("bh_march_hits_lat", "bh_march_hits.hip", EXACT, LAT),
+    Unit("bh_tiles", "bh_tiles.hip", []),
     # the lens shades and the sky chain: the march kernels' shading arithmetic, one rounding per op (bh_lens.hpp)
-    "bh_lens.hip": EXACT,
+    Unit("bh_lens", "bh_lens.hip", EXACT),
     # the disc shade (bh_shade_lens_disc): the same contract, in a unit of its own beside the shades it extends
-    "bh_disc.hip": EXACT,
+    Unit("bh_disc", "bh_disc.hip", EXACT),
     # post-RA scheduling off: fused bloom chain 0.556 -> 0.548 ms (A/B r01; pre-RA off too: 0.561)
     # no SLP vectorisation: packed-FP32 forms of the filter's adjacent channel ops cost more than the
     # scalar ops on gfx950 (a v_pk op issues slower than two scalar ones, plus the shuffles and hazard
     # nops around it) and hold more VGPRs (DESIGN.md §7b)
-    "bh_bloom.hip": ["-ffp-contract=off", "-fno-slp-vectorize", "-mllvm", "-enable-post-misched=0",
-                     "-mllvm", "-pragma-unroll-threshold=200000"],  # the quad pass's 8 taps x 9 read forms
-    "bh_selftest.hip": ["-ffp-contract=off", "-fhip-fp32-correctly-rounded-divide-sqrt"],
+    Unit("bh_bloom", "bh_bloom.hip", ["-ffp-contract=off", "-fno-slp-vectorize", "-mllvm", "-enable-post-misched=0",
+                            "-mllvm", "-pragma-unroll-threshold=200000"]),  # the quad pass's 8 taps x 9 read forms
+    Unit("bh_selftest", "bh_selftest.hip", ["-ffp-contract=off", "-fhip-fp32-correctly-rounded-divide-sqrt"]),
     # the host side of the ABI: arithmetic whose bits are tested (camera, frame constants, bloom plans, mirrors)
-    "bh_host.cpp": ["-ffp-contract=off", "-x", "hip"],
-    "bh_camera.cpp": ["-ffp-contract=off", "-x", "hip"],
-    "bh_bloom_host.cpp": ["-ffp-contract=off", "-x", "hip"],
+    Unit("bh_host", "bh_host.cpp", ["-ffp-contract=off", "-x", "hip"]),
+    Unit("bh_camera", "bh_camera.cpp", ["-ffp-contract=off", "-x", "hip"]),
+    Unit("bh_bloom_host", "bh_bloom_host.cpp", ["-ffp-contract=off", "-x", "hip"]),
     # plain C++ (no HIP): the bloom's plan builders replay the kernels' f32 arithmetic, IEEE and uncontracted
-    "bh_bloom_plan.cpp": ["-ffp-contract=off"],
-    "bh_tiles_host.cpp": ["-ffp-contract=off", "-x", "hip"],
-    "bh_mirror.cpp": ["-ffp-contract=off", "-x", "hip"],
-    "bh_present.cpp": ["-x", "hip"],
-}
+    Unit("bh_bloom_plan", "bh_bloom_plan.cpp", ["-ffp-contract=off"]),
+    Unit("bh_tiles_host", "bh_tiles_host.cpp", ["-ffp-contract=off", "-x", "hip"]),
+    Unit("bh_mirror", "bh_mirror.cpp", ["-ffp-contract=off", "-x", "hip"]),
+    Unit("bh_present", "bh_present.cpp", ["-x", "hip"]),
+]
+
+
+def unit_commands(obj_dir: Path, extra: dict[str, list[str]] | None = None, csrc: Path = CSRC) -> dict[str, list[str]]:
+    """Every unit's compile command, by name.  extra: per unit, flags after the row's own; a key is a unit's name,
+    with or without its source's suffix (bh_march_exact_lat, bh_march_exact_lat.hip).  ValueError for any other."""
+    names = {u.name for u in UNITS}
+    more: dict[str, list[str]] = {}
+    for key, flags in (extra or {}).items():
+        name = key.removesuffix(".hip").removesuffix(".cpp")
+        if name not in names:
+            raise ValueError(f"no such unit: {key!r} (units: {sorted(names)})")
+        more[name] = more.get(name, []) + flags
+    return {u.name: [HIPCC, *COMMON, *u.flags, *u.defines, *more.get(u.name, []), "-c", str(csrc / u.src), "-o",
+                     str(obj_dir / (u.name + ".o"))] for u in UNITS}
 
 
 def _run(cmd: list[str]) -> None:
@@ -107,23 +142,18 @@ def _stale(target: Path, deps: list[Path]) -> bool:
 def build_product(force: bool = False, out_dir: Path | None = None, extra: dict[str, list[str]] | None = None,
                   csrc: Path = CSRC) -> Path:
     """The product library.  out_dir: objects and library into that directory instead of the package (a variant
-    build); extra: per unit, flags after TU_FLAGS' own; csrc: another tree's sources (with ../../include beside it)."""
+    build); extra: per unit, flags after its row's own (unit_commands); csrc: another tree's sources (with
+    ../../include beside it)."""
     obj_dir = Path(out_dir) if out_dir else OBJ
     lib = obj_dir / LIB.name if out_dir else LIB
+    commands = unit_commands(obj_dir, extra, csrc)
     obj_dir.mkdir(parents=True, exist_ok=True)
-    extra = extra or {}
-    if set(extra) - set(TU_FLAGS):
-        raise ValueError(f"no such unit: {sorted(set(extra) - set(TU_FLAGS))} (units: {list(TU_FLAGS)})")
     headers = list(csrc.glob("*.hpp")) + [csrc.parent.parent / "include" / "bh_render.h"]
     objs, jobs = [], []
-    for src, flags in TU_FLAGS.items():
-        s = csrc / src
-        o = obj_dir / (s.stem + ".o")
-        deps = [s, *headers, Path(__file__)]
-        if s.stem.endswith("_lat"):  # a second build of another unit: the file it includes
-            deps += [csrc / inc for inc in re.findall(r'^#include "(\w+\.hip)"', s.read_text(), re.M)]
-        if force or _stale(o, deps):
-            jobs.append([HIPCC, *COMMON, *flags, *extra.get(src, []), "-c", str(s), "-o", str(o)])
+    for u in UNITS:
+        o = obj_dir / (u.name + ".o")
+        if force or _stale(o, [csrc / u.src, *headers, Path(__file__)]):
+            jobs.append(commands[u.name])
         objs.append(o)
     # the translation units compile independently: in parallel (BH_BUILD_JOBS, default min(cpus, 8))
     n = int(os.environ.get("BH_BUILD_JOBS", "0")) or min(os.cpu_count() or 1, 8)

@@ -141,6 +141,20 @@ static_assert(offsetof(MarchArgs, order) == 144 && offsetof(MarchArgs, sky) == 2
                   sizeof(FirstStep) == 12 && sizeof(MarchArgs) == 304 + BH_INLINE_FRAMES * (sizeof(FrameArgs) + sizeof(FirstStep)),
               "MarchArgs: kernel argument layout changed");
 
+// What a march launch carries besides MarchArgs, from the entry point (bh_host.cpp, Launch) to the unit's launcher
+// (bh_march.hpp, BH_MARCH_UNIT).  Host side only, never a kernel argument: a launcher hands its kernels the fields
+// of its family, each as an argument of its own.
+struct MarchLaunch {
+    const float* dirs = nullptr;   // the ray-map families: the device map the rays' directions come from
+    const float* orgs = nullptr;   // ... with an origin map: the rays' origins
+    float* hits = nullptr;         // the hit-map family: where surface rays ended
+    uint32_t shutter_log2 = 0;     // the shutter forms: log2 of the cameras per output frame (a.n_frames counts cameras)
+    // the plain family: a bh_schedule without its flags, and the persistent schedule's work counters and grid
+    uint32_t schedule = BH_SCHED_TILE;
+    uint32_t* counters = nullptr;
+    uint32_t grid = 0;
+};
+
 // The adaptive render's device-side work (bh_render_adaptive; bh_refine.hpp), a second kernel argument of
 // the two kernels that use it -- MarchArgs stays as the existing kernels were compiled against.  The detect
 // kernel (bh_tiles.hip) fills mask, list and counts from the plain frame in the frames' targets; the

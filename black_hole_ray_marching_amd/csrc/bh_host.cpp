@@ -370,8 +370,9 @@ static int stage_frame_table(bh_ctx* c, hipStream_t s, const bh::FrameArgs* fram
 // never evicted (its buffers are what the graph's kernels read and write); when every state is marked
 // the ctx keeps more than BH_ORDER_STATES instead of evicting one.  A capturing stream cannot create a
 // state (the allocation and the reset are not capturable work): BH_ERR_UNSUPPORTED.
-static int order_state(bh_ctx* c, const bh_render_desc* d, uint64_t nt, hipStream_t s, bool capturing,
-                       bh_ctx::OrderState** out, bool from_map = false) {
+static int order_state(bh_ctx* c, const bh_render_desc* d, const bh::MarchLaunch& m, uint64_t nt, hipStream_t s,
+                       bool capturing, bh_ctx::OrderState** out) {
+    const bool from_map = m.dirs != nullptr;  // a ray-map launch's tile costs are its own
     const uint64_t pser = d->partition ? d->partition->serial : 0u;
     for (auto& o : c->orders)
         if (o.matches(d, pser, nt, s, from_map)) {
@@ -504,6 +505,22 @@ int bh_first_step_host(const bh_camera_uniform* cam, const bh_uniforms* U, uint3
     return ok ? 1 : 0;
 }
 
+// ---- one march launch --------------------------------------------------------------------------------------
+// Every render entry point is the same few steps over this record: check_launch, fill_args, then either
+// learned_order and launch_march (bh_render_frames, bh_render_frames_ss, bh_render_lens) or launch_refine
+// (bh_render_frames_adaptive's second pass).  A supersampled render (ss = k > 1) is the launch of the virtual
+// frame k*width x k*height -- geometry, order state, repeat-frame key and all -- with log2 k and the output
+// width for the kernel's resolve epilogue.
+struct Launch {
+    bh_render_desc d;                  // the launch's desc: the virtual frame's (per-frame outputs stay in descs[i])
+    bh::MarchArgs a;                   // the kernel argument
+    std::vector<bh::FrameArgs> table;  // more than BH_INLINE_FRAMES frames: staged in the stream's device table
+    std::vector<bh::FirstStep> first_table;  // ... and their first-step records, staged behind the table
+    uint64_t n_tiles = 0;              // the shard's tiles
+    bh::MarchLaunch m;                 // what the unit's launcher takes beside `a`: the maps, the shutter, the schedule
+    const bh_ray_pose* poses = nullptr;  // the posed ray-map forms: one pose per camera (a.n_frames of them), else null
+};
+
 // What a frame's per-tile costs (the march's step counts) depend on: the camera, the shader uniforms and the
 // launch shape -- FNV-1a over those fields' bits (padding and the unused bg_brightness left out).  The
 // outputs, their format and the sky do not change a step count.  A ray-map launch's rays are its map's: the map's
@@ -512,9 +529,8 @@ int bh_first_step_host(const bh_camera_uniform* cam, const bh_uniforms* U, uint3
 // an origin map's address beside the direction map's (after a marker of its own: a launch with origins is never
 // taken for one without).  A hit map's address enters the same way: the march's step counts do not depend on it, but
 // a launch that writes one is another launch of the frame, as one into another lens is not.
-static uint64_t frame_cost_key(const bh_camera_uniform* cam, const bh_uniforms* U, const bh_render_desc* d,
-                               const float* ray_map = nullptr, const bh_ray_pose* poses = nullptr, uint32_t n_poses = 0u,
-                               const float* origin_map = nullptr, const float* hit_map = nullptr) {
+static uint64_t frame_cost_key(const bh_camera_uniform* cam, const bh_uniforms* U, const Launch& L) {
+    const bh_render_desc* d = &L.d;
     uint64_t h = 1469598103934665603ull;
     auto mix = [&](const void* p, size_t n) {
         const unsigned char* b = static_cast<const unsigned char*>(p);
@@ -530,20 +546,20 @@ static uint64_t frame_cost_key(const bh_camera_uniform* cam, const bh_uniforms* 
                            d->shard_count, d->schedule};
     mix(f, sizeof f);
     mix(&pser, sizeof pser);
-    if (ray_map) mix(&ray_map, sizeof ray_map);
-    if (poses) {
-        mix(&n_poses, sizeof n_poses);
-        mix(poses, sizeof(bh_ray_pose) * n_poses);
+    if (L.m.dirs) mix(&L.m.dirs, sizeof L.m.dirs);
+    if (L.poses) {  // a.n_frames of them
+        mix(&L.a.n_frames, sizeof L.a.n_frames);
+        mix(L.poses, sizeof(bh_ray_pose) * L.a.n_frames);
     }
-    if (origin_map) {
+    if (L.m.orgs) {
         const uint32_t marker = 0x4F524947u;  // "ORIG"
         mix(&marker, sizeof marker);
-        mix(&origin_map, sizeof origin_map);
+        mix(&L.m.orgs, sizeof L.m.orgs);
     }
-    if (hit_map) {
+    if (L.m.hits) {
         const uint32_t marker = 0x48495453u;  // "HITS"
         mix(&marker, sizeof marker);
-        mix(&hit_map, sizeof hit_map);
+        mix(&L.m.hits, sizeof L.m.hits);
     }
     return h | 1u;  // never 0: 0 marks the fresh state's all-zero costs
 }
@@ -602,25 +618,6 @@ static const char* ss_needs(const bh_render_desc* descs, uint32_t n_frames) {
     }
     return nullptr;
 }
-
-// ---- one march launch --------------------------------------------------------------------------------------
-// Every render entry point is the same few steps over this record: check_launch, fill_args, then either
-// learned_order and launch_march (bh_render_frames, bh_render_frames_ss, bh_render_lens) or launch_refine
-// (bh_render_frames_adaptive's second pass).  A supersampled render (ss = k > 1) is the launch of the virtual
-// frame k*width x k*height -- geometry, order state, repeat-frame key and all -- with log2 k and the output
-// width for the kernel's resolve epilogue.
-struct Launch {
-    bh_render_desc d;                  // the launch's desc: the virtual frame's (per-frame outputs stay in descs[i])
-    bh::MarchArgs a;                   // the kernel argument
-    std::vector<bh::FrameArgs> table;  // more than BH_INLINE_FRAMES frames: staged in the stream's device table
-    std::vector<bh::FirstStep> first_table;  // ... and their first-step records, staged behind the table
-    uint64_t n_tiles = 0;              // the shard's tiles
-    uint32_t shutter_log2 = 0;         // bh_render_shutter: log2 of the cameras per output frame (a.n_frames counts cameras)
-    const float* ray_map = nullptr;    // bh_render_rays, bh_render_lens_rays: the device map the rays come from
-    const bh_ray_pose* poses = nullptr;  // the posed ray-map forms: one pose per camera (a.n_frames of them), else null
-    const float* origin_map = nullptr;   // bh_render_frames_rays_origins, bh_render_lens_rays_origins: the rays' origins
-    float* hit_map = nullptr;            // bh_render_lens_hits, bh_render_lens_rays_posed_hits: where surface rays ended
-};
 
 // Every argument check of a launch; no HIP call.  Leaves the launch's desc and tile count in L.
 static int check_launch(const bh_ctx* c, uint32_t n_frames, const bh_camera_uniform* cams, const bh_uniforms* U,
@@ -703,6 +700,9 @@ static void fill_args(const bh_ctx* c, uint32_t n_frames, const bh_camera_unifor
     a.tx_magic = a.shard_count == 1u && a.n_tiles != 0u ? bh::div_magic(a.tiles_x, a.n_tiles - 1u) : 0u;
     a.clk = c->clk;
     a.clk_mask = c->clk_mask;
+    L->m.schedule = d->schedule & 0xFFu;
+    L->m.counters = c->counters;
+    L->m.grid = d->math != BH_MATH_EXACT ? c->grid_fast : c->grid_exact;
     if (n_frames > bh::BH_INLINE_FRAMES) L->table.resize(n_frames);
     bh::FrameArgs* fa = L->table.empty() ? a.frames : L->table.data();
     for (uint32_t i = 0; i < n_frames; ++i) frame_args(&cams[i], a.rs, &descs[i], &fa[i]);
@@ -739,7 +739,7 @@ static int learned_order(bh_ctx* c, Launch* L, const bh_camera_uniform* cam0, co
     if ((d->schedule & 0xFFu) != BH_SCHED_TILE || (d->schedule & BH_SCHED_FLAG_STATIC_ORDER)) return BH_OK;
     // temporal order of this (geometry, shard, stream): allocated at its first render only
     bh_ctx::OrderState* os = nullptr;
-    int st = order_state(c, d, L->n_tiles, s, stream_capturing(s), &os, L->ray_map != nullptr);
+    int st = order_state(c, d, L->m, L->n_tiles, s, stream_capturing(s), &os);
     if (st != BH_OK) return st;
     if (!os->valid) {
         // all costs 0 (one bucket, the uncounted last) and an empty histogram: consistent
@@ -759,7 +759,7 @@ static int learned_order(bh_ctx* c, Launch* L, const bh_camera_uniform* cam0, co
     // buffers behind them costs at most a stale order, never a disagreement.  BH_ORDER_ALWAYS (A/B):
     // build and write on every launch, as before round 5.
     static const bool always = std::getenv("BH_ORDER_ALWAYS") != nullptr;
-    const uint64_t key = frame_cost_key(cam0, U, d, L->ray_map, L->poses, a.n_frames, L->origin_map, L->hit_map);
+    const uint64_t key = frame_cost_key(cam0, U, *L);
     const bool repeat = !always && os->order_key == os->cost_key && os->cost_key == key;
     if (!repeat) {
         int oe = bh_launch_build_order(os->tile_cost, a.n_tiles, a.order_block, a.order_centre, os->counters,
@@ -775,32 +775,55 @@ static int learned_order(bh_ctx* c, Launch* L, const bh_camera_uniform* cam0, co
     return BH_OK;
 }
 
-// The march over every tile, by one of the three builds of its kernels.
+// ---- the march units: which serves a launch ------------------------------------------------------------------
+// The build of a unit (build.py): the exact kernels in issue order or scheduled for latency, or the fast kernels.
+enum MarchBuild : uint32_t { BUILD_ISSUE, BUILD_LAT, BUILD_FAST, N_BUILDS };
+// The family of a launch: which source's kernels march it (bh_march.hpp).
+enum MarchFamily : uint32_t { FAMILY_PLAIN, FAMILY_RAYS, FAMILY_POSE, FAMILY_ORG, FAMILY_HITS, N_FAMILIES };
+
+// [family][build]: the unit's launcher; null: no such unit (the entry points refuse fast math for ray maps and lenses).
+static constexpr MarchUnitFn* MARCH_UNITS[N_FAMILIES][N_BUILDS] = {
+    /* FAMILY_PLAIN */ {bh_launch_unit_exact, bh_launch_unit_exact_lat, bh_launch_unit_fast},
+    /* FAMILY_RAYS  */ {bh_launch_unit_exact_rays, bh_launch_unit_exact_rays_lat, nullptr},
+    /* FAMILY_POSE  */ {bh_launch_unit_exact_rays_pose, bh_launch_unit_exact_rays_pose_lat, nullptr},
+    /* FAMILY_ORG   */ {bh_launch_unit_exact_rays_org, bh_launch_unit_exact_rays_org_lat, nullptr},
+    /* FAMILY_HITS  */ {bh_launch_unit_exact_hits, bh_launch_unit_exact_hits_lat, nullptr},
+};
+// the work-list march: the plain family's units, the scheduled build's in a unit of its own (bh_march_exact.hip)
+static constexpr RefineUnitFn* REFINE_UNITS[N_BUILDS] = {bh_launch_refine_unit_exact, bh_launch_refine_unit_exact_lat_refine,
+                                                         bh_launch_refine_unit_fast};
+static constexpr bool exact_units_filled() {
+    for (uint32_t f = 0; f < N_FAMILIES; ++f)
+        if (!MARCH_UNITS[f][BUILD_ISSUE] || !MARCH_UNITS[f][BUILD_LAT]) return false;
+    return true;
+}
+static_assert(exact_units_filled(), "every family has both exact builds");
+
+// The most specific form first: a launch with a hit map may also be posed and have a ray map (the hit-map kernels take
+// both forms), one with an origin map is always posed, and a posed one always has a ray map -- so each test must come
+// before those of the fields it implies.
+static MarchFamily march_family(const Launch& L) {
+    return L.m.hits   ? FAMILY_HITS   // one frame's lens (bh_render_lens_hits; posed: L.m.dirs)
+           : L.m.orgs ? FAMILY_ORG    // no shutter form (render_rays_posed with an origin map)
+           : L.poses  ? FAMILY_POSE   // render_rays_posed; the shutter form when shutter_log2 != 0
+           : L.m.dirs ? FAMILY_RAYS   // render_rays
+                      : FAMILY_PLAIN; // the shutter march when shutter_log2 != 0, else by the schedule
+}
+static MarchBuild march_build(const bh_render_desc* d, bool issue) {
+    return d->math != BH_MATH_EXACT ? BUILD_FAST : issue ? BUILD_ISSUE : BUILD_LAT;
+}
+
+// The march over every tile, by the launch's family's unit of one of the three builds.
 static int launch_march(bh_ctx* c, const Launch& L, bh_ctx::OrderState* os, hipStream_t s) {
     const bh_render_desc* d = &L.d;
     const bh::MarchArgs& a = L.a;
-    const uint32_t sched = d->schedule & 0xFFu;
     const bool issue = march_variant_issue_order(d, a.n_tiles, a.n_frames, c->cus);  // every camera's tiles
-    int e;
-    if (L.hit_map)  // exact math, tile schedule, one frame's lens (bh_render_lens_hits; posed: L.ray_map)
-        e = issue ? bh_launch_lens_hits_exact(a, L.ray_map, L.hit_map, s)
-                  : bh_launch_lens_hits_exact_lat(a, L.ray_map, L.hit_map, s);
-    else if (L.origin_map)  // exact math, tile schedule, no shutter form (render_rays_posed with an origin map)
-        e = issue ? bh_launch_rays_org_exact(a, L.ray_map, L.origin_map, s)
-                  : bh_launch_rays_org_exact_lat(a, L.ray_map, L.origin_map, s);
-    else if (L.poses)  // exact math, tile schedule (render_rays_posed); the shutter form when shutter_log2 != 0
-        e = issue ? bh_launch_rays_pose_exact(a, L.ray_map, L.shutter_log2, s)
-                  : bh_launch_rays_pose_exact_lat(a, L.ray_map, L.shutter_log2, s);
-    else if (L.ray_map)  // exact math, tile schedule (render_rays)
-        e = issue ? bh_launch_rays_exact(a, L.ray_map, s) : bh_launch_rays_exact_lat(a, L.ray_map, s);
-    else if (const uint32_t ln = L.shutter_log2)
-        e = d->math != BH_MATH_EXACT ? bh_launch_shutter_fast(a, ln, s)
-            : issue                  ? bh_launch_shutter_exact(a, ln, s)
-                                     : bh_launch_shutter_exact_lat(a, ln, s);
-    else
-        e = d->math != BH_MATH_EXACT ? bh_launch_march_fast(a, sched, c->counters, c->grid_fast, s)
-            : issue                  ? bh_launch_march_exact(a, sched, c->counters, c->grid_exact, s)
-                                     : bh_launch_march_exact_lat(a, sched, c->counters, c->grid_exact, s);
+    MarchUnitFn* const unit = MARCH_UNITS[march_family(L)][march_build(d, issue)];
+    if (!unit) {
+        g_last_error = "march launch: this form has no kernels in the fast-math build";
+        return BH_ERR_INTERNAL;
+    }
+    const int e = unit(a, L.m, s);
     if (e != 0) {
         // the costs and their histogram are written together by the march kernel; without it they
         // may disagree, so the next frame of this state starts the temporal order afresh
@@ -831,9 +854,7 @@ static int launch_refine(bh_ctx* c, const Launch& L, const bh::RefineArgs& R, hi
     static const bool by_rule = std::getenv("BH_REFINE_VARIANT_RULE") != nullptr;
     const bool issue = by_rule ? march_variant_issue_order(d, a.n_tiles, a.n_frames, c->cus)
                                : (d->schedule & BH_SCHED_FLAG_ISSUE_ORDER) != 0u;
-    e = d->math != BH_MATH_EXACT ? bh_launch_refine_fast(a, R, waves, s)
-        : issue                  ? bh_launch_refine_exact(a, R, waves, s)
-                                 : bh_launch_refine_exact_lat(a, R, waves, s);
+    e = REFINE_UNITS[march_build(d, issue)](a, R, waves, s);
     if (e != 0) return hip_fail((hipError_t)e, "work-list march launch");
     return BH_OK;
 }
@@ -925,7 +946,7 @@ int bh_render_frames_shutter(bh_ctx* c, uint32_t n_frames, uint32_t n_sub, const
     if (st != BH_OK) return st;
     fill_args(c, n_cams, cams, U, per_cam.data(), ss, &L);
     L.a.ss_out_width = descs[0].width;  // the shutter kernels index the output through it at every ss
-    L.shutter_log2 = ln;
+    L.m.shutter_log2 = ln;
     return march_in_order(c, &L, cams, U, stream);
 }
 
@@ -951,7 +972,7 @@ static int render_lens(const char* fn, bh_ctx* c, const bh_camera_uniform* cam, 
     if (st != BH_OK) return st;
     fill_args(c, 1u, cam, U, &ld, 1u, &L);
     L.a.lens = 1u;
-    L.hit_map = out_hits;
+    L.m.hits = out_hits;
     return march_in_order(c, &L, cam, U, stream);
 }
 
@@ -985,7 +1006,7 @@ static bool rays_refused(const char* fn, const bh_render_desc* descs, const bh_r
 
 // bh_render_rays (out_lens null) and bh_render_lens_rays: the launch of bh_render / bh_render_ss / bh_render_lens of
 // this geometry from a camera that holds only the position -- the corner rays are not read by the ray-map kernels
-// -- with an order state and a repeated-frame key of its own (Launch::ray_map).
+// -- with an order state and a repeated-frame key of its own (the map in the launch's record).
 static int render_rays(const char* fn, bh_ctx* c, const float* pos, const bh_uniforms* U, const bh_render_desc* d,
                        const float* dirs, uint32_t ss, bh_lens_px* out_lens, void* stream) {
     if (!c || !pos || !U || !d || !dirs || (reinterpret_cast<uintptr_t>(dirs) & 3u)) return bad_arg(fn, __LINE__);
@@ -1007,7 +1028,7 @@ static int render_rays(const char* fn, bh_ctx* c, const float* pos, const bh_uni
     if (e != BH_OK) return e;
     fill_args(c, 1u, &cam, U, &ld, ss, &L);
     L.a.lens = out_lens ? 1u : 0u;
-    L.ray_map = dirs;
+    L.m.dirs = dirs;
     return march_in_order(c, &L, &cam, U, stream);
 }
 
@@ -1023,19 +1044,27 @@ int bh_render_lens_rays(bh_ctx* c, const float pos[3], const bh_uniforms* U, con
 }
 
 // ---- posed ray maps (include/bh_render.h, bh_ray_pose): one camera-space map, one pose per camera -----------
+// The maps of a posed launch, as its entry point has them.
+struct PosedMaps {
+    const float* dirs;               // the camera-space direction map
+    bool with_origins = false;       // the entry point takes an origin map: `origins` is required
+    const float* origins = nullptr;
+    float* out_hits = nullptr;       // with out_lens, one frame, no origin map (bh_render_lens_rays_posed_hits)
+};
 // bh_render_frames_rays (n_sub 1), bh_render_frames_shutter_rays (n_sub > 1) and bh_render_lens_rays_posed
 // (out_lens): render_rays' launch -- the ray-map order state, the map in the repeated-frame key -- of
 // n_frames * n_sub cameras as bh_render_frames(_ss) or bh_render_frames_shutter launches them: one FrameArgs entry
 // per camera, holding its position and, in c0..c2, its basis rows (march_slot's POSE form reads them there).
-// with_origins (bh_render_frames_rays_origins, bh_render_lens_rays_origins; n_sub 1): the same launch by the ORG
+// maps.with_origins (bh_render_frames_rays_origins, bh_render_lens_rays_origins; n_sub 1): the same launch by the ORG
 // kernels, which read each ray's origin from `origins` and form the photon-sphere centre per lane (FrameArgs::cps,
 // filled as ever, is not read by them).
 static int render_rays_posed(const char* fn, bh_ctx* c, uint32_t n_frames, uint32_t n_sub, const bh_ray_pose* poses,
-                             const bh_uniforms* U, const bh_render_desc* descs, const float* dirs, uint32_t ss,
-                             bh_lens_px* out_lens, void* stream, bool with_origins = false,
-                             const float* origins = nullptr, float* out_hits = nullptr) {
+                             const bh_uniforms* U, const bh_render_desc* descs, const PosedMaps& maps, uint32_t ss,
+                             bh_lens_px* out_lens, void* stream) {
+    const float* const dirs = maps.dirs;
+    const float* const origins = maps.origins;
     if (!c || !poses || !U || !descs || !dirs || (reinterpret_cast<uintptr_t>(dirs) & 3u)) return bad_arg(fn, __LINE__);
-    if (with_origins && (!origins || (reinterpret_cast<uintptr_t>(origins) & 3u) || n_sub != 1u)) return bad_arg(fn, __LINE__);
+    if (maps.with_origins && (!origins || (reinterpret_cast<uintptr_t>(origins) & 3u) || n_sub != 1u)) return bad_arg(fn, __LINE__);
     const uint32_t ln = bh::shutter::log2_n(n_sub);
     if (ln > bh::shutter::MAX_LOG2 || bh::ss::log2_k(ss) > 3u) return bad_arg(fn, __LINE__);
     if (n_frames == 0 || (uint64_t)n_frames * n_sub > BH_MAX_FRAMES) return bad_arg(fn, __LINE__);
@@ -1077,50 +1106,52 @@ static int render_rays_posed(const char* fn, bh_ctx* c, uint32_t n_frames, uint3
     L.a.lens = out_lens ? 1u : 0u;
     if (ln != 0u) {
         L.a.ss_out_width = descs[0].width;  // the shutter kernels index the output through it at every ss
-        L.shutter_log2 = ln;
+        L.m.shutter_log2 = ln;
     }
-    L.ray_map = dirs;
+    L.m.dirs = dirs;
+    L.m.orgs = maps.with_origins ? origins : nullptr;
+    L.m.hits = maps.out_hits;
     L.poses = poses;
-    L.origin_map = with_origins ? origins : nullptr;
-    L.hit_map = out_hits;  // with out_lens, one frame, no origin map (bh_render_lens_rays_posed_hits)
     return march_in_order(c, &L, cams.data(), U, stream);
 }
 
 int bh_render_frames_rays(bh_ctx* c, uint32_t n_frames, const bh_ray_pose* poses, const bh_uniforms* U,
                           const bh_render_desc* descs, const float* dirs_dev, uint32_t ss, void* stream) {
-    return render_rays_posed(__func__, c, n_frames, 1u, poses, U, descs, dirs_dev, ss, nullptr, stream);
+    return render_rays_posed(__func__, c, n_frames, 1u, poses, U, descs, {dirs_dev}, ss, nullptr, stream);
 }
 
 int bh_render_frames_shutter_rays(bh_ctx* c, uint32_t n_frames, uint32_t n_sub, const bh_ray_pose* poses,
                                   const bh_uniforms* U, const bh_render_desc* descs, const float* dirs_dev, uint32_t ss,
                                   void* stream) {
     if (n_sub == 0u) return bad_arg(__func__, __LINE__);
-    return render_rays_posed(__func__, c, n_frames, n_sub, poses, U, descs, dirs_dev, ss, nullptr, stream);
+    return render_rays_posed(__func__, c, n_frames, n_sub, poses, U, descs, {dirs_dev}, ss, nullptr, stream);
 }
 
 int bh_render_lens_rays_posed(bh_ctx* c, const bh_ray_pose* pose, const bh_uniforms* U, const bh_render_desc* d,
                               const float* dirs_dev, bh_lens_px* out_lens, void* stream) {
     if (!out_lens || (reinterpret_cast<uintptr_t>(out_lens) & 7u)) return bad_arg(__func__, __LINE__);
-    return render_rays_posed(__func__, c, 1u, 1u, pose, U, d, dirs_dev, 1u, out_lens, stream);
+    return render_rays_posed(__func__, c, 1u, 1u, pose, U, d, {dirs_dev}, 1u, out_lens, stream);
 }
 
 int bh_render_lens_rays_posed_hits(bh_ctx* c, const bh_ray_pose* pose, const bh_uniforms* U, const bh_render_desc* d,
                                    const float* dirs_dev, bh_lens_px* out_lens, float* out_hits, void* stream) {
     if (!out_lens || (reinterpret_cast<uintptr_t>(out_lens) & 7u)) return bad_arg(__func__, __LINE__);
     if (!out_hits || (reinterpret_cast<uintptr_t>(out_hits) & 3u)) return bad_arg(__func__, __LINE__);
-    return render_rays_posed(__func__, c, 1u, 1u, pose, U, d, dirs_dev, 1u, out_lens, stream, false, nullptr, out_hits);
+    return render_rays_posed(__func__, c, 1u, 1u, pose, U, d, {dirs_dev, false, nullptr, out_hits}, 1u, out_lens,
+                             stream);
 }
 
 int bh_render_frames_rays_origins(bh_ctx* c, uint32_t n_frames, const bh_ray_pose* poses, const bh_uniforms* U,
                                   const bh_render_desc* descs, const float* dirs_dev, const float* origins_dev,
                                   uint32_t ss, void* stream) {
-    return render_rays_posed(__func__, c, n_frames, 1u, poses, U, descs, dirs_dev, ss, nullptr, stream, true, origins_dev);
+    return render_rays_posed(__func__, c, n_frames, 1u, poses, U, descs, {dirs_dev, true, origins_dev}, ss, nullptr,
+                             stream);
 }
 
 int bh_render_lens_rays_origins(bh_ctx* c, const bh_ray_pose* pose, const bh_uniforms* U, const bh_render_desc* d,
                                 const float* dirs_dev, const float* origins_dev, bh_lens_px* out_lens, void* stream) {
     if (!out_lens || (reinterpret_cast<uintptr_t>(out_lens) & 7u)) return bad_arg(__func__, __LINE__);
-    return render_rays_posed(__func__, c, 1u, 1u, pose, U, d, dirs_dev, 1u, out_lens, stream, true, origins_dev);
+    return render_rays_posed(__func__, c, 1u, 1u, pose, U, d, {dirs_dev, true, origins_dev}, 1u, out_lens, stream);
 }
 
 // bh_sky_create and bh_sky_create_mips: the texels, and with `mips` the chain built from them (a synchronous call)
@@ -1368,7 +1399,8 @@ int bh_render_frames_adaptive(bh_ctx* c, uint32_t n_frames, const bh_camera_unif
         os->captured = true;
         os->last_use = ++c->order_clock;
     } else {
-        st = order_state(c, d, nt, s, false, &os);  // pass 1's own, or (BH_SCHED_FLAG_STATIC_ORDER) a new one
+        // pass 1's own (a plain launch's: no map), or (BH_SCHED_FLAG_STATIC_ORDER) a new one
+        st = order_state(c, d, bh::MarchLaunch{}, nt, s, false, &os);
         if (st != BH_OK) return st;
         if (os->refine_frames < n_frames && os->captured) {
             g_last_error = std::string(fn) + ": a captured graph holds this (geometry, stream)'s work list, which is "

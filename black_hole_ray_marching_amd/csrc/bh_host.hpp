@@ -204,35 +204,23 @@ BH_HIDDEN uint8_t srgb_encode_ref(float x);     // bh_host.cpp: the normative li
 BH_HIDDEN void free_bloom_scratch(bh_ctx::BloomScratch& b);  // bh_bloom_host.cpp
 
 // ---- launchers and host-side planners, defined in the .hip translation units ----------------------------
-BH_INTERNAL int bh_launch_march_exact(const bh::MarchArgs& a, uint32_t schedule, uint32_t* counters, uint32_t grid,
-                hipStream_t s);
-BH_INTERNAL int bh_launch_march_exact_lat(const bh::MarchArgs& a, uint32_t schedule, uint32_t* counters, uint32_t grid,
-                hipStream_t s);
-BH_INTERNAL int bh_launch_march_fast(const bh::MarchArgs& a, uint32_t schedule, uint32_t* counters, uint32_t grid,
-                hipStream_t s);
-// the ray-map march (bh_march_rays.hip): one frame, tile schedule; a.lens / a.ss_log2 pick the form
-BH_INTERNAL int bh_launch_rays_exact(const bh::MarchArgs& a, const float* dirs, hipStream_t s);
-BH_INTERNAL int bh_launch_rays_exact_lat(const bh::MarchArgs& a, const float* dirs, hipStream_t s);
-// the posed ray-map march (bh_march_rays_pose.hip): a.n_frames cameras over one map, their bases in c0..c2;
-// shutter_log2 != 0: the shutter form, 2^shutter_log2 cameras per output frame
-BH_INTERNAL int bh_launch_rays_pose_exact(const bh::MarchArgs& a, const float* dirs, uint32_t shutter_log2, hipStream_t s);
-// ... with an origin map (bh_march_rays_org.hip): the posed launch without a shutter form, the lane's origin from `orgs`
-BH_INTERNAL int bh_launch_rays_org_exact(const bh::MarchArgs& a, const float* dirs, const float* orgs, hipStream_t s);
-BH_INTERNAL int bh_launch_rays_org_exact_lat(const bh::MarchArgs& a, const float* dirs, const float* orgs, hipStream_t s);
-BH_INTERNAL int bh_launch_rays_pose_exact_lat(const bh::MarchArgs& a, const float* dirs, uint32_t shutter_log2,
-                hipStream_t s);
-// the lens march with a hit map (bh_march_hits.hip): one frame; dirs null: the pinhole form, else the posed ray-map form
-BH_INTERNAL int bh_launch_lens_hits_exact(const bh::MarchArgs& a, const float* dirs, float* hits, hipStream_t s);
-BH_INTERNAL int bh_launch_lens_hits_exact_lat(const bh::MarchArgs& a, const float* dirs, float* hits, hipStream_t s);
-// the shutter render's march: 2^ln cameras per output frame, a.n_frames cameras in all (ln in 1..4)
-BH_INTERNAL int bh_launch_shutter_exact(const bh::MarchArgs& a, uint32_t ln, hipStream_t s);
-BH_INTERNAL int bh_launch_shutter_exact_lat(const bh::MarchArgs& a, uint32_t ln, hipStream_t s);
-BH_INTERNAL int bh_launch_shutter_fast(const bh::MarchArgs& a, uint32_t ln, hipStream_t s);
-// the adaptive render's work-list march (a.ss_log2 in 1..3, `waves` pulling waves) and its detect kernel
-BH_INTERNAL int bh_launch_refine_exact(const bh::MarchArgs& a, const bh::RefineArgs& r, uint32_t waves, hipStream_t s);
-BH_INTERNAL int bh_launch_refine_exact_lat(const bh::MarchArgs& a, const bh::RefineArgs& r, uint32_t waves,
-                hipStream_t s);
-BH_INTERNAL int bh_launch_refine_fast(const bh::MarchArgs& a, const bh::RefineArgs& r, uint32_t waves, hipStream_t s);
+// The march units' launchers (bh_march.hpp, BH_MARCH_UNIT and BH_REFINE_UNIT), one per unit and named after its
+// namespace: bh_launch_unit_<ns> of every tile-march unit, all of the one type MarchUnitFn, and
+// bh_launch_refine_unit_<ns> of the three units that hold the adaptive render's work-list march (a.ss_log2 in 1..3,
+// `waves` pulling waves).  bh_host.cpp's tables say which unit serves which family and build.
+#define BH_MARCH_UNIT_NAMESPACES(X)                                                                  \
+    X(exact) X(exact_lat) X(fast) X(exact_rays) X(exact_rays_lat) X(exact_rays_pose) X(exact_rays_pose_lat) \
+    X(exact_rays_org) X(exact_rays_org_lat) X(exact_hits) X(exact_hits_lat)
+#define BH_REFINE_UNIT_NAMESPACES(X) X(exact) X(exact_lat_refine) X(fast)
+using MarchUnitFn = int(const bh::MarchArgs& a, const bh::MarchLaunch& m, hipStream_t s);
+using RefineUnitFn = int(const bh::MarchArgs& a, const bh::RefineArgs& r, uint32_t waves, hipStream_t s);
+#define BH_DECLARE_MARCH_UNIT(ns) BH_INTERNAL MarchUnitFn bh_launch_unit_##ns;
+#define BH_DECLARE_REFINE_UNIT(ns) BH_INTERNAL RefineUnitFn bh_launch_refine_unit_##ns;
+BH_MARCH_UNIT_NAMESPACES(BH_DECLARE_MARCH_UNIT)
+BH_REFINE_UNIT_NAMESPACES(BH_DECLARE_REFINE_UNIT)
+#undef BH_DECLARE_MARCH_UNIT
+#undef BH_DECLARE_REFINE_UNIT
+// the adaptive render's detect kernel (bh_tiles.hip)
 BH_INTERNAL int bh_launch_refine_detect(const bh::MarchArgs& a, const bh::RefineArgs& r, hipStream_t s);
 // the lens shade (bh_lens.hip): ss in {1, 2, 4, 8}, format a bh_out_format
 BH_INTERNAL int bh_launch_lens_shade(const bh::LensShadeArgs& a, uint32_t ss, uint32_t format, hipStream_t s);

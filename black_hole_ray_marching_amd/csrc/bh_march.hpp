@@ -1,14 +1,21 @@
 // bh_march.hpp — the geodesic ray-march kernel for gfx950 (CDNA4), one lane per pixel.
 //
-// Included by two source files, each after defining BH_FAST and BH_NS:
-//   bh_march_exact.hip  (BH_FAST 0; built -ffp-contract=off, correctly-rounded f32 div/sqrt):
-//       same op sequence as the normative arithmetic of oracle/bh_oracle.c -> bit-exact parity
-//       (bh_march_exact_lat.hip and bh_march_refine_lat.hip build the same file again; bh_march_rays.hip and
-//       bh_march_rays_lat.hip hold the ray-map kernels alone, with the same two sets of flags, bh_march_rays_pose*.hip
-//       the posed ones, bh_march_rays_org*.hip those with an origin map and bh_march_hits*.hip the lens kernels with a
-//       hit map);
-//   bh_march_fast.hip   (BH_FAST 1; built -ffp-contract=fast, hardware rcp/rsq/sqrt):
-//       algebraically identical reformulation for throughput -> tolerance parity.
+// Included by the march sources, each after defining BH_FAST and BH_NS.  A source is a family of kernels; a unit
+// is a row of build.py's UNITS over it (name, source, flags, defines), and a source has one row per build:
+//   bh_march_exact.hip      the plain family (tile / ss / lens / shutter kernels, the A/B schedules, the work list)
+//   bh_march_rays.hip       the ray-map kernels alone
+//   bh_march_rays_pose.hip  the posed ray-map kernels, their shutter form
+//   bh_march_rays_org.hip   those with an origin map
+//   bh_march_hits.hip       the lens kernels with a hit map
+//       BH_FAST 0; built -ffp-contract=off, correctly-rounded f32 div/sqrt: same op sequence as the normative
+//       arithmetic of oracle/bh_oracle.c -> bit-exact parity.  Two rows each: the issue-order build, and with
+//       -DBH_LAT=1 the scheduled (latency) build -- a namespace of its own, the packed tail step (BH_TAIL_PACKED,
+//       set below).  bh_march_exact.hip has a third, -DBH_LAT=1 -DBH_REFINE_ONLY=1: the work-list march alone.
+//   bh_march_fast.hip       the plain family again (one row)
+//       BH_FAST 1; built -ffp-contract=fast, hardware rcp/rsq/sqrt: algebraically identical reformulation for
+//       throughput -> tolerance parity.
+// A unit exports one hidden launcher, named after its namespace (BH_MARCH_UNIT at the end of this file); the host
+// finds it in its table of [family][build] (bh_host.cpp, MARCH_UNITS).
 //
 // Semantics follow src/black_hole_maybe.wgsl (reference): fs_main :360-370, get_col :259-345,
 // get_delta_photon_rk4 :134-151, rd_derivative :125-127, sdf* :91-123.  Layout: each wave64 owns
@@ -34,6 +41,9 @@
 #ifndef BH_FAST
 #error "define BH_FAST to 0 or 1"
 #endif
+#if defined(BH_LAT) && !defined(BH_TAIL_PACKED)
+#define BH_TAIL_PACKED 1  // the scheduled builds' tail loop runs the packed-FP32 step (bh_march_step.hpp, step_tail)
+#endif
 // (rd_derivative's reciprocal from the root's own v_rsq, crm::rcp_from_rsq, instead of a v_rcp of Q: four
 // fewer transcendentals per RK step, but NOT exact -- 60 (numerator, Q) pairs, at Q significands next to
 // 2 (e.g. n = 1, Q = 0x2cffffff), round the other way (selftest op 13) -- so the march keeps rcp_refined.)
@@ -44,9 +54,10 @@
 namespace bh {
 namespace BH_NS {
 
-// ---- one launcher for every build of these kernels (bh_march_exact.hip, bh_march_fast.hip) -----------------
+// ---- one launcher per family, for every build of its kernels -------------------------------------------------
 // A launcher is a template, so a unit holds the kernels of the launchers it calls and no others; hidden, like
-// the entry points that call them.
+// the entry points that call them.  Each takes the launch's record (bh_common.hpp, MarchLaunch) and reads its
+// family's fields of it.
 // f(SF) with the launch's scene flags as a compile-time constant where the build folds them: the reference's
 // scene always (Const and with_format: bh_common.hpp); no surfaces (BASELINE config 1: the sdf folds to +inf) with FOLD_NONE, which the exact builds
 // set and the fast build does not; otherwise SF_DYN, the kernels that read the flags.
@@ -78,11 +89,11 @@ __attribute__((visibility("hidden"))) inline int with_tile_form(const MarchArgs&
         return (int)hipGetLastError();
     });
 }
-// The march over every tile under `schedule` (a bh_schedule without its flags); counters, grid: the persistent
+// The march over every tile under m.schedule (a bh_schedule without its flags); m.counters, m.grid: the persistent
 // schedule's.  Returns a hipError_t.
 template <bool FOLD_NONE>
-__attribute__((visibility("hidden"))) inline int launch_march(const MarchArgs& a, uint32_t schedule, uint32_t* counters, uint32_t grid, hipStream_t s) {
-    if (schedule == BH_SCHED_TILE)
+__attribute__((visibility("hidden"))) inline int launch_march(const MarchArgs& a, const MarchLaunch& m, hipStream_t s) {
+    if (m.schedule == BH_SCHED_TILE)
         return with_tile_form<FOLD_NONE>(
             a, [&](auto sf) { launch_tile_schedule(march_tile_lens_kernel<decltype(sf)::value>, a, s); },
             [&](auto fmt, auto sf, auto ss) {
@@ -95,13 +106,13 @@ __attribute__((visibility("hidden"))) inline int launch_march(const MarchArgs& a
 #endif
     return with_format(a.format, [&](auto fmt) {
         constexpr uint32_t FMT = decltype(fmt)::value;
-        if (schedule == BH_SCHED_PAIR) {
+        if (m.schedule == BH_SCHED_PAIR) {
             const uint32_t pairs = (a.n_tiles + 1u) / 2u;
             hipLaunchKernelGGL(march_pair_kernel<FMT>, dim3((pairs + 3u) / 4u), dim3(256), 0, s, a);
         } else {
-            hipError_t e = hipMemsetAsync(counters, 0, NQ * CTR_STRIDE * sizeof(uint32_t), s);
+            hipError_t e = hipMemsetAsync(m.counters, 0, NQ * CTR_STRIDE * sizeof(uint32_t), s);
             if (e != hipSuccess) return (int)e;
-            hipLaunchKernelGGL(march_persistent_kernel<FMT>, dim3(grid), dim3(256), 0, s, a, counters);
+            hipLaunchKernelGGL(march_persistent_kernel<FMT>, dim3(m.grid), dim3(256), 0, s, a, m.counters);
         }
         return (int)hipGetLastError();
     });
@@ -109,58 +120,60 @@ __attribute__((visibility("hidden"))) inline int launch_march(const MarchArgs& a
 #if !BH_FAST
 // The ray-map march (bh_render_rays, bh_render_lens_rays; tile schedule, one frame).
 template <bool FOLD_NONE>
-__attribute__((visibility("hidden"))) inline int launch_rays(const MarchArgs& a, const float* dirs, hipStream_t s) {
-    if (!dirs || a.n_frames != 1u) return (int)hipErrorInvalidValue;
+__attribute__((visibility("hidden"))) inline int launch_rays(const MarchArgs& a, const MarchLaunch& m, hipStream_t s) {
+    if (!m.dirs || a.n_frames != 1u) return (int)hipErrorInvalidValue;
     return with_tile_form<FOLD_NONE>(
-        a, [&](auto sf) { launch_tile_schedule(march_tile_rays_lens_kernel<decltype(sf)::value>, a, s, dirs); },
+        a, [&](auto sf) { launch_tile_schedule(march_tile_rays_lens_kernel<decltype(sf)::value>, a, s, m.dirs); },
         [&](auto fmt, auto sf, auto ss) {
             constexpr uint32_t FMT = decltype(fmt)::value, SF = decltype(sf)::value;
-            launch_tile_schedule(march_tile_rays_kernel<FMT, SF, decltype(ss)::value != 0u>, a, s, dirs);
+            launch_tile_schedule(march_tile_rays_kernel<FMT, SF, decltype(ss)::value != 0u>, a, s, m.dirs);
         });
 }
 // The posed ray-map march (bh_render_frames_rays, bh_render_frames_shutter_rays, bh_render_lens_rays_posed; tile
 // schedule): any number of frames over one camera-space map; ln != 0: the shutter form, 2^ln cameras per output frame.
 template <bool FOLD_NONE>
-__attribute__((visibility("hidden"))) inline int launch_rays_pose(const MarchArgs& a, const float* dirs, uint32_t ln, hipStream_t s) {
-    if (!dirs || a.n_frames == 0u) return (int)hipErrorInvalidValue;
+__attribute__((visibility("hidden"))) inline int launch_rays_pose(const MarchArgs& a, const MarchLaunch& m, hipStream_t s) {
+    const uint32_t ln = m.shutter_log2;
+    if (!m.dirs || a.n_frames == 0u) return (int)hipErrorInvalidValue;
     if (a.lens != 0u ? (ln != 0u || a.n_frames != 1u) : (ln > shutter::MAX_LOG2 || (a.n_frames & ((1u << ln) - 1u)) != 0u))
         return (int)hipErrorInvalidValue;
     return with_tile_form<FOLD_NONE>(
-        a, [&](auto sf) { launch_tile_schedule(march_tile_rays_pose_lens_kernel<decltype(sf)::value>, a, s, dirs); },
+        a, [&](auto sf) { launch_tile_schedule(march_tile_rays_pose_lens_kernel<decltype(sf)::value>, a, s, m.dirs); },
         [&](auto fmt, auto sf, auto ss) {
             constexpr uint32_t FMT = decltype(fmt)::value, SF = decltype(sf)::value;
-            if (ln != 0u) launch_shutter_schedule<FMT, march_tile_shutter_rays_kernel<FMT, SF>>(a, ln, s, dirs);
-            else launch_tile_schedule(march_tile_rays_pose_kernel<FMT, SF, decltype(ss)::value != 0u>, a, s, dirs);
+            if (ln != 0u) launch_shutter_schedule<FMT, march_tile_shutter_rays_kernel<FMT, SF>>(a, ln, s, m.dirs);
+            else launch_tile_schedule(march_tile_rays_pose_kernel<FMT, SF, decltype(ss)::value != 0u>, a, s, m.dirs);
         });
 }
 // The posed ray-map march with an origin map (bh_render_frames_rays_origins, bh_render_lens_rays_origins; tile
 // schedule, no shutter form): any number of frames over one pair of camera-space maps.
 template <bool FOLD_NONE>
-__attribute__((visibility("hidden"))) inline int launch_rays_org(const MarchArgs& a, const float* dirs, const float* orgs, hipStream_t s) {
-    if (!dirs || !orgs || a.n_frames == 0u || (a.lens != 0u && a.n_frames != 1u)) return (int)hipErrorInvalidValue;
+__attribute__((visibility("hidden"))) inline int launch_rays_org(const MarchArgs& a, const MarchLaunch& m, hipStream_t s) {
+    if (!m.dirs || !m.orgs || a.n_frames == 0u || (a.lens != 0u && a.n_frames != 1u)) return (int)hipErrorInvalidValue;
     return with_tile_form<FOLD_NONE>(
-        a, [&](auto sf) { launch_tile_schedule(march_tile_rays_org_lens_kernel<decltype(sf)::value>, a, s, dirs, orgs); },
+        a, [&](auto sf) { launch_tile_schedule(march_tile_rays_org_lens_kernel<decltype(sf)::value>, a, s, m.dirs, m.orgs); },
         [&](auto fmt, auto sf, auto ss) {
             constexpr uint32_t FMT = decltype(fmt)::value, SF = decltype(sf)::value;
-            launch_tile_schedule(march_tile_rays_org_kernel<FMT, SF, decltype(ss)::value != 0u>, a, s, dirs, orgs);
+            launch_tile_schedule(march_tile_rays_org_kernel<FMT, SF, decltype(ss)::value != 0u>, a, s, m.dirs, m.orgs);
         });
 }
 // The lens march with a hit map (bh_render_lens_hits: dirs null, the pinhole form; bh_render_lens_rays_posed_hits: the
 // posed ray-map form; tile schedule, one frame): one kernel per form and scene-flag fold.
 template <bool FOLD_NONE>
-__attribute__((visibility("hidden"))) inline int launch_lens_hits(const MarchArgs& a, const float* dirs, float* hits, hipStream_t s) {
-    if (!hits || a.lens == 0u || a.n_frames != 1u) return (int)hipErrorInvalidValue;
+__attribute__((visibility("hidden"))) inline int launch_lens_hits(const MarchArgs& a, const MarchLaunch& m, hipStream_t s) {
+    if (!m.hits || a.lens == 0u || a.n_frames != 1u) return (int)hipErrorInvalidValue;
     with_scene_fold<FOLD_NONE>(a.scene_flags, [&](auto sf) {
         constexpr uint32_t SF = decltype(sf)::value;
-        if (dirs) launch_tile_schedule(march_tile_rays_pose_lens_hits_kernel<SF>, a, s, dirs, hits);
-        else launch_tile_schedule(march_tile_lens_hits_kernel<SF>, a, s, hits);
+        if (m.dirs) launch_tile_schedule(march_tile_rays_pose_lens_hits_kernel<SF>, a, s, m.dirs, m.hits);
+        else launch_tile_schedule(march_tile_lens_hits_kernel<SF>, a, s, m.hits);
     });
     return (int)hipGetLastError();
 }
 #endif
 // The shutter render's march (bh_render_shutter, n = 2^ln cameras per output frame; tile schedule): the same folds.
 template <bool FOLD_NONE>
-__attribute__((visibility("hidden"))) inline int launch_shutter(const MarchArgs& a, uint32_t ln, hipStream_t s) {
+__attribute__((visibility("hidden"))) inline int launch_shutter(const MarchArgs& a, const MarchLaunch& m, hipStream_t s) {
+    const uint32_t ln = m.shutter_log2;
     if (ln == 0u || ln > shutter::MAX_LOG2 || (a.n_frames & ((1u << ln) - 1u)) != 0u) return (int)hipErrorInvalidValue;
     return with_format(a.format, [&](auto fmt) {
         with_scene_fold<FOLD_NONE>(a.scene_flags, [&](auto sf) {
@@ -169,6 +182,11 @@ __attribute__((visibility("hidden"))) inline int launch_shutter(const MarchArgs&
         });
         return (int)hipGetLastError();
     });
+}
+// The plain family's launcher: the shutter march when m.shutter_log2 != 0, else the march under m.schedule.
+template <bool FOLD_NONE>
+__attribute__((visibility("hidden"))) inline int launch_plain(const MarchArgs& a, const MarchLaunch& m, hipStream_t s) {
+    return m.shutter_log2 != 0u ? launch_shutter<FOLD_NONE>(a, m, s) : launch_march<FOLD_NONE>(a, m, s);
 }
 // The adaptive render's work-list march (bh_render_adaptive): the supersampled kernels' folds.
 template <bool FOLD_NONE>
@@ -183,3 +201,21 @@ __attribute__((visibility("hidden"))) inline int launch_refine(const MarchArgs& 
 
 }  // namespace BH_NS
 }  // namespace bh
+
+// ---- a unit's launcher ---------------------------------------------------------------------------------------
+// The one symbol a tile-march unit exports to the host units: bh_launch_unit_<namespace>, of the one type
+// int (const bh::MarchArgs&, const bh::MarchLaunch&, hipStream_t), forwarding to the family's template above.  A
+// unit that holds the work-list march exports bh_launch_refine_unit_<namespace> the same way.  bh_host.hpp declares
+// them from its list of namespaces.
+#define BH_PASTE_(a, b) a##b
+#define BH_PASTE(a, b) BH_PASTE_(a, b)
+#define BH_MARCH_UNIT(family, FOLD_NONE)                                                                              \
+    extern "C" __attribute__((visibility("hidden"))) int BH_PASTE(bh_launch_unit_, BH_NS)(                            \
+        const bh::MarchArgs& a, const bh::MarchLaunch& m, hipStream_t s) {                                            \
+        return bh::BH_NS::family<FOLD_NONE>(a, m, s);                                                                 \
+    }
+#define BH_REFINE_UNIT(FOLD_NONE)                                                                                     \
+    extern "C" __attribute__((visibility("hidden"))) int BH_PASTE(bh_launch_refine_unit_, BH_NS)(                     \
+        const bh::MarchArgs& a, const bh::RefineArgs& r, uint32_t waves, hipStream_t s) {                             \
+        return bh::BH_NS::launch_refine<FOLD_NONE>(a, r, waves, s);                                                   \
+    }

@@ -1,51 +1,48 @@
 // Exact (parity) instantiation of the march kernel.  Built with -ffp-contract=off and the default
 // correctly-rounded f32 division/sqrt: same op sequence as oracle/bh_oracle.c (bit-exact parity).
 //
-// Two builds of this file (same source, same arithmetic, different instruction schedules; build.py):
-//   bh_march_exact.hip      namespace exact      no machine scheduling: the step in source order, the
-//                                                faster issue stream for throughput-bound frames;
-//   bh_march_exact_lat.hip  namespace exact_lat  LLVM's machine schedulers: interleaved chains, the
-//                                                shorter latency per step of a lone tail wave.
-// bh_render picks one per frame (bh_host.cpp, march_variant).
-// A third build holds the adaptive render's work-list march alone (bh_march_refine_lat.hip).
+// Three builds of this file (same source, same arithmetic, different instruction schedules; the rows of build.py):
+//   bh_march_exact       namespace exact             no machine scheduling: the step in source order, the faster
+//                                                    issue stream for throughput-bound frames;
+//   bh_march_exact_lat   namespace exact_lat         -DBH_LAT=1: LLVM's machine schedulers: interleaved chains, the
+//                                                    shorter latency per step of a lone tail wave; its tail loop runs
+//                                                    the packed-FP32 step (bh_march_step.hpp, step_tail);
+//   bh_march_refine_lat  namespace exact_lat_refine  -DBH_LAT=1 -DBH_REFINE_ONLY=1: the adaptive render's work-list
+//                                                    march alone (bh_march_tile.hpp, march_refine_kernel), scheduled.
+// bh_render picks one of the first two per frame (bh_host.cpp, march_variant_issue_order).  The
+// work-list march has a unit of its own in the scheduled build because that unit is built without machine LICM: the
+// kernel is a loop of march_slot calls, and machine LICM hoists the march's loop invariants out of that loop and keeps
+// them live across it -- 129 VGPRs and 29 spilled SGPRs, 3 waves per SIMD, against 78 VGPRs and 6 waves without it
+// (the scheduled build's other kernels keep LICM: DESIGN.md §5 item 8, §7f).  The issue-order unit holds both.
 #define BH_FAST 0
-#ifndef BH_NS
+#if defined(BH_REFINE_ONLY)
+#define BH_NS exact_lat_refine
+#elif defined(BH_LAT)
+#define BH_NS exact_lat
+#else
 #define BH_NS exact
-#define BH_EXACT_LAUNCH bh_launch_march_exact
-#define BH_EXACT_BLOCKS bh_march_blocks_per_cu_exact
-#define BH_EXACT_SHUTTER bh_launch_shutter_exact
-#define BH_EXACT_REFINE bh_launch_refine_exact
-#define BH_EXACT_AUX 1
 #endif
 #include "bh_march.hpp"
 
 // The launchers: bh_march.hpp's, with the no-surfaces fold (FOLD_NONE) that the exact builds hold kernels for.
 #ifndef BH_REFINE_ONLY
-extern "C" __attribute__((visibility("hidden"))) int BH_EXACT_LAUNCH(const bh::MarchArgs& a, uint32_t schedule,
-                                                                     uint32_t* counters, uint32_t grid, hipStream_t s) {
-    return bh::BH_NS::launch_march<true>(a, schedule, counters, grid, s);
-}
+BH_MARCH_UNIT(launch_plain, true)
+#endif
+#if defined(BH_REFINE_ONLY) || !defined(BH_LAT)
+BH_REFINE_UNIT(true)
+#endif
+
+#ifndef BH_LAT
 // Resident 256-thread blocks per CU of the persistent kernel (sizes its grid: every block resident).
-extern "C" __attribute__((visibility("hidden"))) int BH_EXACT_BLOCKS(void) {
+extern "C" __attribute__((visibility("hidden"))) int bh_march_blocks_per_cu_exact(void) {
     int n = 0;
     if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, bh::BH_NS::march_persistent_kernel<BH_OUT_BGRA8_SRGB>, 256, 0) != hipSuccess) return 1;
     return n > 0 ? n : 1;
 }
-// The shutter render's march (bh_render_shutter): 2^ln cameras per output frame.
-extern "C" __attribute__((visibility("hidden"))) int BH_EXACT_SHUTTER(const bh::MarchArgs& a, uint32_t ln, hipStream_t s) {
-    return bh::BH_NS::launch_shutter<true>(a, ln, s);
-}
-#endif  // BH_REFINE_ONLY
+#endif
 
-#ifdef BH_EXACT_REFINE
-extern "C" __attribute__((visibility("hidden"))) int BH_EXACT_REFINE(const bh::MarchArgs& a, const bh::RefineArgs& r,
-                                                                     uint32_t waves, hipStream_t s) {
-    return bh::BH_NS::launch_refine<true>(a, r, waves, s);
-}
-#endif  // BH_EXACT_REFINE
-
-#if defined(BH_DIAG_SLOW) && defined(BH_EXACT_AUX)
-// diagnostics build only: read and reset the fallback counters
+#if defined(BH_DIAG_SLOW) && !defined(BH_LAT)
+// diagnostics build only (the first build's): read and reset the fallback counters
 extern "C" int bh_diag_slow_counts(uint32_t* lane_steps, uint32_t* wave_steps) {
     uint32_t z = 0;
     if (hipMemcpyFromSymbol(lane_steps, HIP_SYMBOL(bh::BH_NS::g_diag_slow_lane_steps), 4) != hipSuccess) return -1;

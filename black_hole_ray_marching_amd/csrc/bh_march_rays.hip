@@ -3,17 +3,16 @@
 // of their kernels -- those units' code objects stay what they were, and these 21 kernels compile beside them
 // instead of after them.
 //
-// Two builds of this file, as of bh_march_exact.hip (build.py):
-//   bh_march_rays.hip      namespace exact_rays      no machine scheduling: the throughput-bound frames' build;
-//   bh_march_rays_lat.hip  namespace exact_rays_lat  LLVM's machine schedulers and the packed tail step.
+// Two builds of this file (the rows of build.py):
+//   bh_march_rays      namespace exact_rays      no machine scheduling: the throughput-bound build;
+//   bh_march_rays_lat  namespace exact_rays_lat  -DBH_LAT=1: the machine schedulers and the packed tail step.
 // bh_render_rays picks one per launch by bh_render's rule (bh_host.cpp, march_variant_issue_order).
 #define BH_FAST 0
-#ifndef BH_NS
+#ifdef BH_LAT
+#define BH_NS exact_rays_lat
+#else
 #define BH_NS exact_rays
-#define BH_RAYS_LAUNCH bh_launch_rays_exact
 #endif
 #include "bh_march.hpp"
 
-extern "C" __attribute__((visibility("hidden"))) int BH_RAYS_LAUNCH(const bh::MarchArgs& a, const float* dirs, hipStream_t s) {
-    return bh::BH_NS::launch_rays<true>(a, dirs, s);
-}
+BH_MARCH_UNIT(launch_rays, true)

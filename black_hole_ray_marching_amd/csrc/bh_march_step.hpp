@@ -641,7 +641,7 @@ __device__ __forceinline__ uint32_t march_step(const MarchArgs& a, const Frame& 
 }
 
 // One iteration of a tail wave (the tile schedule's cycle watch), in place: BH_FATE_* if the ray
-// terminates, else 0xFF.  The latency build of the exact kernels (BH_TAIL_PACKED, bh_march_exact_lat.hip)
+// terminates, else 0xFF.  The latency build of the exact kernels (BH_TAIL_PACKED, the -DBH_LAT=1 units)
 // runs the packed step, with the same rare IEEE re-run: a lone tail wave's step 0.89 -> 0.79 us, config
 // 5 (one frame, cap 1000) 0.824 -> 0.734 ms.  The issue-order build keeps the scalar step: in
 // multi-frame launches the tail waves share their SIMDs with other frames' bulk, where a packed op
