@@ -506,11 +506,35 @@ int bh_first_step_host(const bh_camera_uniform* cam, const bh_uniforms* U, uint3
 }
 
 // ---- one march launch --------------------------------------------------------------------------------------
-// Every render entry point is the same few steps over this record: check_launch, fill_args, then either
-// learned_order and launch_march (bh_render_frames, bh_render_frames_ss, bh_render_lens) or launch_refine
-// (bh_render_frames_adaptive's second pass).  A supersampled render (ss = k > 1) is the launch of the virtual
-// frame k*width x k*height -- geometry, order state, repeat-frame key and all -- with log2 k and the output
-// width for the kernel's resolve epilogue.
+// What a render entry point asks for, as its caller passed it and nothing derived.  Every entry point but the
+// adaptive pair fills one and calls render_request, which checks it in one order, whatever the form; the adaptive
+// render fills one for its second pass.
+enum : uint32_t { TAKES_DIRS = 1u, TAKES_ORGS = 2u, TAKES_LENS = 4u, TAKES_HITS = 8u };
+enum RaySource : uint32_t { PINHOLE, WORLD_MAP, POSED_MAP };
+struct Request {
+    const char* fn;                            // the entry point, for messages
+    uint32_t n_frames = 1u, n_sub = 1u, ss = 1u;
+    RaySource source = PINHOLE;                // which one of the next three the entry point takes
+    const bh_camera_uniform* cams = nullptr;   // PINHOLE: n_frames * n_sub cameras
+    const float* pos = nullptr;                // WORLD_MAP: a world-space ray map's one position
+    const bh_ray_pose* poses = nullptr;        // POSED_MAP: a camera-space ray map's n_frames * n_sub poses
+    const bh_uniforms* U = nullptr;
+    const bh_render_desc* descs = nullptr;     // n_frames of them
+    uint32_t takes = 0u;                       // TAKES_*: which of the next four the entry point has (each required)
+    const float* dirs = nullptr;               // the ray map, 4-byte aligned
+    const float* orgs = nullptr;               // the origin map, 4-byte aligned
+    bh_lens_px* lens = nullptr;                // the lens, 8-byte aligned: written in place of target 0
+    float* hits = nullptr;                     // the hit map, 4-byte aligned
+    uint32_t n_cams() const { return n_frames * n_sub; }
+    const void* rays() const { return source == PINHOLE ? (const void*)cams : source == WORLD_MAP ? (const void*)pos : (const void*)poses; }
+    // bh_render(_frames): nothing but cameras and descs
+    bool plain() const { return source == PINHOLE && !takes && ss == 1u && n_sub == 1u; }
+};
+
+// The launch of a checked request: check_launch leaves its desc and tile count, fill_args everything else; then
+// either learned_order and launch_march (render_request) or launch_refine (bh_render_frames_adaptive's second pass).
+// A supersampled render (ss = k > 1) is the launch of the virtual frame k*width x k*height -- geometry, order state,
+// repeat-frame key and all -- with log2 k and the output width for the kernel's resolve epilogue.
 struct Launch {
     bh_render_desc d;                  // the launch's desc: the virtual frame's (per-frame outputs stay in descs[i])
     bh::MarchArgs a;                   // the kernel argument
@@ -519,6 +543,7 @@ struct Launch {
     uint64_t n_tiles = 0;              // the shard's tiles
     bh::MarchLaunch m;                 // what the unit's launcher takes beside `a`: the maps, the shutter, the schedule
     const bh_ray_pose* poses = nullptr;  // the posed ray-map forms: one pose per camera (a.n_frames of them), else null
+    bh_camera_uniform cam0;            // camera 0: the caller's, or a ray map's position-only camera (order centre, key)
 };
 
 // What a frame's per-tile costs (the march's step counts) depend on: the camera, the shader uniforms and the
@@ -604,40 +629,65 @@ static bool sdf_skip_disabled() {
 }
 
 // What the resolve in the wave does not cover (include/bh_render.h), checked on every frame's desc: what the
-// launch needs instead, or null.
-static const char* ss_needs(const bh_render_desc* descs, uint32_t n_frames) {
+// launch needs instead, or null.  per_ray_dbg: the dbg_* outputs are allowed (a ray-map render that resolves nothing).
+static const char* ss_needs(const bh_render_desc* descs, uint32_t n_frames, bool per_ray_dbg = false) {
     for (uint32_t i = 0; i < n_frames; ++i) {
         const bh_render_desc* e = &descs[i];
         const char* why = e->layout != BH_LAYOUT_ROWMAJOR      ? "a row-major output (BH_LAYOUT_ROWMAJOR)"
                           : e->shard_count != 1u               ? "the whole frame (shard_count 1)"
                           : e->partition                       ? "no partition"
                           : (e->schedule & 0xFFu) != BH_SCHED_TILE ? "the tile schedule (BH_SCHED_TILE)"
-                          : (e->dbg_n_rk || e->dbg_fate || e->dbg_steps) ? "no dbg_* outputs (they are per ray, not per pixel)"
+                          : !per_ray_dbg && (e->dbg_n_rk || e->dbg_fate || e->dbg_steps) ? "no dbg_* outputs (they are per ray, not per pixel)"
                                                                : nullptr;
         if (why) return why;
     }
     return nullptr;
 }
 
-// Every argument check of a launch; no HIP call.  Leaves the launch's desc and tile count in L.
-static int check_launch(const bh_ctx* c, uint32_t n_frames, const bh_camera_uniform* cams, const bh_uniforms* U,
-                        const bh_render_desc* descs, uint32_t ss, Launch* L) {
-    if (!c || !cams || !U || !descs || n_frames == 0 || n_frames > BH_MAX_FRAMES) return bad_arg(__func__, __LINE__);
-    const bh_render_desc* const d0 = &descs[0];
+// What the request's form refuses of its descs (BH_ERR_UNSUPPORTED): what it needs instead, or null.  A pinhole render
+// that resolves in the wave (ss > 1, a shutter) needs what ss_needs lists; a lens and a ray map need it always, a lens
+// no colour target, and both exact math.
+static const char* request_needs(const Request& r) {
+    if (r.plain()) return nullptr;
+    const bool map = r.source != PINHOLE, lens = (r.takes & TAKES_LENS) != 0u;
+    for (uint32_t i = 0; i < r.n_frames; ++i) {
+        const bh_render_desc* e = &r.descs[i];
+        // the two families' own predicates, kept as they are: a pinhole lens refuses every math but exact here (an
+        // unknown one too); a ray map refuses fast math alone (an unknown one is check_launch's invalid argument)
+        if (map && e->math == BH_MATH_FAST) return "exact math (BH_MATH_EXACT): a ray map has no fast-math kernels";
+        if (!map && lens && e->math != BH_MATH_EXACT) return "exact math (BH_MATH_EXACT): fast math has no defined bits to promise";
+        if (lens && (e->out_col || e->out_blackout)) return "no out_col or out_blackout (it writes only the lens)";
+    }
+    // a ray map's dbg_* outputs are per ray: allowed where bh_render_frames allows them (nothing resolved, no lens)
+    return ss_needs(r.descs, r.n_frames, map && !lens && r.ss == 1u && r.n_sub == 1u);
+}
+
+// The checks of a launch's desc, cameras and tile count, after render_request's (or the adaptive render's) own; no HIP
+// call.  Leaves the launch's desc and tile count in L.
+static int check_launch(const bh_ctx* c, const Request& r, Launch* L) {
+    const uint32_t n_frames = r.n_cams();  // a frame of the launch is a camera
+    if (!c || !r.rays() || !r.U || !r.descs || n_frames == 0 || n_frames > BH_MAX_FRAMES) return bad_arg(r.fn, __LINE__);
+    const bool lens = (r.takes & TAKES_LENS) != 0u;
+    const bh_render_desc* const d0 = &r.descs[0];
     L->d = *d0;
-    if (ss > 1u) { L->d.width *= ss; L->d.height *= ss; }
+    if (r.ss > 1u) { L->d.width *= r.ss; L->d.height *= r.ss; }
+    if (lens) {  // bh_render's launch of the frame with the lens in place of target 0; the format word is not read
+        L->d.format = BH_OUT_RGBA32F;
+        L->d.out_col = r.lens;
+    }
     const bh_render_desc* d = &L->d;
-    if (!d->out_col) return bad_arg(__func__, __LINE__);
-    if (!frame_shape_ok(d->width, d->height, 1u)) return bad_arg(__func__, __LINE__);
-    if (d->max_iters == 0 || d->max_iters > 65535u) return bad_arg(__func__, __LINE__);
-    if (d->format > BH_OUT_BGRA8_SRGB || d->math > BH_MATH_FAST || d->layout > BH_LAYOUT_TILES_RGBM14) return bad_arg(__func__, __LINE__);
-    if ((d->schedule & 0xFFu) > BH_SCHED_PERSISTENT || (d->schedule & ~(0xFFu | BH_SCHED_FLAG_STATIC_ORDER | BH_SCHED_FLAG_ISSUE_ORDER | BH_SCHED_FLAG_LATENCY))) return bad_arg(__func__, __LINE__);
-    if (d->scene_flags & ~BH_SCENE_DEFAULT) return bad_arg(__func__, __LINE__);
-    if (d->shard_count == 0 || d->shard_index >= d->shard_count) return bad_arg(__func__, __LINE__);
-    if (d->layout == BH_LAYOUT_ROWMAJOR && d->shard_count != 1) return bad_arg(__func__, __LINE__);
+    if (!d->out_col) return bad_arg(r.fn, __LINE__);
+    if (!frame_shape_ok(d->width, d->height, 1u)) return bad_arg(r.fn, __LINE__);
+    if (d->max_iters == 0 || d->max_iters > 65535u) return bad_arg(r.fn, __LINE__);
+    if (d->format > BH_OUT_BGRA8_SRGB || d->math > BH_MATH_FAST || d->layout > BH_LAYOUT_TILES_RGBM14) return bad_arg(r.fn, __LINE__);
+    if ((d->schedule & 0xFFu) > BH_SCHED_PERSISTENT || (d->schedule & ~(0xFFu | BH_SCHED_FLAG_STATIC_ORDER | BH_SCHED_FLAG_ISSUE_ORDER | BH_SCHED_FLAG_LATENCY))) return bad_arg(r.fn, __LINE__);
+    if (d->scene_flags & ~BH_SCENE_DEFAULT) return bad_arg(r.fn, __LINE__);
+    if (d->shard_count == 0 || d->shard_index >= d->shard_count) return bad_arg(r.fn, __LINE__);
+    if (d->layout == BH_LAYOUT_ROWMAJOR && d->shard_count != 1) return bad_arg(r.fn, __LINE__);
     for (uint32_t i = 0; i < n_frames; ++i) {
-        if (!descs[i].out_col || !same_launch(d0, &descs[i])) return bad_arg(__func__, __LINE__);
-        if (!screen_tri_default(&cams[i])) { g_last_error = "non-default screen triangle"; return BH_ERR_UNSUPPORTED; }
+        const bh_render_desc* e = &r.descs[i / r.n_sub];
+        if ((!lens && !e->out_col) || !same_launch(d0, e)) return bad_arg(r.fn, __LINE__);
+        if (r.cams && !screen_tri_default(&r.cams[i])) { g_last_error = "non-default screen triangle"; return BH_ERR_UNSUPPORTED; }
     }
     const uint32_t sched = d->schedule & 0xFFu;
     if ((d->layout == BH_LAYOUT_TILES_RGBM || d->layout == BH_LAYOUT_TILES_RGBM14) && sched == BH_SCHED_PERSISTENT) {
@@ -663,13 +713,19 @@ static int check_launch(const bh_ctx* c, uint32_t n_frames, const bh_camera_unif
         L->n_tiles = bh::shard_tile_count((d->width + 7u) / 8u, (d->height + 7u) / 8u, d->shard_index, d->shard_count);
     }
     // the launch's wave slots; the frames of another schedule than the tile schedule launch one by one
-    if (L->n_tiles * (sched == BH_SCHED_TILE ? n_frames : 1u) > 0xFFFFFFF0ull) return bad_arg(__func__, __LINE__);
+    if (L->n_tiles * (sched == BH_SCHED_TILE ? n_frames : 1u) > 0xFFFFFFF0ull) return bad_arg(r.fn, __LINE__);
     return BH_OK;
 }
 
-// The kernel argument of a checked launch, and the frames' table when they do not fit inline.  Pure.
-static void fill_args(const bh_ctx* c, uint32_t n_frames, const bh_camera_uniform* cams, const bh_uniforms* U,
-                      const bh_render_desc* descs, uint32_t ss, Launch* L) {
+// The whole launch of a checked request: the kernel argument, the frames' table when they do not fit inline, the maps
+// and the form's words.  Pure; no caller writes into L afterwards.  One FrameArgs entry per camera: frame f's outputs
+// in every entry of its n_sub cameras (a shutter's writer wave reads its own camera's entry), the lens in place of
+// target 0; a ray map's camera holds only its position -- the map kernels do not read the corner rays -- and a posed
+// one its pose's basis rows in c0..c2, where march_slot's POSE form reads them.
+static void fill_args(const bh_ctx* c, const Request& r, Launch* L) {
+    const bh_uniforms* U = r.U;
+    const bh_render_desc* descs = r.descs;
+    const uint32_t n_frames = r.n_cams(), ss = r.ss;
     const bh_render_desc* d = &L->d;
     bh::MarchArgs& a = L->a;
     std::memset(&a, 0, sizeof(a));
@@ -678,7 +734,10 @@ static void fill_args(const bh_ctx* c, uint32_t n_frames, const bh_camera_unifor
     a.skip_sdf = (U->delta_time_mult > 0.0f && U->rs > 0.0f && U->rs <= 8.0f && !sdf_skip_disabled()) ? 1u : 0u;
     a.far_r2 = a.skip_sdf ? sdf_far_r2(U->rs, U->delta_time_mult) : INFINITY;
     a.width = d->width; a.height = d->height; a.max_iters = d->max_iters; a.scene_flags = d->scene_flags;
-    if (ss > 1u) { a.ss_log2 = bh::ss::log2_k(ss); a.ss_out_width = descs[0].width; }
+    if (ss > 1u) a.ss_log2 = bh::ss::log2_k(ss);
+    // the resolve's output width; the shutter kernels index the output through it at every ss
+    if (ss > 1u || r.n_sub > 1u) a.ss_out_width = descs[0].width;
+    a.lens = (r.takes & TAKES_LENS) ? 1u : 0u;
     a.format = d->format; a.layout = d->layout;
     a.shard_index = d->shard_index; a.shard_count = d->shard_count;
     a.tiles_x = (d->width + 7u) / 8u; a.tiles_y = (d->height + 7u) / 8u;
@@ -686,7 +745,6 @@ static void fill_args(const bh_ctx* c, uint32_t n_frames, const bh_camera_unifor
     a.n_tiles = (uint32_t)L->n_tiles;
     // centre-out dispatch blocks of ~one tile row of this shard, centred on the black hole's row
     a.order_block = (uint32_t)((L->n_tiles + a.tiles_y - 1u) / a.tiles_y);
-    a.order_centre = bh_tile_row(&cams[0], d->height);
     a.sky = c->sky; a.srgb_lut = c->lut; a.srgb_enc = c->enc; a.sky_w = c->sky_w; a.sky_h = c->sky_h;
     // k = (DP * RS) * -1.5 (:126); the per-frame fields (camera, c_ps, outputs)
     a.kfac = (a.dp * a.rs) * -1.5f;
@@ -703,9 +761,23 @@ static void fill_args(const bh_ctx* c, uint32_t n_frames, const bh_camera_unifor
     L->m.schedule = d->schedule & 0xFFu;
     L->m.counters = c->counters;
     L->m.grid = d->math != BH_MATH_EXACT ? c->grid_fast : c->grid_exact;
+    L->m.shutter_log2 = bh::shutter::log2_n(r.n_sub);
+    L->m.dirs = r.dirs; L->m.orgs = r.orgs; L->m.hits = r.hits;
+    L->poses = r.poses;
     if (n_frames > bh::BH_INLINE_FRAMES) L->table.resize(n_frames);
     bh::FrameArgs* fa = L->table.empty() ? a.frames : L->table.data();
-    for (uint32_t i = 0; i < n_frames; ++i) frame_args(&cams[i], a.rs, &descs[i], &fa[i]);
+    for (uint32_t i = 0; i < n_frames; ++i) {
+        bh_camera_uniform of_map;
+        if (!r.cams) position_camera(&of_map, r.pos ? r.pos : r.poses[i].pos);
+        const bh_camera_uniform* cam = r.cams ? &r.cams[i] : &of_map;
+        frame_args(cam, a.rs, &descs[i / r.n_sub], &fa[i]);
+        if (a.lens) fa[i].out_col = r.lens;
+        for (int k = 0; r.poses && k < 3; ++k) {
+            fa[i].c0[k] = r.poses[i].r[k]; fa[i].c1[k] = r.poses[i].u[k]; fa[i].c2[k] = r.poses[i].f[k];
+        }
+        if (i == 0u) L->cam0 = *cam;
+    }
+    a.order_centre = bh_tile_row(&L->cam0, d->height);
     // the frames' first-step records, for the exact builds' tile-schedule kernels (the others never read them); the
     // records of a staged launch ride behind its table
     if (!L->table.empty()) L->first_table.assign(n_frames, bh::FirstStep{0.0f, 0.0f, 0.0f});
@@ -804,9 +876,9 @@ static_assert(exact_units_filled(), "every family has both exact builds");
 // before those of the fields it implies.
 static MarchFamily march_family(const Launch& L) {
     return L.m.hits   ? FAMILY_HITS   // one frame's lens (bh_render_lens_hits; posed: L.m.dirs)
-           : L.m.orgs ? FAMILY_ORG    // no shutter form (render_rays_posed with an origin map)
-           : L.poses  ? FAMILY_POSE   // render_rays_posed; the shutter form when shutter_log2 != 0
-           : L.m.dirs ? FAMILY_RAYS   // render_rays
+           : L.m.orgs ? FAMILY_ORG    // no shutter form (bh_render_frames_rays_origins and its lens)
+           : L.poses  ? FAMILY_POSE   // a posed map; the shutter form when shutter_log2 != 0
+           : L.m.dirs ? FAMILY_RAYS   // a world-space map (bh_render_rays)
                       : FAMILY_PLAIN; // the shutter march when shutter_log2 != 0, else by the schedule
 }
 static MarchBuild march_build(const bh_render_desc* d, bool issue) {
@@ -860,7 +932,7 @@ static int launch_refine(bh_ctx* c, const Launch& L, const bh::RefineArgs& R, hi
 }
 
 // order -> march: the tail of every launch but the adaptive render's second pass
-static int march_in_order(bh_ctx* c, Launch* L, const bh_camera_uniform* cam0, const bh_uniforms* U, void* stream) {
+static int march_in_order(bh_ctx* c, Launch* L, const bh_uniforms* U, void* stream) {
     if (L->a.n_tiles == 0) return BH_OK;
     DeviceScope dev(c->device);
     if (dev.err != hipSuccess) return hip_fail(dev.err, "hipSetDevice");
@@ -868,25 +940,99 @@ static int march_in_order(bh_ctx* c, Launch* L, const bh_camera_uniform* cam0, c
     int st = stage_frames(c, s, L);
     if (st != BH_OK) return st;
     bh_ctx::OrderState* os = nullptr;
-    st = learned_order(c, L, cam0, U, s, &os);
+    st = learned_order(c, L, &L->cam0, U, s, &os);
     if (st != BH_OK) return st;
     return launch_march(c, *L, os, s);
 }
 
+// ---- the render entry points (include/bh_render.h) -----------------------------------------------------------
+// Every one of them but the adaptive pair: the request's checks in one order, then its launch.  The launch is the one
+// bh_render_frames(_ss) makes of the n_frames * n_sub cameras -- geometry, order state, repeated-frame key (camera 0 of
+// frame 0: the order it stands for is the same array of tiles whichever kernel walks it), frame table -- whatever
+// marches it: the shutter kernels, a lens in place of target 0, a ray map's kernels (with an order state and a key of
+// their own: the maps in the launch's record).
+static int render_request(bh_ctx* c, const Request& r, void* stream) {
+    auto misaligned = [](const void* p, uintptr_t to) { return !p || (reinterpret_cast<uintptr_t>(p) & (to - 1u)); };
+    // 1. the pointers; a map or output the entry point takes is required, and aligned
+    if (!c || !r.rays() || !r.U || !r.descs) return bad_arg(r.fn, __LINE__);
+    if (((r.takes & TAKES_DIRS) && misaligned(r.dirs, 4u)) || ((r.takes & TAKES_ORGS) && misaligned(r.orgs, 4u)) ||
+        ((r.takes & TAKES_HITS) && misaligned(r.hits, 4u)) || ((r.takes & TAKES_LENS) && misaligned(r.lens, 8u)))
+        return bad_arg(r.fn, __LINE__);
+    // 2. ss and n_sub; an origin map has no shutter form
+    if (bh::ss::log2_k(r.ss) > 3u || bh::shutter::log2_n(r.n_sub) > bh::shutter::MAX_LOG2) return bad_arg(r.fn, __LINE__);
+    if ((r.takes & TAKES_ORGS) && r.n_sub != 1u) return bad_arg(r.fn, __LINE__);
+    // 3. the frame count: nothing beyond descs[0], cams[0] or poses[0] is read before it has passed
+    if (r.n_frames == 0 || (uint64_t)r.n_frames * r.n_sub > BH_MAX_FRAMES) return bad_arg(r.fn, __LINE__);
+    // 4. the frame shape
+    if (!frame_shape_ok(r.descs[0].width, r.descs[0].height, r.ss)) return bad_arg(r.fn, __LINE__);
+    // 5. what the form needs of its descs
+    if (const char* why = request_needs(r)) {
+        g_last_error = r.source != PINHOLE       ? std::string(r.fn) + ": a ray-map render needs "
+                       : (r.takes & TAKES_LENS)  ? std::string(r.fn) + ": a lens render needs "
+                       : r.n_sub > 1u            ? "bh_render_shutter: a shutter render (n_sub > 1) needs "
+                                                 : "bh_render_ss: a supersampled render (ss > 1) needs ";
+        g_last_error += std::string(why) + ".";
+        return BH_ERR_UNSUPPORTED;
+    }
+    // 6. the launch's own
+    Launch L;
+    int st = check_launch(c, r, &L);
+    if (st != BH_OK) return st;
+    // only a plain request gets here with another schedule than the tile schedule: one launch per frame
+    if (r.n_frames > 1u && (L.d.schedule & 0xFFu) != BH_SCHED_TILE) {
+        Request one = r;
+        one.n_frames = 1u;
+        for (uint32_t i = 0; i < r.n_frames && st == BH_OK; ++i) {
+            one.cams = &r.cams[i];
+            one.descs = &r.descs[i];
+            st = render_request(c, one, stream);
+        }
+        return st;
+    }
+    try {
+        fill_args(c, r, &L);
+    } catch (const std::bad_alloc&) {  // the frames' table of a launch of more than BH_INLINE_FRAMES cameras
+        return BH_ERR_OUT_OF_MEMORY;
+    }
+    return march_in_order(c, &L, r.U, stream);
+}
+
+static Request request(const char* fn, uint32_t n_frames, uint32_t n_sub, const bh_uniforms* U,
+                       const bh_render_desc* descs, uint32_t ss) {
+    Request r{fn};
+    r.n_frames = n_frames; r.n_sub = n_sub; r.ss = ss;
+    r.U = U; r.descs = descs;
+    return r;
+}
+static Request pinhole(const char* fn, uint32_t n_frames, uint32_t n_sub, const bh_camera_uniform* cams,
+                       const bh_uniforms* U, const bh_render_desc* descs, uint32_t ss) {
+    Request r = request(fn, n_frames, n_sub, U, descs, ss);
+    r.cams = cams;
+    return r;
+}
+// one frame of a world-space ray map, from `pos`
+static Request world_map(const char* fn, const float* pos, const bh_uniforms* U, const bh_render_desc* d,
+                         const float* dirs, uint32_t ss) {
+    Request r = request(fn, 1u, 1u, U, d, ss);
+    r.source = WORLD_MAP; r.pos = pos;
+    r.takes = TAKES_DIRS; r.dirs = dirs;
+    return r;
+}
+// n_frames * n_sub poses of a camera-space ray map
+static Request posed_map(const char* fn, uint32_t n_frames, uint32_t n_sub, const bh_ray_pose* poses,
+                         const bh_uniforms* U, const bh_render_desc* descs, const float* dirs, uint32_t ss) {
+    Request r = request(fn, n_frames, n_sub, U, descs, ss);
+    r.source = POSED_MAP; r.poses = poses;
+    r.takes = TAKES_DIRS; r.dirs = dirs;
+    return r;
+}
+static Request& with_lens(Request& r, bh_lens_px* out_lens) { r.takes |= TAKES_LENS; r.lens = out_lens; return r; }
+static Request& with_hits(Request& r, float* out_hits) { r.takes |= TAKES_HITS; r.hits = out_hits; return r; }
+static Request& with_origins(Request& r, const float* origins) { r.takes |= TAKES_ORGS; r.orgs = origins; return r; }
+
 int bh_render_frames(bh_ctx* c, uint32_t n_frames, const bh_camera_uniform* cams, const bh_uniforms* U,
                      const bh_render_desc* descs, void* stream) {
-    Launch L;
-    int st = check_launch(c, n_frames, cams, U, descs, 1u, &L);
-    if (st != BH_OK) return st;
-    if (n_frames > 1u && (L.d.schedule & 0xFFu) != BH_SCHED_TILE) {  // one launch per frame
-        for (uint32_t i = 0; i < n_frames; ++i) {
-            st = bh_render_frames(c, 1u, &cams[i], U, &descs[i], stream);
-            if (st != BH_OK) return st;
-        }
-        return BH_OK;
-    }
-    fill_args(c, n_frames, cams, U, descs, 1u, &L);
-    return march_in_order(c, &L, cams, U, stream);
+    return render_request(c, pinhole(__func__, n_frames, 1u, cams, U, descs, 1u), stream);
 }
 
 int bh_render_ss(bh_ctx* c, const bh_camera_uniform* cam, const bh_uniforms* U, const bh_render_desc* d, uint32_t ss,
@@ -894,22 +1040,11 @@ int bh_render_ss(bh_ctx* c, const bh_camera_uniform* cam, const bh_uniforms* U, 
     return bh_render_frames_ss(c, 1u, cam, U, d, ss, stream);
 }
 
+// ss == 1 is the plain call, its messages' name included
 int bh_render_frames_ss(bh_ctx* c, uint32_t n_frames, const bh_camera_uniform* cams, const bh_uniforms* U,
                         const bh_render_desc* descs, uint32_t ss, void* stream) {
-    const uint32_t lk = bh::ss::log2_k(ss);
-    if (lk > 3u) return bad_arg(__func__, __LINE__);
     if (ss == 1u) return bh_render_frames(c, n_frames, cams, U, descs, stream);
-    if (!c || !cams || !U || !descs || n_frames == 0 || n_frames > BH_MAX_FRAMES) return bad_arg(__func__, __LINE__);
-    if (!frame_shape_ok(descs[0].width, descs[0].height, ss)) return bad_arg(__func__, __LINE__);
-    if (const char* why = ss_needs(descs, n_frames)) {
-        g_last_error = std::string("bh_render_ss: a supersampled render (ss > 1) needs ") + why + ".";
-        return BH_ERR_UNSUPPORTED;
-    }
-    Launch L;
-    const int st = check_launch(c, n_frames, cams, U, descs, ss, &L);
-    if (st != BH_OK) return st;
-    fill_args(c, n_frames, cams, U, descs, ss, &L);
-    return march_in_order(c, &L, cams, U, stream);
+    return render_request(c, pinhole(__func__, n_frames, 1u, cams, U, descs, ss), stream);
 }
 
 // ---- shutter renders (include/bh_render.h; the mapping and the tree: bh_shutter.hpp) -----------------------
@@ -918,240 +1053,75 @@ int bh_render_shutter(bh_ctx* c, uint32_t n_sub, const bh_camera_uniform* cams, 
     return bh_render_frames_shutter(c, 1u, n_sub, cams, U, d, ss, stream);
 }
 
-// The launch of n_frames * n_sub cameras as bh_render_frames(_ss) would launch them -- geometry, order state,
-// repeated-frame key (camera 0 of frame 0: the order it stands for is the same array of tiles whichever kernel
-// walks it), frame table -- marched by the shutter kernels: one FrameArgs entry per camera, the output pointers
-// of frame f in every entry of its group (a writer wave reads its own camera's entry).
+// n_sub == 1 is the ss call (an ss this call would refuse stays this call's to refuse)
 int bh_render_frames_shutter(bh_ctx* c, uint32_t n_frames, uint32_t n_sub, const bh_camera_uniform* cams,
                              const bh_uniforms* U, const bh_render_desc* descs, uint32_t ss, void* stream) {
-    const uint32_t ln = bh::shutter::log2_n(n_sub);
-    if (ln > bh::shutter::MAX_LOG2 || bh::ss::log2_k(ss) > 3u) return bad_arg(__func__, __LINE__);
-    if (n_sub == 1u) return bh_render_frames_ss(c, n_frames, cams, U, descs, ss, stream);
-    if (!c || !cams || !U || !descs || n_frames == 0 || (uint64_t)n_frames * n_sub > BH_MAX_FRAMES) return bad_arg(__func__, __LINE__);
-    if (!frame_shape_ok(descs[0].width, descs[0].height, ss)) return bad_arg(__func__, __LINE__);
-    if (const char* why = ss_needs(descs, n_frames)) {
-        g_last_error = std::string("bh_render_shutter: a shutter render (n_sub > 1) needs ") + why + ".";
-        return BH_ERR_UNSUPPORTED;
-    }
-    const uint32_t n_cams = n_frames * n_sub;
-    std::vector<bh_render_desc> per_cam;
-    try {
-        per_cam.reserve(n_cams);
-    } catch (const std::bad_alloc&) {
-        return BH_ERR_OUT_OF_MEMORY;
-    }
-    for (uint32_t i = 0; i < n_cams; ++i) per_cam.push_back(descs[i / n_sub]);
-    Launch L;
-    const int st = check_launch(c, n_cams, cams, U, per_cam.data(), ss, &L);
-    if (st != BH_OK) return st;
-    fill_args(c, n_cams, cams, U, per_cam.data(), ss, &L);
-    L.a.ss_out_width = descs[0].width;  // the shutter kernels index the output through it at every ss
-    L.m.shutter_log2 = ln;
-    return march_in_order(c, &L, cams, U, stream);
+    if (n_sub == 1u && bh::ss::log2_k(ss) <= 3u) return bh_render_frames_ss(c, n_frames, cams, U, descs, ss, stream);
+    return render_request(c, pinhole(__func__, n_frames, n_sub, cams, U, descs, ss), stream);
 }
 
-// ---- lens maps (include/bh_render.h; the shading of a record: bh_lens.hpp) ---------------------------------
-// bh_render_lens (out_hits null) and bh_render_lens_hits
-static int render_lens(const char* fn, bh_ctx* c, const bh_camera_uniform* cam, const bh_uniforms* U,
-                       const bh_render_desc* d, bh_lens_px* out_lens, float* out_hits, void* stream) {
-    if (!c || !cam || !U || !d || !out_lens || (reinterpret_cast<uintptr_t>(out_lens) & 7u)) return bad_arg(fn, __LINE__);
-    const char* why = d->math != BH_MATH_EXACT ? "exact math (BH_MATH_EXACT): fast math has no defined bits to promise"
-                      : (d->out_col || d->out_blackout) ? "no out_col or out_blackout (it writes only the lens)"
-                                                        : ss_needs(d, 1u);
-    if (why) {
-        g_last_error = std::string(fn) + ": a lens render needs " + why + ".";
-        return BH_ERR_UNSUPPORTED;
-    }
-    // bh_render's launch of this frame -- the same geometry, order state and repeated-frame key -- with the
-    // lens in place of target 0; the format word is not read
-    bh_render_desc ld = *d;
-    ld.format = BH_OUT_RGBA32F;
-    ld.out_col = out_lens;
-    Launch L;
-    const int st = check_launch(c, 1u, cam, U, &ld, 1u, &L);
-    if (st != BH_OK) return st;
-    fill_args(c, 1u, cam, U, &ld, 1u, &L);
-    L.a.lens = 1u;
-    L.m.hits = out_hits;
-    return march_in_order(c, &L, cam, U, stream);
-}
-
+// ---- lens maps (include/bh_render.h; the shading of a record: bh_lens.hpp) and hit maps: the lens march also
+// stores where its surface rays ended ----------------------------------------------------------------------------
 int bh_render_lens(bh_ctx* c, const bh_camera_uniform* cam, const bh_uniforms* U, const bh_render_desc* d,
                    bh_lens_px* out_lens, void* stream) {
-    return render_lens(__func__, c, cam, U, d, out_lens, nullptr, stream);
+    Request r = pinhole(__func__, 1u, 1u, cam, U, d, 1u);
+    return render_request(c, with_lens(r, out_lens), stream);
 }
 
-// ---- hit maps (include/bh_render.h): the lens march also stores where its surface rays ended ----------------
 int bh_render_lens_hits(bh_ctx* c, const bh_camera_uniform* cam, const bh_uniforms* U, const bh_render_desc* d,
                         bh_lens_px* out_lens, float* out_hits, void* stream) {
-    if (!out_hits || (reinterpret_cast<uintptr_t>(out_hits) & 3u)) return bad_arg(__func__, __LINE__);
-    return render_lens(__func__, c, cam, U, d, out_lens, out_hits, stream);
+    Request r = pinhole(__func__, 1u, 1u, cam, U, d, 1u);
+    return render_request(c, with_hits(with_lens(r, out_lens), out_hits), stream);
 }
 
-// ---- ray maps (include/bh_render.h): the caller's direction per pixel, one origin per frame -----------------
-// What both ray-map paths refuse: fast math or, with a lens, a colour target in any of descs[0..n_frames), then
-// whatever ss_needs refuses in `plain` (the same frames, their dbg_* outputs cleared where the call allows them).
-// true: refused, and the error is set.
-static bool rays_refused(const char* fn, const bh_render_desc* descs, const bh_render_desc* plain, uint32_t n_frames,
-                         const bh_lens_px* out_lens) {
-    const char* why = nullptr;
-    for (uint32_t i = 0; i < n_frames && !why; ++i)
-        why = descs[i].math == BH_MATH_FAST ? "exact math (BH_MATH_EXACT): a ray map has no fast-math kernels"
-              : out_lens && (descs[i].out_col || descs[i].out_blackout) ? "no out_col or out_blackout (it writes only the lens)"
-                                                                       : nullptr;
-    if (!why) why = ss_needs(plain, n_frames);
-    if (why) g_last_error = std::string(fn) + ": a ray-map render needs " + why + ".";
-    return why != nullptr;
-}
-
-// bh_render_rays (out_lens null) and bh_render_lens_rays: the launch of bh_render / bh_render_ss / bh_render_lens of
-// this geometry from a camera that holds only the position -- the corner rays are not read by the ray-map kernels
-// -- with an order state and a repeated-frame key of its own (the map in the launch's record).
-static int render_rays(const char* fn, bh_ctx* c, const float* pos, const bh_uniforms* U, const bh_render_desc* d,
-                       const float* dirs, uint32_t ss, bh_lens_px* out_lens, void* stream) {
-    if (!c || !pos || !U || !d || !dirs || (reinterpret_cast<uintptr_t>(dirs) & 3u)) return bad_arg(fn, __LINE__);
-    if (bh::ss::log2_k(ss) > 3u) return bad_arg(fn, __LINE__);
-    if (!frame_shape_ok(d->width, d->height, ss)) return bad_arg(fn, __LINE__);
-    bh_render_desc one = *d;
-    // the dbg_* outputs are per ray: allowed where bh_render allows them
-    if (ss == 1u && !out_lens) one.dbg_n_rk = nullptr, one.dbg_fate = nullptr, one.dbg_steps = nullptr;
-    if (rays_refused(fn, d, &one, 1u, out_lens)) return BH_ERR_UNSUPPORTED;
-    bh_camera_uniform cam;
-    position_camera(&cam, pos);
-    bh_render_desc ld = *d;
-    if (out_lens) {  // as bh_render_lens: the lens in place of target 0, the format word not read
-        ld.format = BH_OUT_RGBA32F;
-        ld.out_col = out_lens;
-    }
-    Launch L;
-    const int e = check_launch(c, 1u, &cam, U, &ld, ss, &L);
-    if (e != BH_OK) return e;
-    fill_args(c, 1u, &cam, U, &ld, ss, &L);
-    L.a.lens = out_lens ? 1u : 0u;
-    L.m.dirs = dirs;
-    return march_in_order(c, &L, &cam, U, stream);
-}
-
+// ---- ray maps (include/bh_render.h): the caller's direction per pixel; world-space with one origin per frame, or
+// posed (bh_ray_pose): one camera-space map, one pose per camera, and with an origin map an origin per ray (the ORG
+// kernels form the photon-sphere centre per lane: FrameArgs::cps, filled as ever, is not read by them) ------------
 int bh_render_rays(bh_ctx* c, const float pos[3], const bh_uniforms* U, const bh_render_desc* d, const float* dirs_dev,
                    uint32_t ss, void* stream) {
-    return render_rays(__func__, c, pos, U, d, dirs_dev, ss, nullptr, stream);
+    return render_request(c, world_map(__func__, pos, U, d, dirs_dev, ss), stream);
 }
 
 int bh_render_lens_rays(bh_ctx* c, const float pos[3], const bh_uniforms* U, const bh_render_desc* d,
                         const float* dirs_dev, bh_lens_px* out_lens, void* stream) {
-    if (!out_lens || (reinterpret_cast<uintptr_t>(out_lens) & 7u)) return bad_arg(__func__, __LINE__);
-    return render_rays(__func__, c, pos, U, d, dirs_dev, 1u, out_lens, stream);
-}
-
-// ---- posed ray maps (include/bh_render.h, bh_ray_pose): one camera-space map, one pose per camera -----------
-// The maps of a posed launch, as its entry point has them.
-struct PosedMaps {
-    const float* dirs;               // the camera-space direction map
-    bool with_origins = false;       // the entry point takes an origin map: `origins` is required
-    const float* origins = nullptr;
-    float* out_hits = nullptr;       // with out_lens, one frame, no origin map (bh_render_lens_rays_posed_hits)
-};
-// bh_render_frames_rays (n_sub 1), bh_render_frames_shutter_rays (n_sub > 1) and bh_render_lens_rays_posed
-// (out_lens): render_rays' launch -- the ray-map order state, the map in the repeated-frame key -- of
-// n_frames * n_sub cameras as bh_render_frames(_ss) or bh_render_frames_shutter launches them: one FrameArgs entry
-// per camera, holding its position and, in c0..c2, its basis rows (march_slot's POSE form reads them there).
-// maps.with_origins (bh_render_frames_rays_origins, bh_render_lens_rays_origins; n_sub 1): the same launch by the ORG
-// kernels, which read each ray's origin from `origins` and form the photon-sphere centre per lane (FrameArgs::cps,
-// filled as ever, is not read by them).
-static int render_rays_posed(const char* fn, bh_ctx* c, uint32_t n_frames, uint32_t n_sub, const bh_ray_pose* poses,
-                             const bh_uniforms* U, const bh_render_desc* descs, const PosedMaps& maps, uint32_t ss,
-                             bh_lens_px* out_lens, void* stream) {
-    const float* const dirs = maps.dirs;
-    const float* const origins = maps.origins;
-    if (!c || !poses || !U || !descs || !dirs || (reinterpret_cast<uintptr_t>(dirs) & 3u)) return bad_arg(fn, __LINE__);
-    if (maps.with_origins && (!origins || (reinterpret_cast<uintptr_t>(origins) & 3u) || n_sub != 1u)) return bad_arg(fn, __LINE__);
-    const uint32_t ln = bh::shutter::log2_n(n_sub);
-    if (ln > bh::shutter::MAX_LOG2 || bh::ss::log2_k(ss) > 3u) return bad_arg(fn, __LINE__);
-    if (n_frames == 0 || (uint64_t)n_frames * n_sub > BH_MAX_FRAMES) return bad_arg(fn, __LINE__);
-    if (!frame_shape_ok(descs[0].width, descs[0].height, ss)) return bad_arg(fn, __LINE__);
-    const uint32_t n_cams = n_frames * n_sub;
-    std::vector<bh_render_desc> per_cam, plain;
-    std::vector<bh_camera_uniform> cams;
-    try {
-        per_cam.reserve(n_cams);
-        plain.assign(descs, descs + n_frames);
-        cams.resize(n_cams);
-    } catch (const std::bad_alloc&) {
-        return BH_ERR_OUT_OF_MEMORY;
-    }
-    // the dbg_* outputs are per ray: allowed where bh_render_frames allows them (ss == 1, no shutter)
-    if (ss == 1u && n_sub == 1u && !out_lens)
-        for (auto& e : plain) e.dbg_n_rk = nullptr, e.dbg_fate = nullptr, e.dbg_steps = nullptr;
-    if (rays_refused(fn, descs, plain.data(), n_frames, out_lens)) return BH_ERR_UNSUPPORTED;
-    for (uint32_t i = 0; i < n_cams; ++i) {
-        position_camera(&cams[i], poses[i].pos);
-        per_cam.push_back(descs[i / n_sub]);
-        if (out_lens) {  // as bh_render_lens: the lens in place of target 0, the format word not read
-            per_cam.back().format = BH_OUT_RGBA32F;
-            per_cam.back().out_col = out_lens;
-        }
-    }
-    Launch L;
-    const int e = check_launch(c, n_cams, cams.data(), U, per_cam.data(), ss, &L);
-    if (e != BH_OK) return e;
-    fill_args(c, n_cams, cams.data(), U, per_cam.data(), ss, &L);
-    bh::FrameArgs* fa = L.table.empty() ? L.a.frames : L.table.data();
-    for (uint32_t i = 0; i < n_cams; ++i)
-        for (int k = 0; k < 3; ++k) {
-            fa[i].c0[k] = poses[i].r[k]; fa[i].c1[k] = poses[i].u[k]; fa[i].c2[k] = poses[i].f[k];
-        }
-    for (int k = 0; k < 3; ++k) {  // camera 0's again in the argument itself (fill_args)
-        L.a.c0[k] = fa[0].c0[k]; L.a.c1[k] = fa[0].c1[k]; L.a.c2[k] = fa[0].c2[k];
-    }
-    L.a.lens = out_lens ? 1u : 0u;
-    if (ln != 0u) {
-        L.a.ss_out_width = descs[0].width;  // the shutter kernels index the output through it at every ss
-        L.m.shutter_log2 = ln;
-    }
-    L.m.dirs = dirs;
-    L.m.orgs = maps.with_origins ? origins : nullptr;
-    L.m.hits = maps.out_hits;
-    L.poses = poses;
-    return march_in_order(c, &L, cams.data(), U, stream);
+    Request r = world_map(__func__, pos, U, d, dirs_dev, 1u);
+    return render_request(c, with_lens(r, out_lens), stream);
 }
 
 int bh_render_frames_rays(bh_ctx* c, uint32_t n_frames, const bh_ray_pose* poses, const bh_uniforms* U,
                           const bh_render_desc* descs, const float* dirs_dev, uint32_t ss, void* stream) {
-    return render_rays_posed(__func__, c, n_frames, 1u, poses, U, descs, {dirs_dev}, ss, nullptr, stream);
+    return render_request(c, posed_map(__func__, n_frames, 1u, poses, U, descs, dirs_dev, ss), stream);
 }
 
 int bh_render_frames_shutter_rays(bh_ctx* c, uint32_t n_frames, uint32_t n_sub, const bh_ray_pose* poses,
                                   const bh_uniforms* U, const bh_render_desc* descs, const float* dirs_dev, uint32_t ss,
                                   void* stream) {
-    if (n_sub == 0u) return bad_arg(__func__, __LINE__);
-    return render_rays_posed(__func__, c, n_frames, n_sub, poses, U, descs, {dirs_dev}, ss, nullptr, stream);
+    return render_request(c, posed_map(__func__, n_frames, n_sub, poses, U, descs, dirs_dev, ss), stream);
 }
 
 int bh_render_lens_rays_posed(bh_ctx* c, const bh_ray_pose* pose, const bh_uniforms* U, const bh_render_desc* d,
                               const float* dirs_dev, bh_lens_px* out_lens, void* stream) {
-    if (!out_lens || (reinterpret_cast<uintptr_t>(out_lens) & 7u)) return bad_arg(__func__, __LINE__);
-    return render_rays_posed(__func__, c, 1u, 1u, pose, U, d, {dirs_dev}, 1u, out_lens, stream);
+    Request r = posed_map(__func__, 1u, 1u, pose, U, d, dirs_dev, 1u);
+    return render_request(c, with_lens(r, out_lens), stream);
 }
 
 int bh_render_lens_rays_posed_hits(bh_ctx* c, const bh_ray_pose* pose, const bh_uniforms* U, const bh_render_desc* d,
                                    const float* dirs_dev, bh_lens_px* out_lens, float* out_hits, void* stream) {
-    if (!out_lens || (reinterpret_cast<uintptr_t>(out_lens) & 7u)) return bad_arg(__func__, __LINE__);
-    if (!out_hits || (reinterpret_cast<uintptr_t>(out_hits) & 3u)) return bad_arg(__func__, __LINE__);
-    return render_rays_posed(__func__, c, 1u, 1u, pose, U, d, {dirs_dev, false, nullptr, out_hits}, 1u, out_lens,
-                             stream);
+    Request r = posed_map(__func__, 1u, 1u, pose, U, d, dirs_dev, 1u);
+    return render_request(c, with_hits(with_lens(r, out_lens), out_hits), stream);
 }
 
 int bh_render_frames_rays_origins(bh_ctx* c, uint32_t n_frames, const bh_ray_pose* poses, const bh_uniforms* U,
                                   const bh_render_desc* descs, const float* dirs_dev, const float* origins_dev,
                                   uint32_t ss, void* stream) {
-    return render_rays_posed(__func__, c, n_frames, 1u, poses, U, descs, {dirs_dev, true, origins_dev}, ss, nullptr,
-                             stream);
+    Request r = posed_map(__func__, n_frames, 1u, poses, U, descs, dirs_dev, ss);
+    return render_request(c, with_origins(r, origins_dev), stream);
 }
 
 int bh_render_lens_rays_origins(bh_ctx* c, const bh_ray_pose* pose, const bh_uniforms* U, const bh_render_desc* d,
                                 const float* dirs_dev, const float* origins_dev, bh_lens_px* out_lens, void* stream) {
-    if (!out_lens || (reinterpret_cast<uintptr_t>(out_lens) & 7u)) return bad_arg(__func__, __LINE__);
-    return render_rays_posed(__func__, c, 1u, 1u, pose, U, d, {dirs_dev, true, origins_dev}, 1u, out_lens, stream);
+    Request r = posed_map(__func__, 1u, 1u, pose, U, d, dirs_dev, 1u);
+    return render_request(c, with_lens(with_origins(r, origins_dev), out_lens), stream);
 }
 
 // bh_sky_create and bh_sky_create_mips: the texels, and with `mips` the chain built from them (a synchronous call)
@@ -1439,10 +1409,11 @@ int bh_render_frames_adaptive(bh_ctx* c, uint32_t n_frames, const bh_camera_unif
     R.n_heads = one_head ? 1u : bh::REFINE_HEADS;
     R.thr = bh::refine::threshold(d->format, ad->threshold);
     // pass 2: the virtual frame's launch, over the tiles the detect pass lists
+    const Request r = pinhole(fn, n_frames, 1u, cams, U, descs, ss);
     Launch L;
-    st = check_launch(c, n_frames, cams, U, descs, ss, &L);
+    st = check_launch(c, r, &L);
     if (st != BH_OK) return st;
-    fill_args(c, n_frames, cams, U, descs, ss, &L);
+    fill_args(c, r, &L);
     if (L.a.n_tiles == 0) return BH_OK;
     st = stage_frames(c, s, &L);
     if (st != BH_OK) return st;
