@@ -9,7 +9,7 @@ from ._abi import (BH_BLOOM_AUTO, BH_BLOOM_LITERAL, BH_FATE_BLACKOUT, BH_FATE_CA
                    BH_OUT_RGBA32F, BH_SCENE_DEFAULT, BH_SCENE_DISC, BH_SCENE_MARKERS, BH_SCHED_FLAG_STATIC_ORDER, BH_SCHED_FLAG_ISSUE_ORDER, BH_SCHED_FLAG_LATENCY, BH_SCHED_PAIR, BH_SCHED_PERSISTENT, BH_SCHED_TILE,
                    BH_LENS_BLACKOUT, BH_LENS_SURFACE, BYTES_PER_PIXEL,
                    BhError, load)
-from .scene import (MAX_ITERATIONS, Camera, CameraController, CameraUniform, Disc, FrameBatch, Partition, Presenter, Scene, Sky, Uniforms, bloom_check, bloom_plan_failures, clock_mhz, first_step_host, lens_shade_disc_host, lens_shade_host, load_sky, synthetic_disc, sky_mips_host,
+from .scene import (MAX_ITERATIONS, Camera, CameraController, CameraUniform, Disc, FrameBatch, Partition, Presenter, Scene, Sky, Uniforms, bloom_check, bloom_plan_failures, clock_mhz, first_step_host, lens_shade_disc_beamed_host, lens_shade_disc_host, lens_shade_host, load_sky, synthetic_disc, sky_mips_host,
                     partition_map, refine_cover_host, refine_mask_host, shard_tile_count, shutter_resolve_host, srgb_encode_table, ss_resolve_host, tiles_unpack_rgbm_partition,
                     synthetic_sky, tile_bytes, tiles_unpack, tiles_unpack_rgb, tiles_unpack_rgbm)
 from . import raymap

@@ -89,6 +89,10 @@ class bh_disc_desc(C.Structure):
                 ("spin", C.c_float), ("gain", C.c_float)]
 
 
+class bh_beam_desc(C.Structure):
+    _fields_ = [("arrivals", C.c_void_p), ("beam", C.c_float), ("sense", C.c_int32), ("distortion_power", C.c_float)]
+
+
 class bh_ray_pose(C.Structure):
     _fields_ = [("pos", C.c_float * 3), ("r", C.c_float * 3), ("u", C.c_float * 3), ("f", C.c_float * 3)]
 
@@ -183,6 +187,17 @@ SIGNATURES = {
     "bh_lens_shade_disc_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p,
                                           C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint32, C.c_uint32, C.c_float,
                                           C.c_uint32, C.c_float, C.c_float, C.c_void_p, C.c_void_p]),
+    "bh_march_lens_arrivals": (C.c_int, [C.c_void_p, C.POINTER(bh_camera_uniform), C.POINTER(bh_uniforms),
+                                          C.POINTER(bh_render_desc), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "bh_march_lens_rays_posed_arrivals": (C.c_int, [C.c_void_p, C.POINTER(bh_ray_pose), C.POINTER(bh_uniforms),
+                                                     C.POINTER(bh_render_desc), C.c_void_p, C.c_void_p, C.c_void_p,
+                                                     C.c_void_p, C.c_void_p]),
+    "bh_shade_lens_disc_beamed": (C.c_int, [C.c_void_p, C.POINTER(bh_shade_desc), C.POINTER(bh_disc_desc),
+                                            C.POINTER(bh_beam_desc), C.c_void_p]),
+    "bh_lens_shade_disc_beamed_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p,
+                                                 C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint32, C.c_uint32, C.c_float,
+                                                 C.c_uint32, C.c_float, C.c_float, C.c_void_p, C.c_void_p,
+                                                 C.c_void_p, C.c_float, C.c_int32, C.c_float]),
     "bh_shard_tile_count": (C.c_int64, [C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32]),
     "bh_tiles_unpack": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32,
                                   C.c_uint64, C.c_uint32, C.c_void_p]),

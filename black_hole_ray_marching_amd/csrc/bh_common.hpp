@@ -148,6 +148,7 @@ struct MarchLaunch {
     const float* dirs = nullptr;   // the ray-map families: the device map the rays' directions come from
     const float* orgs = nullptr;   // ... with an origin map: the rays' origins
     float* hits = nullptr;         // the hit-map family: where surface rays ended
+    float* arrivals = nullptr;     // the arrival-map family, beside hits: the direction they ended with
     uint32_t shutter_log2 = 0;     // the shutter forms: log2 of the cameras per output frame (a.n_frames counts cameras)
     // the plain family: a bh_schedule without its flags, and the persistent schedule's work counters and grid
     uint32_t schedule = BH_SCHED_TILE;
@@ -206,6 +207,13 @@ struct LensDiscArgs : LensShadeArgs {
     float rs;
     uint32_t scene_flags;
     float spin, gain;
+};
+
+// One bh_shade_lens_disc_beamed launch (bh_disc.hip): the same, the lens's arrival map beside its hit map and the
+// beam (include/bh_render.h, bh_beam_desc); sense as a float, +1 or -1.
+struct LensBeamArgs : LensDiscArgs {
+    const float* arrivals;
+    float beam, sense, dp;
 };
 
 constexpr uint32_t REFINE_HEADS = 8, REFINE_HEAD_STRIDE = 32, REFINE_HEAD0 = 32;  // 128-byte lines

@@ -509,7 +509,7 @@ int bh_first_step_host(const bh_camera_uniform* cam, const bh_uniforms* U, uint3
 // What a render entry point asks for, as its caller passed it and nothing derived.  Every entry point but the
 // adaptive pair fills one and calls render_request, which checks it in one order, whatever the form; the adaptive
 // render fills one for its second pass.
-enum : uint32_t { TAKES_DIRS = 1u, TAKES_ORGS = 2u, TAKES_LENS = 4u, TAKES_HITS = 8u };
+enum : uint32_t { TAKES_DIRS = 1u, TAKES_ORGS = 2u, TAKES_LENS = 4u, TAKES_HITS = 8u, TAKES_ARRIVALS = 16u };
 enum RaySource : uint32_t { PINHOLE, WORLD_MAP, POSED_MAP };
 struct Request {
     const char* fn;                            // the entry point, for messages
@@ -520,11 +520,12 @@ struct Request {
     const bh_ray_pose* poses = nullptr;        // POSED_MAP: a camera-space ray map's n_frames * n_sub poses
     const bh_uniforms* U = nullptr;
     const bh_render_desc* descs = nullptr;     // n_frames of them
-    uint32_t takes = 0u;                       // TAKES_*: which of the next four the entry point has (each required)
+    uint32_t takes = 0u;                       // TAKES_*: which of the next five the entry point has (each required)
     const float* dirs = nullptr;               // the ray map, 4-byte aligned
     const float* orgs = nullptr;               // the origin map, 4-byte aligned
     bh_lens_px* lens = nullptr;                // the lens, 8-byte aligned: written in place of target 0
     float* hits = nullptr;                     // the hit map, 4-byte aligned
+    float* arrivals = nullptr;                 // the arrival map, 4-byte aligned (with a hit map)
     uint32_t n_cams() const { return n_frames * n_sub; }
     const void* rays() const { return source == PINHOLE ? (const void*)cams : source == WORLD_MAP ? (const void*)pos : (const void*)poses; }
     // bh_render(_frames): nothing but cameras and descs
@@ -553,7 +554,8 @@ struct Launch {
 // and so does every pose of a posed launch (after a marker: a posed launch is never taken for an unposed one), and
 // an origin map's address beside the direction map's (after a marker of its own: a launch with origins is never
 // taken for one without).  A hit map's address enters the same way: the march's step counts do not depend on it, but
-// a launch that writes one is another launch of the frame, as one into another lens is not.
+// a launch that writes one is another launch of the frame, as one into another lens is not; and an arrival map's after
+// the hit map's.
 static uint64_t frame_cost_key(const bh_camera_uniform* cam, const bh_uniforms* U, const Launch& L) {
     const bh_render_desc* d = &L.d;
     uint64_t h = 1469598103934665603ull;
@@ -585,6 +587,11 @@ static uint64_t frame_cost_key(const bh_camera_uniform* cam, const bh_uniforms* 
         const uint32_t marker = 0x48495453u;  // "HITS"
         mix(&marker, sizeof marker);
         mix(&L.m.hits, sizeof L.m.hits);
+    }
+    if (L.m.arrivals) {
+        const uint32_t marker = 0x41525256u;  // "ARRV"
+        mix(&marker, sizeof marker);
+        mix(&L.m.arrivals, sizeof L.m.arrivals);
     }
     return h | 1u;  // never 0: 0 marks the fresh state's all-zero costs
 }
@@ -762,7 +769,7 @@ static void fill_args(const bh_ctx* c, const Request& r, Launch* L) {
     L->m.counters = c->counters;
     L->m.grid = d->math != BH_MATH_EXACT ? c->grid_fast : c->grid_exact;
     L->m.shutter_log2 = bh::shutter::log2_n(r.n_sub);
-    L->m.dirs = r.dirs; L->m.orgs = r.orgs; L->m.hits = r.hits;
+    L->m.dirs = r.dirs; L->m.orgs = r.orgs; L->m.hits = r.hits; L->m.arrivals = r.arrivals;
     L->poses = r.poses;
     if (n_frames > bh::BH_INLINE_FRAMES) L->table.resize(n_frames);
     bh::FrameArgs* fa = L->table.empty() ? a.frames : L->table.data();
@@ -851,7 +858,7 @@ static int learned_order(bh_ctx* c, Launch* L, const bh_camera_uniform* cam0, co
 // The build of a unit (build.py): the exact kernels in issue order or scheduled for latency, or the fast kernels.
 enum MarchBuild : uint32_t { BUILD_ISSUE, BUILD_LAT, BUILD_FAST, N_BUILDS };
 // The family of a launch: which source's kernels march it (bh_march.hpp).
-enum MarchFamily : uint32_t { FAMILY_PLAIN, FAMILY_RAYS, FAMILY_POSE, FAMILY_ORG, FAMILY_HITS, N_FAMILIES };
+enum MarchFamily : uint32_t { FAMILY_PLAIN, FAMILY_RAYS, FAMILY_POSE, FAMILY_ORG, FAMILY_HITS, FAMILY_ARRIVALS, N_FAMILIES };
 
 // [family][build]: the unit's launcher; null: no such unit (the entry points refuse fast math for ray maps and lenses).
 static constexpr MarchUnitFn* MARCH_UNITS[N_FAMILIES][N_BUILDS] = {
@@ -860,6 +867,7 @@ static constexpr MarchUnitFn* MARCH_UNITS[N_FAMILIES][N_BUILDS] = {
     /* FAMILY_POSE  */ {bh_launch_unit_exact_rays_pose, bh_launch_unit_exact_rays_pose_lat, nullptr},
     /* FAMILY_ORG   */ {bh_launch_unit_exact_rays_org, bh_launch_unit_exact_rays_org_lat, nullptr},
     /* FAMILY_HITS  */ {bh_launch_unit_exact_hits, bh_launch_unit_exact_hits_lat, nullptr},
+    /* FAMILY_ARRIVALS */ {bh_launch_unit_exact_arr, bh_launch_unit_exact_arr_lat, nullptr},  // the hit-map units' second
 };
 // the work-list march: the plain family's units, the scheduled build's in a unit of its own (bh_march_exact.hip)
 static constexpr RefineUnitFn* REFINE_UNITS[N_BUILDS] = {bh_launch_refine_unit_exact, bh_launch_refine_unit_exact_lat_refine,
@@ -871,11 +879,12 @@ static constexpr bool exact_units_filled() {
 }
 static_assert(exact_units_filled(), "every family has both exact builds");
 
-// The most specific form first: a launch with a hit map may also be posed and have a ray map (the hit-map kernels take
+// The most specific form first: a launch with an arrival map always has a hit map, one with a hit map may also be posed and have a ray map (the hit-map kernels take
 // both forms), one with an origin map is always posed, and a posed one always has a ray map -- so each test must come
 // before those of the fields it implies.
 static MarchFamily march_family(const Launch& L) {
-    return L.m.hits   ? FAMILY_HITS   // one frame's lens (bh_render_lens_hits; posed: L.m.dirs)
+    return L.m.arrivals ? FAMILY_ARRIVALS  // bh_march_lens_arrivals; posed: L.m.dirs
+           : L.m.hits ? FAMILY_HITS   // one frame's lens (bh_render_lens_hits; posed: L.m.dirs)
            : L.m.orgs ? FAMILY_ORG    // no shutter form (bh_render_frames_rays_origins and its lens)
            : L.poses  ? FAMILY_POSE   // a posed map; the shutter form when shutter_log2 != 0
            : L.m.dirs ? FAMILY_RAYS   // a world-space map (bh_render_rays)
@@ -956,7 +965,8 @@ static int render_request(bh_ctx* c, const Request& r, void* stream) {
     // 1. the pointers; a map or output the entry point takes is required, and aligned
     if (!c || !r.rays() || !r.U || !r.descs) return bad_arg(r.fn, __LINE__);
     if (((r.takes & TAKES_DIRS) && misaligned(r.dirs, 4u)) || ((r.takes & TAKES_ORGS) && misaligned(r.orgs, 4u)) ||
-        ((r.takes & TAKES_HITS) && misaligned(r.hits, 4u)) || ((r.takes & TAKES_LENS) && misaligned(r.lens, 8u)))
+        ((r.takes & TAKES_HITS) && misaligned(r.hits, 4u)) || ((r.takes & TAKES_ARRIVALS) && misaligned(r.arrivals, 4u)) ||
+        ((r.takes & TAKES_LENS) && misaligned(r.lens, 8u)))
         return bad_arg(r.fn, __LINE__);
     // 2. ss and n_sub; an origin map has no shutter form
     if (bh::ss::log2_k(r.ss) > 3u || bh::shutter::log2_n(r.n_sub) > bh::shutter::MAX_LOG2) return bad_arg(r.fn, __LINE__);
@@ -1028,6 +1038,7 @@ static Request posed_map(const char* fn, uint32_t n_frames, uint32_t n_sub, cons
 }
 static Request& with_lens(Request& r, bh_lens_px* out_lens) { r.takes |= TAKES_LENS; r.lens = out_lens; return r; }
 static Request& with_hits(Request& r, float* out_hits) { r.takes |= TAKES_HITS; r.hits = out_hits; return r; }
+static Request& with_arrivals(Request& r, float* out_arrivals) { r.takes |= TAKES_ARRIVALS; r.arrivals = out_arrivals; return r; }
 static Request& with_origins(Request& r, const float* origins) { r.takes |= TAKES_ORGS; r.orgs = origins; return r; }
 
 int bh_render_frames(bh_ctx* c, uint32_t n_frames, const bh_camera_uniform* cams, const bh_uniforms* U,
@@ -1074,6 +1085,13 @@ int bh_render_lens_hits(bh_ctx* c, const bh_camera_uniform* cam, const bh_unifor
     return render_request(c, with_hits(with_lens(r, out_lens), out_hits), stream);
 }
 
+// ... and with an arrival map beside it, the direction they ended with: the request of bh_render_lens_hits and one map
+int bh_march_lens_arrivals(bh_ctx* c, const bh_camera_uniform* cam, const bh_uniforms* U, const bh_render_desc* d,
+                            bh_lens_px* out_lens, float* out_hits, float* out_arrivals, void* stream) {
+    Request r = pinhole(__func__, 1u, 1u, cam, U, d, 1u);
+    return render_request(c, with_arrivals(with_hits(with_lens(r, out_lens), out_hits), out_arrivals), stream);
+}
+
 // ---- ray maps (include/bh_render.h): the caller's direction per pixel; world-space with one origin per frame, or
 // posed (bh_ray_pose): one camera-space map, one pose per camera, and with an origin map an origin per ray (the ORG
 // kernels form the photon-sphere centre per lane: FrameArgs::cps, filled as ever, is not read by them) ------------
@@ -1109,6 +1127,13 @@ int bh_render_lens_rays_posed_hits(bh_ctx* c, const bh_ray_pose* pose, const bh_
                                    const float* dirs_dev, bh_lens_px* out_lens, float* out_hits, void* stream) {
     Request r = posed_map(__func__, 1u, 1u, pose, U, d, dirs_dev, 1u);
     return render_request(c, with_hits(with_lens(r, out_lens), out_hits), stream);
+}
+
+int bh_march_lens_rays_posed_arrivals(bh_ctx* c, const bh_ray_pose* pose, const bh_uniforms* U, const bh_render_desc* d,
+                                       const float* dirs_dev, bh_lens_px* out_lens, float* out_hits, float* out_arrivals,
+                                       void* stream) {
+    Request r = posed_map(__func__, 1u, 1u, pose, U, d, dirs_dev, 1u);
+    return render_request(c, with_arrivals(with_hits(with_lens(r, out_lens), out_hits), out_arrivals), stream);
 }
 
 int bh_render_frames_rays_origins(bh_ctx* c, uint32_t n_frames, const bh_ray_pose* poses, const bh_uniforms* U,
@@ -1284,25 +1309,53 @@ int bh_disc_destroy(bh_disc* k) {
 }
 
 // bh_shade_lens's contract: validation and one kernel launch.
+// The checks and the arguments both disc shades share.
+static bool disc_desc_ok(const bh_ctx* c, const bh_shade_desc* d, const bh_disc_desc* dd) {
+    if (!shade_desc_ok(c, d) || !dd) return false;
+    if (!dd->hits || (reinterpret_cast<uintptr_t>(dd->hits) & 3u) || !dd->disc || dd->disc->ctx != c) return false;
+    if (dd->scene_flags & ~BH_SCENE_DEFAULT) return false;
+    return std::isfinite(dd->spin) && std::isfinite(dd->gain) && dd->gain >= 0.0f;
+}
+static void fill_disc_args(const bh_ctx* c, const bh_shade_desc* d, const bh_disc_desc* dd, bh::LensDiscArgs* a) {
+    fill_shade_args(c, d, a);
+    a->hits = dd->hits;
+    a->disc = dd->disc->texels;
+    a->n_phi = dd->disc->n_phi;
+    a->n_r = dd->disc->n_r;
+    a->rs = dd->rs;
+    a->scene_flags = dd->scene_flags;
+    a->spin = dd->spin;
+    a->gain = dd->gain;
+}
+
 int bh_shade_lens_disc(bh_ctx* c, const bh_shade_desc* d, const bh_disc_desc* dd, void* stream) {
-    if (!shade_desc_ok(c, d) || !dd) return bad_arg(__func__, __LINE__);
-    if (!dd->hits || (reinterpret_cast<uintptr_t>(dd->hits) & 3u) || !dd->disc || dd->disc->ctx != c) return bad_arg(__func__, __LINE__);
-    if (dd->scene_flags & ~BH_SCENE_DEFAULT) return bad_arg(__func__, __LINE__);
-    if (!std::isfinite(dd->spin) || !std::isfinite(dd->gain) || !(dd->gain >= 0.0f)) return bad_arg(__func__, __LINE__);
+    if (!disc_desc_ok(c, d, dd)) return bad_arg(__func__, __LINE__);
     bh::LensDiscArgs a;
-    fill_shade_args(c, d, &a);
-    a.hits = dd->hits;
-    a.disc = dd->disc->texels;
-    a.n_phi = dd->disc->n_phi;
-    a.n_r = dd->disc->n_r;
-    a.rs = dd->rs;
-    a.scene_flags = dd->scene_flags;
-    a.spin = dd->spin;
-    a.gain = dd->gain;
+    fill_disc_args(c, d, dd, &a);
     DeviceScope dev(c->device);
     if (dev.err != hipSuccess) return hip_fail(dev.err, "hipSetDevice");
     const int e = bh_launch_lens_shade_disc(a, d->ss, d->format, reinterpret_cast<hipStream_t>(stream));
     if (e != 0) return hip_fail((hipError_t)e, "disc shade kernel launch");
+    return BH_OK;
+}
+
+// ---- beamed disc shades (include/bh_render.h; the factor of a disc hit: bh_lens.hpp, beam_factor) ----------
+int bh_shade_lens_disc_beamed(bh_ctx* c, const bh_shade_desc* d, const bh_disc_desc* dd, const bh_beam_desc* bd,
+                              void* stream) {
+    if (!disc_desc_ok(c, d, dd) || !bd) return bad_arg(__func__, __LINE__);
+    if (!bd->arrivals || (reinterpret_cast<uintptr_t>(bd->arrivals) & 3u)) return bad_arg(__func__, __LINE__);
+    if ((bd->sense != 1 && bd->sense != -1) || !(bd->beam >= 0.0f && bd->beam <= 1.0f) || !std::isfinite(bd->distortion_power))
+        return bad_arg(__func__, __LINE__);
+    bh::LensBeamArgs a;
+    fill_disc_args(c, d, dd, &a);
+    a.arrivals = bd->arrivals;
+    a.beam = bd->beam;
+    a.sense = (float)bd->sense;
+    a.dp = bd->distortion_power;
+    DeviceScope dev(c->device);
+    if (dev.err != hipSuccess) return hip_fail(dev.err, "hipSetDevice");
+    const int e = bh_launch_lens_shade_disc_beamed(a, d->ss, d->format, reinterpret_cast<hipStream_t>(stream));
+    if (e != 0) return hip_fail((hipError_t)e, "beamed disc shade kernel launch");
     return BH_OK;
 }
 

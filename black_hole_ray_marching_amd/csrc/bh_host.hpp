@@ -210,7 +210,7 @@ BH_HIDDEN void free_bloom_scratch(bh_ctx::BloomScratch& b);  // bh_bloom_host.cp
 // `waves` pulling waves).  bh_host.cpp's tables say which unit serves which family and build.
 #define BH_MARCH_UNIT_NAMESPACES(X)                                                                  \
     X(exact) X(exact_lat) X(fast) X(exact_rays) X(exact_rays_lat) X(exact_rays_pose) X(exact_rays_pose_lat) \
-    X(exact_rays_org) X(exact_rays_org_lat) X(exact_hits) X(exact_hits_lat)
+    X(exact_rays_org) X(exact_rays_org_lat) X(exact_hits) X(exact_hits_lat) X(exact_arr) X(exact_arr_lat)
 #define BH_REFINE_UNIT_NAMESPACES(X) X(exact) X(exact_lat_refine) X(fast)
 using MarchUnitFn = int(const bh::MarchArgs& a, const bh::MarchLaunch& m, hipStream_t s);
 using RefineUnitFn = int(const bh::MarchArgs& a, const bh::RefineArgs& r, uint32_t waves, hipStream_t s);
@@ -228,6 +228,8 @@ BH_INTERNAL int bh_launch_lens_shade(const bh::LensShadeArgs& a, uint32_t ss, ui
 BH_INTERNAL int bh_launch_lens_shade_mip(const bh::LensMipArgs& a, uint32_t ss, uint32_t format, hipStream_t s);
 // the disc shade (bh_disc.hip): ss in {1, 2, 4, 8}
 BH_INTERNAL int bh_launch_lens_shade_disc(const bh::LensDiscArgs& a, uint32_t ss, uint32_t format, hipStream_t s);
+// the beamed disc shade (bh_disc.hip): ss in {1, 2, 4, 8}
+BH_INTERNAL int bh_launch_lens_shade_disc_beamed(const bh::LensBeamArgs& a, uint32_t ss, uint32_t format, hipStream_t s);
 BH_INTERNAL int bh_launch_sky_mips(const uint32_t* sky, uint32_t w0, uint32_t h0, const float* srgb_lut, void* chain,
                 hipStream_t s);
 BH_INTERNAL int bh_march_blocks_per_cu_exact(void);

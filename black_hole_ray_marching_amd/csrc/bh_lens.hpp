@@ -489,5 +489,82 @@ struct DiscLens {
     }
 };
 
+// ---- the beamed disc shade (include/bh_render.h, "Beamed disc shades"): the disc shade with a disc hit's colour
+// multiplied by the fourth power of the frequency ratio g of a Keplerian emitter, formed from the hit and the ray's
+// arrival there (the lens's arrival map).  bh_disc.hip and bh_lens_shade_disc_beamed_host run these; the header's
+// steps 6 to 8, op for op, as above.
+struct BeamView {
+    float beam;   // 0 .. 1
+    float sense;  // +1.0f or -1.0f
+    float dp;     // the uniforms' distortion_power
+};
+BH_LENS_HD float dot3(float ax, float ay, float az, float bx, float by, float bz) { return (ax * bx + ay * by) + az * bz; }
+// Step 3's test alone (disc_colour's first four lines, which the compiler merges with them): is p a disc hit, and rho.
+BH_LENS_HD bool disc_on(float x, float y, float z, float rs, float* rho_out) {
+    const float rho = sqrtf(x * x + z * z);
+    const float ri = 3.0f * rs, ro = 6.0f * rs;
+    const float sd = fmaxf(fmaxf(rho - ro, -(rho - ri)), fabsf(y) - 0.02f);
+    *rho_out = rho;
+    return sd < 0.001f;
+}
+// Steps 6 to 8 up to the factor f of a disc hit p = (x, y, z) with arrival d = (dx, dy, dz) and step 3's rho.
+BH_LENS_HD float beam_factor(float x, float y, float z, float dx, float dy, float dz, float rho, float rs, const BeamView& b) {
+    const float r2 = dot3(x, y, z, x, y, z), r = sqrtf(r2);                                       // 6.
+    const float lx = y * dz - z * dy, ly = z * dx - x * dz, lz = x * dy - y * dx;
+    const float h2 = dot3(lx, ly, lz, lx, ly, lz);
+    const float e2 = dot3(dx, dy, dz, dx, dy, dz) - ((b.dp * rs) * h2) / (r2 * r);
+    const float e = sqrtf(e2);
+    const float om = sqrtf((0.5f * rs) / ((rho * rho) * rho));                                    // 7.
+    const float q = 1.0f - (1.5f * rs) / rho;
+    const float den = 1.0f - (b.sense * om) * (ly / e);
+    float g = sqrtf(q) / den;
+    if (!((e2 > 0.0f) & (q > 0.0f) & (den > 0.0f) & (g < INFINITY))) g = 1.0f;
+    const float ge = 1.0f + b.beam * (g - 1.0f);                                                  // 8.
+    // finite: g > 1 needs a finite om, so rs > 0 and q < 1, and a positive fp32 den is 2^-24 at least -- g < 2^24
+    return (ge * ge) * (ge * ge);
+}
+// col of one record, its hit and its arrival: both 12-byte loads of a surface record of a scene with the disc issued
+// before either is used; the arrival enters the colour of a disc hit alone
+BH_LENS_HD Rgb shade_disc_beamed(float u, float v, const float* hit, const float* arr, const DiscView& d, const BeamView& b,
+                                 const SkyView& s, const float* lut) {
+    if (u != BH_LENS_SURFACE) return shade(u, v, s, lut);
+    if (!(d.scene_flags & BH_SCENE_DISC)) return {1.0f, 1.0f, 1.0f};
+    const float x = hit[0], y = hit[1], z = hit[2], dx = arr[0], dy = arr[1], dz = arr[2];
+    const Rgb c = disc_colour(x, y, z, d, lut);
+    float rho;
+    if (!disc_on(x, y, z, d.rs, &rho)) return c;  // a marker: disc_colour's (1, 1, 1)
+    const float f = beam_factor(x, y, z, dx, dy, dz, rho, d.rs, b);
+    return {c.r * f, c.g * f, c.b * f};
+}
+
+// The beamed disc shade's lens: DiscLens with the record's 12 bytes of the arrival map beside its hit's.
+struct BeamLens {
+    const bh_lens_px* lens;
+    const float* hits;
+    const float* arrivals;
+    uint32_t width;
+    SkyView s;
+    DiscView d;
+    BeamView b;
+    const float* lut;
+    struct Cursor {
+        const BeamLens& f;
+        size_t vw, at;  // the virtual frame's width and the record's index
+        BH_LENS_FI Rgb col() const {
+            const bh_lens_px r = load_px(f.lens + at);
+            return shade_disc_beamed(r.u, r.v, f.hits + at * 3u, f.arrivals + at * 3u, f.d, f.b, f.s, f.lut);
+        }
+        BH_LENS_FI Cursor right(int n) const { return {f, vw, at + (size_t)n}; }
+        BH_LENS_FI Cursor down(int n) const { return {f, vw, at + (size_t)n * vw}; }
+        template <int K>
+        static constexpr int barrier_at() { return K == 8 ? 4 : 0; }
+    };
+    template <int K, bool BO>
+    BH_LENS_FI Acc pixel(uint32_t x, uint32_t y) const {
+        const size_t vw = (size_t)width * K;
+        return scaled<K, BO>(sum_y<K, K, BO>(Cursor{*this, vw, (size_t)y * K * vw + (size_t)x * K}));
+    }
+};
+
 }  // namespace lens
 }  // namespace bh

@@ -6,7 +6,7 @@
 //   bh_march_rays.hip       the ray-map kernels alone
 //   bh_march_rays_pose.hip  the posed ray-map kernels, their shutter form
 //   bh_march_rays_org.hip   those with an origin map
-//   bh_march_hits.hip       the lens kernels with a hit map
+//   bh_march_hits.hip       the lens kernels with a hit map, and those with an arrival map beside it
 //       BH_FAST 0; built -ffp-contract=off, correctly-rounded f32 div/sqrt: same op sequence as the normative
 //       arithmetic of oracle/bh_oracle.c -> bit-exact parity.  Two rows each: the issue-order build, and with
 //       -DBH_LAT=1 the scheduled (latency) build -- a namespace of its own, the packed tail step (BH_TAIL_PACKED,
@@ -169,6 +169,17 @@ __attribute__((visibility("hidden"))) inline int launch_lens_hits(const MarchArg
     });
     return (int)hipGetLastError();
 }
+// The same with an arrival map beside the hit map (bh_march_lens_arrivals, bh_march_lens_rays_posed_arrivals).
+template <bool FOLD_NONE>
+__attribute__((visibility("hidden"))) inline int launch_lens_arrivals(const MarchArgs& a, const MarchLaunch& m, hipStream_t s) {
+    if (!m.hits || !m.arrivals || a.lens == 0u || a.n_frames != 1u) return (int)hipErrorInvalidValue;
+    with_scene_fold<FOLD_NONE>(a.scene_flags, [&](auto sf) {
+        constexpr uint32_t SF = decltype(sf)::value;
+        if (m.dirs) launch_tile_schedule(march_tile_rays_pose_lens_arrivals_kernel<SF>, a, s, m.dirs, m.hits, m.arrivals);
+        else launch_tile_schedule(march_tile_lens_arrivals_kernel<SF>, a, s, m.hits, m.arrivals);
+    });
+    return (int)hipGetLastError();
+}
 #endif
 // The shutter render's march (bh_render_shutter, n = 2^ln cameras per output frame; tile schedule): the same folds.
 template <bool FOLD_NONE>
@@ -209,8 +220,10 @@ __attribute__((visibility("hidden"))) inline int launch_refine(const MarchArgs& 
 // them from its list of namespaces.
 #define BH_PASTE_(a, b) a##b
 #define BH_PASTE(a, b) BH_PASTE_(a, b)
-#define BH_MARCH_UNIT(family, FOLD_NONE)                                                                              \
-    extern "C" __attribute__((visibility("hidden"))) int BH_PASTE(bh_launch_unit_, BH_NS)(                            \
+#define BH_MARCH_UNIT(family, FOLD_NONE) BH_MARCH_UNIT_AS(BH_NS, family, FOLD_NONE)
+// A unit that holds a second family exports that family's launcher under a name of its own (bh_march_hits.hip).
+#define BH_MARCH_UNIT_AS(name, family, FOLD_NONE)                                                                     \
+    extern "C" __attribute__((visibility("hidden"))) int BH_PASTE(bh_launch_unit_, name)(                             \
         const bh::MarchArgs& a, const bh::MarchLaunch& m, hipStream_t s) {                                            \
         return bh::BH_NS::family<FOLD_NONE>(a, m, s);                                                                 \
     }

@@ -143,10 +143,15 @@ __device__ __forceinline__ SlotHead slot_head(const MarchArgs& A, uint32_t slot,
 // a peeled step) and keeps st otherwise, the tie at i = 0 included -- whole states, ro with n_rk.  In the tail
 // (march_cycles) march_step_tail copies st, steps into the copy and copies back: a lane that ends before the update
 // gets its own state back.  The cycle fast-forward ends rays by the cap only.
+// ARR (with HIT only; the march_tile_lens_arrivals_kernel and march_tile_rays_pose_lens_arrivals_kernel forms): the
+// epilogue stores, beside the hit, 12 bytes of the lane's pixel in the arrival map `arrs` (the hit map's layout): st.rd,
+// unnormalised, where the fate is BH_FATE_SURFACE, (+0, +0, +0) otherwise.  The argument above is about whole
+// RayStates, so st.rd is the direction of the state whose ro the hit map holds; lens_record reads it already, so it
+// is live here in every lens form.
 // A form is a mask of these bits, one template argument of march_slot_body, march_slot, march_tile_wave and
 // shutter_workgroup; march_slot_body's static_asserts say which masks are forms.
 constexpr uint32_t F_SS = 1u, F_ITEM = 2u, F_LENS = 4u, F_SHUT = 8u, F_RAYS = 16u, F_POSE = 32u, F_ORG = 64u,
-                   F_HIT = 128u;
+                   F_HIT = 128u, F_ARR = 256u;
 constexpr bool form_first_step(uint32_t form) { return !BH_FAST && !(form & F_ORG); }
 struct ShutterLane { uint32_t px, py; bool valid, ok; };
 // The ORG form's prologue.  org_load: both 12-byte loads of a valid lane issued before either is used (one wait), and
@@ -190,9 +195,11 @@ __device__ __forceinline__ Frame slot_frame(const MarchArgs& a, const OrgRay& g)
 template <uint32_t FMT, uint32_t SF, uint32_t FORM>
 __device__ __forceinline__ void march_slot_body(const MarchArgs& A, const SlotHead& h, const float* lut,
                                                 uint32_t lane, ShutterLane* sl = nullptr, const float* dirs = nullptr,
-                                                const float* orgs = nullptr, [[maybe_unused]] float* hits = nullptr) {
+                                                const float* orgs = nullptr, [[maybe_unused]] float* hits = nullptr,
+                                                [[maybe_unused]] float* arrs = nullptr) {
     constexpr bool SS = FORM & F_SS, ITEM = FORM & F_ITEM, LENS = FORM & F_LENS, SHUT = FORM & F_SHUT,
-                   RAYS = FORM & F_RAYS, POSE = FORM & F_POSE, ORG = FORM & F_ORG, HIT = FORM & F_HIT;
+                   RAYS = FORM & F_RAYS, POSE = FORM & F_POSE, ORG = FORM & F_ORG, HIT = FORM & F_HIT,
+                   ARR = FORM & F_ARR;
     static_assert(SS || !ITEM, "work items are supersampled tiles");
     static_assert(!LENS || (!SS && !BH_FAST), "a lens is one record per ray, in exact math");
     static_assert(!SHUT || (!SS && !ITEM && !LENS), "a shutter wave takes its ss from the argument");
@@ -201,6 +208,7 @@ __device__ __forceinline__ void march_slot_body(const MarchArgs& A, const SlotHe
     static_assert(!POSE || RAYS, "a pose turns a ray map");
     static_assert(!ORG || (RAYS && POSE && !SHUT && !ITEM), "an origin map goes with a posed ray map, outside the shutter form");
     static_assert(!HIT || (LENS && !ORG), "a hit map goes with a lens, pinhole or posed ray map, without an origin map");
+    static_assert(!ARR || HIT, "an arrival map goes with a hit map");
     const uint32_t fi = h.fi, t = h.t, tx = h.tx, ty = h.ty;
     MarchArgs a = A;
     select_camera(a, h.cam);
@@ -318,6 +326,13 @@ __device__ __forceinline__ void march_slot_body(const MarchArgs& A, const SlotHe
                 q[0] = on ? st.ro.x : 0.0f;
                 q[1] = on ? st.ro.y : 0.0f;
                 q[2] = on ? st.ro.z : 0.0f;
+                if constexpr (ARR) {
+                    // the arrival map (the hit map's layout): the direction that ray ended with, +0 for any other
+                    float* w = arrs + ((size_t)py * a.width + px) * 3u;
+                    w[0] = on ? st.rd.x : 0.0f;
+                    w[1] = on ? st.rd.y : 0.0f;
+                    w[2] = on ? st.rd.z : 0.0f;
+                }
             }
         } else
 #endif
@@ -374,7 +389,7 @@ __device__ __forceinline__ void clock_end(unsigned long long* acc, const ClockSt
 }
 
 // One wave of the tile schedule: its dispatch slot (the grid covers every slot, WG_WAVES waves per workgroup),
-// marched in march_slot_body's form FORM (of F_SS, F_LENS, F_RAYS, F_POSE, F_ORG, F_HIT), between the clock probe's two
+// marched in march_slot_body's form FORM (of F_SS, F_LENS, F_RAYS, F_POSE, F_ORG, F_HIT, F_ARR), between the clock probe's two
 // readings.
 // The wave's start is one trip to memory deep where it can be: the table copy's loads (lut != null: 16 bytes of
 // each table per lane, srgb_fetch) are issued first and awaited last, and the slot's own chain -- kernel argument,
@@ -384,7 +399,8 @@ __device__ __forceinline__ void clock_end(unsigned long long* acc, const ClockSt
 // multiply: DESIGN.md §5 item 32.)
 template <uint32_t FMT, uint32_t SF, uint32_t FORM>
 __device__ __forceinline__ void march_tile_wave(const MarchArgs& A, float* lut, const float* dirs = nullptr,
-                                                const float* orgs = nullptr, float* hits = nullptr) {
+                                                const float* orgs = nullptr, float* hits = nullptr,
+                                                float* arrs = nullptr) {
     static_assert(WG_WAVES == 1u, "the table copy is one wave's: 64 lanes x 16 bytes per table");
     static_assert(!(FORM & (F_ITEM | F_SHUT)), "work items and shutter waves have kernels of their own");
     constexpr bool LENS = FORM & F_LENS;
@@ -407,7 +423,7 @@ __device__ __forceinline__ void march_tile_wave(const MarchArgs& A, float* lut, 
     const bool probe = A.clk && ((slot + (slot >> 8)) & A.clk_mask) == 0u;
     ClockStart c0{0u, 0u};
     if (probe) c0 = clock_start();
-    if (h.ok) march_slot_body<FMT, SF, FORM>(A, h, lut, threadIdx.x & 63u, nullptr, dirs, orgs, hits);
+    if (h.ok) march_slot_body<FMT, SF, FORM>(A, h, lut, threadIdx.x & 63u, nullptr, dirs, orgs, hits, arrs);
     if (probe) clock_end(A.clk, c0);
 }
 
@@ -554,6 +570,18 @@ __global__ void __launch_bounds__(64 * WG_WAVES) march_tile_rays_pose_lens_hits_
     march_tile_wave<BH_OUT_RGBA32F, SF, F_LENS | F_RAYS | F_POSE | F_HIT>(A, nullptr, dirs, nullptr, hits);
 }
 
+// The same two with an arrival map (bh_march_lens_arrivals, bh_march_lens_rays_posed_arrivals): march_slot_body's ARR
+// switch -- the epilogue's third store -- and the map as the last argument, after `hits`.
+template <uint32_t SF>
+__global__ void __launch_bounds__(64 * WG_WAVES) march_tile_lens_arrivals_kernel(MarchArgs A, float* hits, float* arrs) {
+    march_tile_wave<BH_OUT_RGBA32F, SF, F_LENS | F_HIT | F_ARR>(A, nullptr, nullptr, nullptr, hits, arrs);
+}
+template <uint32_t SF>
+__global__ void __launch_bounds__(64 * WG_WAVES) march_tile_rays_pose_lens_arrivals_kernel(MarchArgs A, const float* dirs, float* hits,
+                                                                                          float* arrs) {
+    march_tile_wave<BH_OUT_RGBA32F, SF, F_LENS | F_RAYS | F_POSE | F_HIT | F_ARR>(A, nullptr, dirs, nullptr, hits, arrs);
+}
+
 // The shutter form over a posed ray map (bh_render_frames_shutter_rays): march_tile_shutter_kernel's shell with the
 // map as the second argument, and shutter_workgroup with the F_RAYS and F_POSE bits -- the n waves of a workgroup read
 // the same 12 bytes per pixel and differ in their FrameArgs' pose.
@@ -629,8 +657,8 @@ __global__ void __launch_bounds__(64 * WG_WAVES) march_refine_kernel(MarchArgs A
 // out_col the lens).  (A persistent form -- resident
 // waves claiming slots in order from one device-scope counter -- measured 2.5x slower: a returning
 // atomic on one word is serialised across the 8 XCDs at ~85 M claims/s)
-// The ray-map forms take the same grid; `maps`: their direction map, then their origin map or their hit map, the
-// kernel's arguments after the first.
+// The ray-map forms take the same grid; `maps`: their direction map, then their origin map or their hit map and their
+// arrival map, the kernel's arguments after the first.
 template <class K, class... Maps>
 inline void launch_tile_schedule(K kernel, const MarchArgs& a, hipStream_t s, Maps... maps) {
     const uint32_t waves = a.n_tiles * a.n_frames;

@@ -215,24 +215,53 @@ int bh_lens_shade_host(const bh_lens_px* lens, uint32_t width, uint32_t height, 
     return BH_OK;
 }
 
-// bh_shade_lens_disc on the host: the disc shade's lens (bh_lens.hpp, DiscLens) through the same loop.
-int bh_lens_shade_disc_host(const bh_lens_px* lens, const float* hits, uint32_t width, uint32_t height, uint32_t ss,
-                            const uint8_t* sky, uint32_t sky_w, uint32_t sky_h, const uint8_t* disc, uint32_t n_phi,
-                            uint32_t n_r, float rs, uint32_t scene_flags, float spin, float gain, float* out_col,
-                            float* out_bo) {
-    if (!lens || !hits || !sky || !disc || !out_col || bh::ss::log2_k(ss) > 3u || !frame_shape_ok(width, height, ss)) return bad_arg(__func__, __LINE__);
-    if (sky_w == 0 || sky_h == 0 || sky_w > 32768u || sky_h > 32768u) return bad_arg(__func__, __LINE__);
-    if (n_phi == 0 || n_r == 0 || n_phi > 32768u || n_r > 32768u || (scene_flags & ~BH_SCENE_DEFAULT)) return bad_arg(__func__, __LINE__);
-    if (!std::isfinite(spin) || !std::isfinite(gain) || !(gain >= 0.0f)) return bad_arg(__func__, __LINE__);
-    HostSky k, dk;  // the disc's texels travel as a sky's do
-    if (!host_sky(sky, sky_w, sky_h, &k) || !host_sky(disc, n_phi, n_r, &dk)) return BH_ERR_OUT_OF_MEMORY;
-    const bh::lens::DiscLens l{lens, hits, width, k.view, {dk.texels.data(), n_phi, n_r, rs, scene_flags, spin, gain}, k.lut};
+// What both disc mirrors refuse, and their loop over either lens (bh_lens.hpp, DiscLens and BeamLens).
+static bool disc_host_ok(const bh_lens_px* lens, const float* hits, uint32_t width, uint32_t height, uint32_t ss,
+                         const uint8_t* sky, uint32_t sky_w, uint32_t sky_h, const uint8_t* disc, uint32_t n_phi,
+                         uint32_t n_r, uint32_t scene_flags, float spin, float gain, const float* out_col) {
+    if (!lens || !hits || !sky || !disc || !out_col || bh::ss::log2_k(ss) > 3u || !frame_shape_ok(width, height, ss)) return false;
+    if (sky_w == 0 || sky_h == 0 || sky_w > 32768u || sky_h > 32768u) return false;
+    if (n_phi == 0 || n_r == 0 || n_phi > 32768u || n_r > 32768u || (scene_flags & ~BH_SCENE_DEFAULT)) return false;
+    return std::isfinite(spin) && std::isfinite(gain) && gain >= 0.0f;
+}
+extern "C++" template <class Lens>
+static void lens_shade_any(const Lens& l, uint32_t width, uint32_t height, uint32_t ss, float* out_col, float* out_bo) {
     switch (ss) {
         case 1u: lens_shade_rows<1>(l, width, height, out_col, out_bo); break;
         case 2u: lens_shade_rows<2>(l, width, height, out_col, out_bo); break;
         case 4u: lens_shade_rows<4>(l, width, height, out_col, out_bo); break;
         default: lens_shade_rows<8>(l, width, height, out_col, out_bo); break;
     }
+}
+
+// bh_shade_lens_disc on the host: the disc shade's lens (bh_lens.hpp, DiscLens) through the same loop.
+int bh_lens_shade_disc_host(const bh_lens_px* lens, const float* hits, uint32_t width, uint32_t height, uint32_t ss,
+                            const uint8_t* sky, uint32_t sky_w, uint32_t sky_h, const uint8_t* disc, uint32_t n_phi,
+                            uint32_t n_r, float rs, uint32_t scene_flags, float spin, float gain, float* out_col,
+                            float* out_bo) {
+    if (!disc_host_ok(lens, hits, width, height, ss, sky, sky_w, sky_h, disc, n_phi, n_r, scene_flags, spin, gain, out_col))
+        return bad_arg(__func__, __LINE__);
+    HostSky k, dk;  // the disc's texels travel as a sky's do
+    if (!host_sky(sky, sky_w, sky_h, &k) || !host_sky(disc, n_phi, n_r, &dk)) return BH_ERR_OUT_OF_MEMORY;
+    const bh::lens::DiscLens l{lens, hits, width, k.view, {dk.texels.data(), n_phi, n_r, rs, scene_flags, spin, gain}, k.lut};
+    lens_shade_any(l, width, height, ss, out_col, out_bo);
+    return BH_OK;
+}
+
+// bh_shade_lens_disc_beamed on the host: BeamLens through the same loop.
+int bh_lens_shade_disc_beamed_host(const bh_lens_px* lens, const float* hits, uint32_t width, uint32_t height, uint32_t ss,
+                                   const uint8_t* sky, uint32_t sky_w, uint32_t sky_h, const uint8_t* disc, uint32_t n_phi,
+                                   uint32_t n_r, float rs, uint32_t scene_flags, float spin, float gain, float* out_col,
+                                   float* out_bo, const float* arrivals, float beam, int32_t sense, float distortion_power) {
+    if (!disc_host_ok(lens, hits, width, height, ss, sky, sky_w, sky_h, disc, n_phi, n_r, scene_flags, spin, gain, out_col))
+        return bad_arg(__func__, __LINE__);
+    if (!arrivals || (sense != 1 && sense != -1) || !(beam >= 0.0f && beam <= 1.0f) || !std::isfinite(distortion_power))
+        return bad_arg(__func__, __LINE__);
+    HostSky k, dk;
+    if (!host_sky(sky, sky_w, sky_h, &k) || !host_sky(disc, n_phi, n_r, &dk)) return BH_ERR_OUT_OF_MEMORY;
+    const bh::lens::BeamLens l{lens, hits, arrivals, width, k.view, {dk.texels.data(), n_phi, n_r, rs, scene_flags, spin, gain},
+                               {beam, (float)sense, distortion_power}, k.lut};
+    lens_shade_any(l, width, height, ss, out_col, out_bo);
     return BH_OK;
 }
 

@@ -303,6 +303,34 @@ def lens_shade_disc_host(lens: np.ndarray, hits: np.ndarray, sky: np.ndarray, di
     return col, bo
 
 
+def lens_shade_disc_beamed_host(lens: np.ndarray, hits: np.ndarray, arrivals: np.ndarray, sky: np.ndarray,
+                                disc: np.ndarray, *, rs: float, scene_flags: int = BH_SCENE_DEFAULT, spin: float = 0.0,
+                                gain: float = 1.0, ss: int = 1, beam: float = 1.0, sense: int = 1,
+                                distortion_power: float = 1.0):
+    """bh_lens_shade_disc_beamed_host (host only): what the beamed disc shade kernel runs, on the CPU.
+    lens_shade_disc_host's arguments and `arrivals`: (ss*H, ss*W, 3) float32, the lens's arrival map -> (col,
+    blackout_col), fp32 (H, W, 4)."""
+    ln = np.ascontiguousarray(lens, np.float32)
+    ht = np.ascontiguousarray(hits, np.float32)
+    ar = np.ascontiguousarray(arrivals, np.float32)
+    s = np.ascontiguousarray(sky, np.uint8)
+    dc = np.ascontiguousarray(disc, np.uint8)
+    k = _ss_arg(ss)
+    if ln.ndim != 3 or ln.shape[2] != 2 or ht.shape != ln.shape[:2] + (3,) or ar.shape != ht.shape:
+        raise BhError(_abi.BH_ERR_INVALID_ARG, "lens_shade_disc_beamed_host: lens must be (ss*H, ss*W, 2), hits and arrivals (ss*H, ss*W, 3)")
+    if s.ndim != 3 or s.shape[2] != 4 or dc.ndim != 3 or dc.shape[2] != 4:
+        raise BhError(_abi.BH_ERR_INVALID_ARG, "lens_shade_disc_beamed_host: sky must be (h, w, 4), disc (n_r, n_phi, 4)")
+    if k == 0 or ln.shape[0] % k or ln.shape[1] % k:
+        raise BhError(_abi.BH_ERR_INVALID_ARG, "lens_shade_disc_beamed_host: the lens sides must be multiples of ss")
+    h, w = ln.shape[0] // k, ln.shape[1] // k
+    col, bo = np.empty((h, w, 4), np.float32), np.empty((h, w, 4), np.float32)
+    check(load().bh_lens_shade_disc_beamed_host(ln.ctypes.data, ht.ctypes.data, w, h, k, s.ctypes.data, s.shape[1],
+                                                s.shape[0], dc.ctypes.data, dc.shape[1], dc.shape[0], rs, scene_flags, spin,
+                                                gain, col.ctypes.data, bo.ctypes.data, ar.ctypes.data, beam, sense,
+                                                distortion_power), "bh_lens_shade_disc_beamed_host")
+    return col, bo
+
+
 def synthetic_disc(n_phi: int = 1024, n_r: int = 128, seed: int = 0x0D15C) -> np.ndarray:
     """A deterministic disc texture for Disc(): (n_r, n_phi, 4) uint8 RGBA8 sRGB.  A radial temperature ramp --
     white-hot and bright at the inner edge (row 0), dim red at the outer edge -- multiplied by seeded azimuthal
@@ -765,7 +793,7 @@ class Scene:
               "bh_render_frames_shutter_rays")
 
     def render_lens(self, lens, *, width: int | None = None, height: int | None = None, schedule: int = 0,
-                    stream=None, dirs=None, pos=None, pose=None, origins=None, hits=None) -> None:
+                    stream=None, dirs=None, pos=None, pose=None, origins=None, hits=None, arrivals=None) -> None:
         """bh_render_lens: march this scene's camera once into `lens`, a device buffer of height x width records
         (u, v) of 8 bytes (e.g. a float32 tensor (H, W, 2)) -- the view, without any sky.  Exact math, whatever
         the scene's math mode.  Shade it with shade(), as often and with as many skies as wanted.
@@ -775,7 +803,9 @@ class Scene:
         origin map of `dirs`' shape) beside the pose, bh_render_lens_rays_origins.
         `hits` (a float32 device tensor (height, width, 3)): bh_render_lens_hits, or with `dirs` bh_render_lens_rays_posed_hits
         (`pose` defaults to the unit axes at the scene camera's position or at `pos`) -- the march also stores where
-        each surface ray ended, for shade(hits=, disc=).  Not with `origins`."""
+        each surface ray ended, for shade(hits=, disc=).  Not with `origins`.
+        `arrivals` (beside `hits`, of its shape): bh_march_lens_arrivals or bh_march_lens_rays_posed_arrivals -- the
+        march also stores the direction each surface ray ended with, for shade(arrivals=)."""
         d = _abi.bh_render_desc()
         d.width, d.height = width or self.width, height or self.height
         d.max_iters, d.scene_flags = self.max_iters, self.scene_flags
@@ -783,6 +813,11 @@ class Scene:
         if lens is None:
             raise BhError(_abi.BH_ERR_INVALID_ARG, "render_lens: lens is required")
         _check_size(lens, d.width * d.height * 8, "lens", "render_lens")
+        if arrivals is not None:
+            if hits is None:
+                raise BhError(_abi.BH_ERR_INVALID_ARG, "render_lens: an arrival map goes with a hit map (give hits)")
+            _check_dirs(arrivals, d.height, d.width, "render_lens", "arrivals")
+        arr = () if arrivals is None else (_ptr(arrivals),)
         if hits is not None:
             if origins is not None:
                 raise BhError(_abi.BH_ERR_INVALID_ARG, "render_lens: a hit map is not built with an origin map")
@@ -790,9 +825,9 @@ class Scene:
             if dirs is None:
                 if pos is not None or pose is not None:
                     raise BhError(_abi.BH_ERR_INVALID_ARG, "render_lens: pos and pose belong to a ray-map render (give dirs)")
-                check(self.lib.bh_render_lens_hits(self._ctx, C.byref(self.camera_uniform.c), C.byref(self.uniforms.to_c()),
-                                                   C.byref(d), _ptr(lens), _ptr(hits), _stream_handle(stream)),
-                      "bh_render_lens_hits")
+                name = "bh_march_lens_arrivals" if arr else "bh_render_lens_hits"
+                check(getattr(self.lib, name)(self._ctx, C.byref(self.camera_uniform.c), C.byref(self.uniforms.to_c()),
+                                              C.byref(d), _ptr(lens), _ptr(hits), *arr, _stream_handle(stream)), name)
                 return
             if pose is not None and pos is not None:
                 raise BhError(_abi.BH_ERR_INVALID_ARG, "render_lens: give pos or pose, not both (a pose holds its position)")
@@ -801,9 +836,9 @@ class Scene:
                 from . import raymap
                 pose = raymap.pose(self.camera_uniform.pos if pos is None else pos)
             ps = _poses_arg([pose], 1, "render_lens")
-            check(self.lib.bh_render_lens_rays_posed_hits(self._ctx, ps, C.byref(self.uniforms.to_c()), C.byref(d),
-                                                          _ptr(dirs), _ptr(lens), _ptr(hits), _stream_handle(stream)),
-                  "bh_render_lens_rays_posed_hits")
+            name = "bh_march_lens_rays_posed_arrivals" if arr else "bh_render_lens_rays_posed_hits"
+            check(getattr(self.lib, name)(self._ctx, ps, C.byref(self.uniforms.to_c()), C.byref(d), _ptr(dirs),
+                                          _ptr(lens), _ptr(hits), *arr, _stream_handle(stream)), name)
             return
         if origins is not None and pose is None:
             raise BhError(_abi.BH_ERR_INVALID_ARG, "render_lens: origins are in camera space and need a pose: give "
@@ -837,7 +872,8 @@ class Scene:
     def shade(self, lens, output, blackout_output=None, *, fmt: int = BH_OUT_RGBA32F, sky: "Sky | None" = None,
               ss: int = 1, width: int | None = None, height: int | None = None, stream=None, mip: bool = False,
               hits=None, disc: "Disc | None" = None, spin: float = 0.0, gain: float = 1.0, rs: float | None = None,
-              scene_flags: int | None = None) -> None:
+              scene_flags: int | None = None, arrivals=None, beam: float = 1.0, sense: int = 1,
+              distortion_power: float | None = None) -> None:
         """bh_shade_lens: `lens` (render_lens of ss*width x ss*height) and a sky -> the bytes render() -- with
         ss > 1, render(ss=ss) -- writes for that view with that sky.  `sky`: a Sky of this scene, or None for the
         scene's own.  Asynchronous on `stream`; allocates nothing (capturable from the first call).
@@ -846,7 +882,11 @@ class Scene:
         hits= and disc= (render_lens(hits=) of the same lens and a Disc of this scene): bh_shade_lens_disc, the surface
         records that lie on the accretion disc coloured from the disc texture, turned by `spin` turns of its inner
         edge (Keplerian: slower further out) and scaled by `gain`; `rs` and `scene_flags` default to the scene's, which
-        the lens was marched with.  Not with mip=True."""
+        the lens was marched with.  Not with mip=True.
+        arrivals= beside them (render_lens(hits=, arrivals=) of the same lens): bh_shade_lens_disc_beamed, each disc hit's
+        colour scaled by g^4 -- g the Doppler and redshift factor of a Keplerian disc turning in `sense` (+1: the way
+        a growing `spin` carries the texture), blended in by `beam` in 0 .. 1; `distortion_power` defaults to the
+        scene's."""
         k = _ss_arg(ss)
         d = _abi.bh_shade_desc()
         d.width, d.height, d.ss, d.format = width or self.width, height or self.height, k, fmt
@@ -858,6 +898,8 @@ class Scene:
         _check_size(blackout_output, need, "blackout_output", "shade")
         d.lens, d.sky = _ptr(lens), None if sky is None else sky.handle
         d.out_col, d.out_blackout = _ptr(output), _ptr(blackout_output)
+        if arrivals is not None and (hits is None or disc is None):
+            raise BhError(_abi.BH_ERR_INVALID_ARG, "shade: a beamed disc shade takes hits=, disc= and arrivals= together")
         if hits is not None or disc is not None:
             if hits is None or disc is None or mip:
                 raise BhError(_abi.BH_ERR_INVALID_ARG, "shade: a disc shade takes hits= and disc= together, without mip")
@@ -869,6 +911,16 @@ class Scene:
             dd.rs = self.uniforms.rs if rs is None else rs
             dd.scene_flags = self.scene_flags if scene_flags is None else scene_flags
             dd.spin, dd.gain = spin, gain
+            if arrivals is not None:
+                _check_dirs(arrivals, d.height * k, d.width * k, "shade", "arrivals")
+                if sense not in (1, -1):
+                    raise BhError(_abi.BH_ERR_INVALID_ARG, "shade: sense must be +1 or -1")
+                bd = _abi.bh_beam_desc()
+                bd.arrivals, bd.beam, bd.sense = _ptr(arrivals), beam, sense
+                bd.distortion_power = self.uniforms.distortion_power if distortion_power is None else distortion_power
+                check(self.lib.bh_shade_lens_disc_beamed(self._ctx, C.byref(d), C.byref(dd), C.byref(bd),
+                                                         _stream_handle(stream)), "bh_shade_lens_disc_beamed")
+                return
             check(self.lib.bh_shade_lens_disc(self._ctx, C.byref(d), C.byref(dd), _stream_handle(stream)),
                   "bh_shade_lens_disc")
             return

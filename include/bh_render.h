@@ -653,6 +653,28 @@ int bh_render_lens_rays_posed_hits(bh_ctx* ctx, const bh_ray_pose* pose, const b
                                    const bh_render_desc* desc, const float* dirs_dev, bh_lens_px* out_lens,
                                    float* out_hits, void* hip_stream);
 
+/* Arrival maps: the lens march also stores the direction its surface rays ended with.  An arrival map (normative) is a
+ * device array with a hit map's layout: height x width x 3 fp32 values, row-major, 12 bytes per pixel, 4-byte aligned.
+ * For a ray of fate BH_FATE_SURFACE the three values are the ray's final rd: the unnormalised direction of the state
+ * the loop's SDF test saw -- the state whose ro the hit map holds -- before that iteration's RK update, bit for bit.
+ * For every other fate they are (+0, +0, +0).
+ * bh_march_lens_arrivals: bh_render_lens_hits, which also writes out_arrivals -- the same lens bytes and hit bytes, the
+ * same refusals in the same order, order state, repeated-frame key (which the arrival map's address enters after the
+ * hit map's) and graph contract.  bh_march_lens_rays_posed_arrivals: bh_render_lens_rays_posed_hits likewise.
+ * BH_ERR_INVALID_ARG for a NULL or misaligned out_arrivals, with the other pointers' check; every bh_last_error()
+ * sentence starts with the function's name.  A refused call launches nothing and writes nothing.  Not built, as for hit
+ * maps: arrival maps with an origin map, with ss resolved in the march, in fast math, in the tiled layouts, with shards
+ * or partitions.  Additive: BH_ABI_VERSION unchanged, callers probe for the symbols.  The names: bh_render_* are the
+ * eighteen entry points whose refusals the census records (tests/test_gpu_refusals.py, which holds that list closed);
+ * these two are the _hits requests with one more map, named for what they do -- the lens march -- and their refusals
+ * are tested beside them (tests/test_gpu_beam.py). */
+int bh_march_lens_arrivals(bh_ctx* ctx, const bh_camera_uniform* camera, const bh_uniforms* uniforms,
+                            const bh_render_desc* desc, bh_lens_px* out_lens, float* out_hits, float* out_arrivals,
+                            void* hip_stream);
+int bh_march_lens_rays_posed_arrivals(bh_ctx* ctx, const bh_ray_pose* pose, const bh_uniforms* uniforms,
+                                       const bh_render_desc* desc, const float* dirs_dev, bh_lens_px* out_lens,
+                                       float* out_hits, float* out_arrivals, void* hip_stream);
+
 /* Disc shades: bh_shade_lens with the surface records looked up in a disc texture (not in the reference).  The disc
  * is an immutable object beside bh_sky: n_phi x n_r RGBA8-sRGB texels (n_phi * n_r * 4 bytes, each side 1..32768),
  * x running around the disc and y from its inner edge to its outer edge, decoded through the 256-entry table the sky
@@ -702,6 +724,50 @@ int bh_lens_shade_disc_host(const bh_lens_px* lens, const float* hits, uint32_t 
                             const uint8_t* disc_rgba8, uint32_t n_phi, uint32_t n_r,
                             float rs, uint32_t scene_flags, float spin, float gain,
                             float* out_col_rgba, float* out_blackout_rgba_or_NULL);
+
+/* Beamed disc shades: bh_shade_lens_disc with a disc hit's colour scaled by the fourth power of the frequency ratio g
+ * between a Keplerian emitter in the disc and a static observer far away -- Doppler beaming and gravitational redshift:
+ * the approaching side bright, the receding side dim, the inner edge darkened (not in the reference).  g is formed at
+ * the hit from the hit map's p and the arrival map's d alone: in this integrator the acceleration is radial, so
+ * L = p x d is conserved along a ray, and so is E^2 = |d|^2 - distortion_power * rs * |L|^2 / r^3 (to the RK4 step's
+ * accuracy); the disc, 3 rs .. 6 rs, starts at the Schwarzschild ISCO, so a circular orbit exists over all of it.
+ * The colour of one record (normative; fp32, one rounding per op, no FMA, dot(a, b) = (ax*bx + ay*by) + az*bz):
+ *   1 to 5. bh_shade_lens_disc's.  Only a record that reaches step 5 -- a surface record of a scene with BH_SCENE_DISC
+ *      whose hit p = (x, y, z) has sd < 0.001f -- goes on, with c its colour after the gain, rho, ri and rs as in step
+ *      3 and d = (dx, dy, dz) its entry of the arrival map; no other record's arrival enters its colour.
+ *   6. r2 = dot(p, p); r = sqrtf(r2);
+ *      L = (y*dz - z*dy, z*dx - x*dz, x*dy - y*dx); h2 = dot(L, L);
+ *      E2 = dot(d, d) - ((distortion_power * rs) * h2) / (r2 * r); E = sqrtf(E2).
+ *   7. om = sqrtf((0.5f * rs) / ((rho * rho) * rho))   -- Kepler: Omega^2 = M / rho^3 with M = rs / 2;
+ *      q = 1.0f - (1.5f * rs) / rho                    -- 1 / (u^t)^2 of the circular orbit;
+ *      den = 1.0f - ((float)sense * om) * (L.y / E)    -- the traced ray runs backwards, so the photon's angular
+ *      momentum about the disc's sense of rotation is L.y of p x d;
+ *      g = sqrtf(q) / den.  Unless E2 > 0, q > 0, den > 0 and g < INFINITY are all true, g = 1: a zero arrival, NaN
+ *      components, an rs at which the terms are not finite.
+ *   8. ge = 1.0f + beam * (g - 1.0f); f = (ge * ge) * (ge * ge); colour = c * f per channel -- the bolometric
+ *      I ~ g^4.  f is finite: a g other than 1 has q in (0, 1) and den >= 2^-24, so g < 2^24.
+ * blackout_col, ss, the tree and the encode are bh_shade_lens_disc's.  beam = 0 gives bh_shade_lens_disc's bytes for
+ * any arrival map; scaling every arrival by a power of two leaves the bytes unchanged (short of overflow).
+ * Not applied: the camera's own gravitational blueshift (uniform over the frame: it belongs in `gain`) and the
+ * camera's velocity -- g is the ratio seen by a static observer far away. */
+typedef struct {
+    const float* arrivals;    /* the lens's arrival map: (ss*height) x (ss*width) x 3 floats, device, 4-byte aligned */
+    float beam;               /* 0 .. 1: 0 = bh_shade_lens_disc's bytes, 1 = the full factor */
+    int32_t sense;            /* +1: the disc's matter moves towards growing atan2(z, x), the way a growing `spin`
+                                 carries the texture; -1: the other way */
+    float distortion_power;   /* the uniforms' distortion_power the lens was marched with; finite */
+} bh_beam_desc;
+/* bh_shade_lens_disc's contract and refusals; BH_ERR_INVALID_ARG also for a NULL beam desc, a NULL or misaligned
+ * arrivals, a sense other than +1 or -1, a beam outside [0, 1] or not finite, a distortion_power that is not finite. */
+int bh_shade_lens_disc_beamed(bh_ctx* ctx, const bh_shade_desc* desc, const bh_disc_desc* disc_desc,
+                              const bh_beam_desc* beam_desc, void* hip_stream);
+/* Host only: bh_lens_shade_disc_host for bh_shade_lens_disc_beamed -- arrivals: (ss*height) x (ss*width) x 3 floats. */
+int bh_lens_shade_disc_beamed_host(const bh_lens_px* lens, const float* hits, uint32_t width, uint32_t height, uint32_t ss,
+                                   const uint8_t* sky_rgba8, uint32_t sky_w, uint32_t sky_h,
+                                   const uint8_t* disc_rgba8, uint32_t n_phi, uint32_t n_r,
+                                   float rs, uint32_t scene_flags, float spin, float gain,
+                                   float* out_col_rgba, float* out_blackout_rgba_or_NULL,
+                                   const float* arrivals, float beam, int32_t sense, float distortion_power);
 
 /* Bloom::render (src/bloom.rs:53-71): the reference's Kawase bloom + remix chain over the scene's two
  * targets, on BGRA8-sRGB images (bh_render with BH_OUT_BGRA8_SRGB): `col` (full_image_input),

@@ -35,7 +35,13 @@ Depth of field: the ss x ss samples of a pixel start on a thin lens of radius A 
 A textured, turning accretion disc: each view is marched into a lens map and a hit map (bh_render_lens_hits) and
 shaded with the disc texture turned by TURNS_PER_FRAME * frame turns of its inner edge (bh_shade_lens_disc).  A frame
 whose camera did not move re-uses the last march: with a still camera (an empty --script) the path is one march and
-one shade per frame."""
+one shade per frame.
+
+    python tools/render_path.py --disc synthetic --disc-spin 0.01 --disc-beam 1 --script "" --frames 120
+The same with Doppler beaming and gravitational redshift: the march also writes an arrival map
+(bh_march_lens_arrivals) and the shade scales every disc hit by the fourth power of a Keplerian emitter's frequency
+ratio (bh_shade_lens_disc_beamed) -- the approaching side bright, the receding side dim, the inner edge darkened.
+--disc-sense -1 turns the matter the other way (a negative --disc-spin carries the texture that way)."""
 import argparse
 import dataclasses
 import json
@@ -90,6 +96,10 @@ p.add_argument("--disc", default=None, metavar="{synthetic,IMAGE}",
 p.add_argument("--disc-spin", type=float, default=0.0, metavar="TURNS_PER_FRAME",
                help="with --disc: turns of the disc's inner edge per frame (Keplerian: slower further out)")
 p.add_argument("--disc-gain", type=float, default=1.0, metavar="G", help="with --disc: the disc colour's multiplier")
+p.add_argument("--disc-beam", type=float, default=None, metavar="B",
+               help="with --disc: beam the disc -- 0..1, 0 the unbeamed colours, 1 the full Doppler and redshift factor g^4")
+p.add_argument("--disc-sense", type=int, default=1, choices=(1, -1),
+               help="with --disc-beam: +1 the matter moves the way a growing --disc-spin carries the texture, -1 the other way")
 args = p.parse_args()
 if args.disc and (args.projection or args.shutter > 1 or args.adaptive is not None or args.sky_frames
                   or args.sky_filter != "none" or args.aperture is not None):
@@ -99,6 +109,10 @@ if not args.disc and (args.disc_spin != 0.0 or args.disc_gain != 1.0):
     p.error("--disc-spin and --disc-gain go with --disc")
 if not (abs(args.disc_spin) < float("inf") and 0.0 <= args.disc_gain < float("inf")):
     p.error("--disc-spin must be finite and --disc-gain finite and 0 or more")
+if args.disc_beam is None and args.disc_sense != 1:
+    p.error("--disc-sense goes with --disc-beam")
+if args.disc_beam is not None and not (args.disc and 0.0 <= args.disc_beam <= 1.0):
+    p.error("--disc-beam goes with --disc and lies in 0..1")
 mip = args.sky_filter == "mip"
 proj, proj_deg = None, None
 if args.projection is not None:
@@ -252,16 +266,19 @@ if args.disc:  # a lens and a hit map per view, a disc shade per frame
     k, marches = args.ss, 0
     lens = torch.empty((k * H, k * W, 2), dtype=torch.float32, device="cuda")
     hits = torch.empty((k * H, k * W, 3), dtype=torch.float32, device="cuda")
+    beam = {}  # --disc-beam: the arrival map beside the hit map, for the march and for the shade
+    if args.disc_beam is not None:
+        beam = dict(arrivals=torch.empty((k * H, k * W, 3), dtype=torch.float32, device="cuda"))
     for f in range(args.frames):
         for key, a, b in keys:
             ctrl.process_key(key, a <= f <= b)
         cam, moved = ctrl.update_camera(cam, args.dt)
         if f == 0 or moved:
             scene.update(cam)
-            scene.render_lens(lens, width=k * W, height=k * H, hits=hits)
+            scene.render_lens(lens, width=k * W, height=k * H, hits=hits, **beam)
             marches += 1
         scene.shade(lens, col, bo, fmt=bh.BH_OUT_BGRA8_SRGB, ss=k, hits=hits, disc=disc, spin=args.disc_spin * f,
-                    gain=args.disc_gain)
+                    gain=args.disc_gain, **beam, **(dict(beam=args.disc_beam, sense=args.disc_sense) if beam else {}))
         scene.bloom(col, bo, surf)
         if not args.no_png:
             write_png(out_dir / f"frame_{f:04d}.png", surf.cpu().numpy())
@@ -317,5 +334,5 @@ for f in range(0 if args.sky_frames or posed or args.disc else args.frames):
 torch.cuda.synchronize()
 dt = time.perf_counter() - t0
 (out_dir / "path.json").write_text(json.dumps(log, indent=0))
-print(json.dumps({"frames": args.frames, "width": W, "height": H, "ss": args.ss, "adaptive": args.adaptive, "shutter": args.shutter, "sky_filter": args.sky_filter, "projection": args.projection, "map_uploads": map_uploads, "disc": args.disc, "marches": marches, "seconds": round(dt, 3),
+print(json.dumps({"frames": args.frames, "width": W, "height": H, "ss": args.ss, "adaptive": args.adaptive, "shutter": args.shutter, "sky_filter": args.sky_filter, "projection": args.projection, "map_uploads": map_uploads, "disc": args.disc, "disc_beam": args.disc_beam, "marches": marches, "seconds": round(dt, 3),
                   "frames_per_s_incl_png": round(args.frames / dt, 2), "out": str(out_dir)}))
